@@ -35,6 +35,17 @@ Multi-GPU (element-range sharding):
     (torch.distributed.run as a child process, before anything touches a GPU);
     under a launcher, --gpus must equal WORLD_SIZE.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up (the W steps,
+then 1 s of the step to bring the GPU out of idle: settle()), times the K steps of
+the `value`'s own form and prints the line; every field that needs a run
+of its own is null. --full adds those runs: the other step form and the eager time,
+per-kernel times and the roofline, the N-rank parity check, the `approx` block, the
+extra workloads, the host-buffer paths, the strong block and the CPU baseline (the
+--no-* options and --extras trim them). --dump-outputs DIR writes what the last
+timed step computed as DIR/{merged_text,merged_f32,encoded_text}.npy (float32; an
+array over its cap as a fixed seeded sample): the inputs are synthesised from a fixed
+seed, so two builds can be compared output for output.
+
 Output: ONE JSON line on rank 0 (see DESIGN.md §6 for every field).
 """
 from __future__ import annotations
@@ -63,8 +74,8 @@ WORKLOADS = {
     "synth1m_256": ("synth1m", 256, "north-star target: 1M-float buckets, C=256 (SURVEY.md §8d)"),
     "synth4m_4096": ("synth4m", 4096, "configs[4]: synthetic 4M-float buckets x 4096 clients"),
 }
-HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec, /opt/skills/guides/MI355X_MICROARCH.md:36
-HBM_COPY_GBS = 6290.0  # measured copy ceiling, same line (SURVEY.md §8d asks for both)
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec
+HBM_COPY_GBS = 6290.0  # measured copy ceiling (SURVEY.md §8d asks for both)
 # what actually bounds each aggregation kernel: none is HBM-bound
 LIMITER = {
     "k_update_pipe": "latency of the serial client chain (one consumer wave per tile; DESIGN.md 4.2)",
@@ -181,6 +192,44 @@ def kernel_ms(torch, fn, reps: int = 10, rounds: int = 3) -> float:
     return float(np.mean(best))
 
 
+DUMP_SEED = 20240607
+# elements written per array (float32): the merged text and merged_f32 of the headline
+# (5.6 M / 1 M) in full, the M encoded uploads as a sample; 3 arrays stay under 64 MB
+DUMP_CAP = {"merged_text": 6 << 20, "merged_f32": 6 << 20, "encoded_text": 2 << 20}
+
+
+def dumper(torch, outdir: str):
+    """--dump-outputs: a function that writes {name: device tensor} as outdir/<name>.npy
+    (float32; Base64 bytes as their values 0..255). An array over its DUMP_CAP is
+    written as a fixed sample: the elements at DUMP_CAP[name] flat indices drawn once
+    from a seeded generator (the same for every run of the same shape), in index order."""
+    def dump(named):
+        os.makedirs(outdir, exist_ok=True)
+        for name, t in named.items():
+            flat = t.reshape(-1)
+            cap = DUMP_CAP[name]
+            if flat.numel() > cap:
+                idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), cap))
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+            np.save(os.path.join(outdir, name + ".npy"), flat.cpu().numpy().astype(np.float32, copy=False))
+    return dump
+
+
+SETTLE_S = 1.0
+
+
+def settle(torch, fn):
+    """Run fn (the step about to be timed) for SETTLE_S seconds before the clock. A plain run
+    starts its timed steps on a GPU that has just left idle: measured on synth1m_256,
+    20 steps right after 3 warm-up steps take 1.113 ms each against 1.072 ms in steady
+    state (200 or 2000 steps, or the same 20 after the other blocks of a --full run);
+    0.2 s of the step is enough to reach it, 1 s and 3 s give the same figure."""
+    end = time.perf_counter() + SETTLE_S
+    while time.perf_counter() < end:
+        fn()
+        torch.cuda.synchronize()
+
+
 def steps_per_graph(steps: int, cap: int = 10) -> int:
     return max(d for d in range(1, min(cap, steps) + 1) if steps % d == 0)
 
@@ -219,14 +268,16 @@ def all_gather_fn(torch, dist, world, src, out):
     return f
 
 
-def time_pipelined(torch, dist, codec, sh, steps, warmup, world):
+def time_pipelined(torch, dist, codec, sh, steps, warmup, world, full=True, dump=None):
     """The same steps software-pipelined over two upload buffers: step i
     aggregates batch i (buffer i % 2) and encodes batch i+1 into the other buffer
     in one launch (fleet_update_encode_device; k_update_encode = the stream
     update's blocks + the client encode's blocks). Per step: one aggregation and
     one client encode, as in the sequential step; batch 0 is encoded before the
     clock starts. Graph-replayed like the sequential step (an even number of
-    steps per graph, so every replay starts on buffer 0)."""
+    steps per graph, so every replay starts on buffer 0). full: the launch's device
+    time (kernel_ms) in graph replays of its own after the timed steps. dump: called
+    with the last timed step's outputs."""
     import fleet_amd as F
     if not sh.n_local or sh.strong:
         return None
@@ -255,20 +306,27 @@ def time_pipelined(torch, dist, codec, sh, steps, warmup, world):
         g.replay()
     if g1:
         g1.replay()
+    if not full:
+        settle(torch, lambda: ((g or g1).replay(), (g1 or g).replay()))
     seq = ([g.replay] * (E // G) if G else []) + ([g1.replay] if g1 else [])
     it = iter(seq)
     elapsed = run_timed(torch, dist, world, lambda: next(it)(), len(seq))
     codec.check()
     del g, g1
-    fused_ms = kernel_ms(torch, lambda: (step(), step()), reps=5) / 2  # a buffer-0/1 pair per graph entry
-    codec.check()
+    if dump:  # the last timed step (index steps - 1) encoded into buffer steps % 2
+        dump({"merged_text": sh.merged[:sh.L], "merged_f32": sh.merged_f32[:sh.n_local],
+              "encoded_text": bufs[steps % 2]})
+    fused_ms = None
+    if full:
+        fused_ms = kernel_ms(torch, lambda: (step(), step()), reps=5) / 2  # a buffer-0/1 pair per graph entry
+        codec.check()
     del bufs[1]
     return {"ms_per_step": elapsed / steps * 1e3,
             "gib_s": world * sh.M * sh.n_local * 4 / (elapsed / steps) / 2**30,
             "steps_per_graph": G, "kernel": F.update_encode_kernel(sh.L), "kernel_ms": fused_ms}
 
 
-def strong_pipelined(torch, dist, codec, name, steps, warmup, rank, world):
+def strong_pipelined(torch, dist, codec, name, steps, warmup, rank, world, full=True, dump=None):
     """`value`: strong scaling of ONE fixed problem. The rank's column window of
     every upload is a bucket of its own (n_local values, the header slots that
     fall inside it): the pipelined step (fleet_update_encode_device on the window,
@@ -280,7 +338,9 @@ def strong_pipelined(torch, dist, codec, name, steps, warmup, rank, world):
     launch, the slice buffers double-buffered by step parity, and the step that
     reuses a slice buffer first waits for the gather that read it (every gather
     completes inside the timed region; FLEET_BENCH_GATHER_OVERLAP=0 runs them in
-    line)."""
+    line). full: rank 0's launch timed on its own after the steps (kernel_ms_rank0,
+    exposed_ms). dump (rank 0): called with the last step's gathered merged text, the
+    rank's merged_f32 window and the window's next batch."""
     import fleet_amd as F
     from fleet_amd.layouts import LAYOUTS
     lay_name, M, note = WORKLOADS[name]
@@ -318,6 +378,8 @@ def strong_pipelined(torch, dist, codec, name, steps, warmup, rank, world):
     graphs = [graph_of(torch, lambda: local(0), 1), graph_of(torch, lambda: local(1), 1)]
     graphs[0].replay()
     graphs[1].replay()
+    if not full:
+        settle(torch, lambda: (graphs[0].replay(), graphs[1].replay()))
     state = {"i": 0}
     works = [None, None]
 
@@ -352,15 +414,19 @@ def strong_pipelined(torch, dist, codec, name, steps, warmup, rank, world):
             a, b = group_range(G, world, r)
             base = r * 16 * wmax if world > 1 else 0
             parts.append((outs[kl] if world > 1 else srcs[kl])[base: base + 16 * (b - a)])
-        gathered = torch.cat(parts).cpu().numpy()
-    kern_ms = kernel_ms(torch, lambda: (local(0), local(1)), reps=5) / 2
+        gathered = torch.cat(parts)
+        if dump:
+            dump({"merged_text": gathered[:sh.L], "merged_f32": sh.merged_f32[:sh.n_local],
+                  "encoded_text": bufs[steps % 2]})
+        gathered = gathered.cpu().numpy()
+    kern_ms = kernel_ms(torch, lambda: (local(0), local(1)), reps=5) / 2 if full else None
     res = {"workload": name, "note": note, "clients": M, "n_up_total": layout.n_up, "n_up_per_rank": sh.n_local,
            "groups_per_rank_max": wmax, "ms_per_step": elapsed / steps * 1e3,
            "gib_s": M * layout.n_up * 4 / (elapsed / steps) / 2**30,
            "kernel": F.update_encode_kernel(L_loc), "kernel_ms_rank0": kern_ms,
            # what the step costs beyond rank 0's launch: the all_gather's exposed part plus
            # the step's launch gaps and any rank imbalance (the clock is the max over ranks)
-           "exposed_ms": elapsed / steps * 1e3 - kern_ms,
+           "exposed_ms": elapsed / steps * 1e3 - kern_ms if full else None,
            "step": "pipelined launch on the rank's column window + all_gather of the merged slices (inside; "
                    + ("issued async, overlapping the next step's launch)" if overlap else "in line)")}
     del graphs, bufs, sh, srcs, outs
@@ -443,12 +509,17 @@ def approx_client_sharded(torch, dist, codec, name, steps, warmup, rank, world, 
     return res
 
 
-def time_workload(torch, dist, codec, name, steps, warmup, rank, world, graph=True, pipelined_step=True):
+def time_workload(torch, dist, codec, name, steps, warmup, rank, world, graph=True, pipelined_step=True,
+                  full=True, sequential=False, dump=None):
     """Weak-scaling measurement of `name`: times `steps` steps. graph=True: a
     step (encode + aggregation) is captured once into a HIP graph of G steps
     and replayed steps/G times; graph=False: eager launches. N>1: the
     all_gather of the merged slices is timed after the steps, on its own
-    (exchange_ms)."""
+    (exchange_ms).
+
+    full=False times only the form the headline reports -- the pipelined step, or
+    with sequential=True (or graph=False) the sequential one -- and leaves every
+    other figure None. dump: called with the outputs of that form's last timed step."""
     import fleet_amd as F
     from fleet_amd.layouts import LAYOUTS
     lay_name, M, note = WORKLOADS[name]
@@ -456,45 +527,66 @@ def time_workload(torch, dist, codec, name, steps, warmup, rank, world, graph=Tr
     sh = Shard(codec, torch, layout, M, rank, world)
     gathered = torch.empty((world * sh.pitch,), dtype=torch.uint8, device=sh.merged.device) if world > 1 else None
 
+    headline_pipelined = bool(graph and pipelined_step and not sequential)
+
     def local():
         sh.encode()
         sh.aggregate()
 
-    for _ in range(warmup):
-        local()
-    torch.cuda.synchronize()
-    codec.check()
+    def dump_sequential():
+        if dump and not headline_pipelined:
+            dump({"merged_text": sh.merged[:sh.L], "merged_f32": sh.merged_f32[:sh.n_local], "encoded_text": sh.text})
 
-    eager_elapsed = run_timed(torch, dist, world, local, steps)
-    codec.check()
-    eager_ms = eager_elapsed / steps * 1e3
-
-    # per-kernel device time (roofline): graph of 10 back-to-back launches each
-    enc_ms = kernel_ms(torch, sh.encode)
-    upd_ms = kernel_ms(torch, sh.aggregate)
-    codec.check()
-
-    elapsed = eager_elapsed
+    elapsed = eager_ms = enc_ms = upd_ms = None
     G = 1
-    if graph:
-        G = steps_per_graph(steps)
-        g = graph_of(torch, local, G)
-        for _ in range(max(1, warmup // G)):
-            g.replay()
-        elapsed = run_timed(torch, dist, world, g.replay, steps // G)
+    if full or not headline_pipelined:
+        for _ in range(warmup):
+            local()
+        torch.cuda.synchronize()
         codec.check()
-        del g
-    pipelined = time_pipelined(torch, dist, codec, sh, steps, warmup, world) if (graph and pipelined_step) else None
+
+        if full or not graph:
+            if not full:
+                settle(torch, local)
+            elapsed = run_timed(torch, dist, world, local, steps)
+            codec.check()
+            eager_ms = elapsed / steps * 1e3
+            if not graph:
+                dump_sequential()
+
+        if full:
+            # per-kernel device time (roofline): graph of 10 back-to-back launches each
+            enc_ms = kernel_ms(torch, sh.encode)
+            upd_ms = kernel_ms(torch, sh.aggregate)
+            codec.check()
+
+        if graph:
+            G = steps_per_graph(steps)
+            g = graph_of(torch, local, G)
+            for _ in range(max(1, warmup // G)):
+                g.replay()
+            if not full:
+                settle(torch, g.replay)
+            elapsed = run_timed(torch, dist, world, g.replay, steps // G)
+            codec.check()
+            dump_sequential()
+            del g
+    pipelined = None
+    if graph and pipelined_step and (full or headline_pipelined):
+        pipelined = time_pipelined(torch, dist, codec, sh, steps, warmup, world, full,
+                                   dump if headline_pipelined else None)
     exchange_ms = None
-    if world > 1:
+    if world > 1 and full:
         exchange = all_gather_fn(torch, dist, world, sh.merged, gathered)
         exchange()
         exchange_ms = run_timed(torch, dist, world, exchange, 5) / 5 * 1e3
         if not torch.equal(gathered[rank * sh.pitch:(rank + 1) * sh.pitch], sh.merged):
             raise RuntimeError("all_gather returned a different merged slice")
-    ms = elapsed / steps * 1e3
     total_bytes_fp32 = world * M * sh.n_local * 4
-    gib_s = total_bytes_fp32 / (elapsed / steps) / 2**30
+    ms = gib_s = None
+    if elapsed is not None:
+        ms = elapsed / steps * 1e3
+        gib_s = total_bytes_fp32 / (elapsed / steps) / 2**30
     upd_b, enc_b = sh.algorithmic_bytes()
     res = {
         "workload": name, "note": note, "layout": lay_name, "clients": M, "n_up_per_rank": sh.n_local,
@@ -502,8 +594,9 @@ def time_workload(torch, dist, codec, name, steps, warmup, rank, world, graph=Tr
         "graph": graph, "steps": steps, "steps_per_graph": G, "eager_ms_per_step": eager_ms, "exchange_ms": exchange_ms,
         "update_kernel": F.update_kernel(sh.L),
         "update_bytes": upd_b, "encode_bytes": enc_b,
-        "update_gbs": upd_b / (upd_ms * 1e-3) / 1e9, "encode_gbs": enc_b / (enc_ms * 1e-3) / 1e9,
-        "element_clients_per_s": world * M * sh.n_local / (elapsed / steps),
+        "update_gbs": upd_b / (upd_ms * 1e-3) / 1e9 if full else None,
+        "encode_gbs": enc_b / (enc_ms * 1e-3) / 1e9 if full else None,
+        "element_clients_per_s": world * M * sh.n_local / (elapsed / steps) if elapsed is not None else None,
         "pipelined": pipelined,
     }
     del sh
@@ -511,10 +604,11 @@ def time_workload(torch, dist, codec, name, steps, warmup, rank, world, graph=Tr
     return res
 
 
-def strong_device(torch, dist, codec, name, steps, warmup, rank, world):
+def strong_device(torch, dist, codec, name, steps, warmup, rank, world, dump=None):
     """Strong scaling of ONE fixed problem split over the ranks (device-resident):
     step = encode + aggregation of this rank's window; timed once with the
-    all_gather of the merged slices inside every step and once without it."""
+    all_gather of the merged slices inside every step and once without it.
+    dump (rank 0): called with the gather-inside run's last outputs."""
     from fleet_amd.layouts import LAYOUTS
     lay_name, M, note = WORKLOADS[name]
     layout = LAYOUTS[lay_name]
@@ -540,6 +634,11 @@ def strong_device(torch, dist, codec, name, steps, warmup, rank, world):
     torch.cuda.synchronize()
     codec.check()
     inside = run_timed(torch, dist, world, with_gather, steps) / steps
+    if dump and rank == 0:
+        whole = sh.merged[: 16 * sh.groups] if world == 1 else torch.cat(
+            [out[r * 16 * wmax: r * 16 * wmax + 16 * (b - a)]
+             for r, (a, b) in enumerate(group_range(G, world, q) for q in range(world))])
+        dump({"merged_text": whole[:sh.L], "merged_f32": sh.merged_f32[:sh.n_local], "encoded_text": sh.text})
     outside = run_timed(torch, dist, world, local, steps) / steps
     codec.check()
     if world > 1 and not torch.equal(out[rank * 16 * wmax: rank * 16 * wmax + 16 * sh.groups],
@@ -840,7 +939,18 @@ def main():
     ap.add_argument("--e2e", default="synth1m_256,cifar10_256,mnist64",
                     help="workloads of the host-buffer (PCIe-inclusive) measurement (N=1)")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the other step forms, per-kernel times and "
+                         "the roofline, the approx block, the extra workloads, the host-buffer paths, the strong "
+                         "block, the N-rank parity check and the CPU baseline. Without it only the `value`'s own "
+                         "steps are run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step of the `value`'s path computed "
+                         "(merged_text, merged_f32, encoded_text) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    full = args.full
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -878,13 +988,21 @@ def main():
     import fleet_amd as F
     codec = F.Codec(local)
 
-    main_res = time_workload(torch, dist, codec, args.workload, args.steps, args.warmup, rank, world, args.graph)
+    # the outputs of the path `value` times: --strong's configs[4] step, at N > 1 the
+    # strong-scaling step, else the workload's own step
+    dump = dumper(torch, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    strong_is_value = world > 1 and bool(args.graph)
+    main_res = time_workload(torch, dist, codec, args.workload, args.steps, args.warmup, rank, world, args.graph,
+                             full=full, sequential=args.sequential,
+                             dump=None if (args.strong or strong_is_value) else dump)
     strong_value = None
     exact = None  # rank 0: the N = 1 problem's merged bytes (full width, one GPU)
-    if world > 1 and args.graph:
-        strong_value = strong_pipelined(torch, dist, codec, args.workload, args.steps, args.warmup, rank, world)
+    if strong_is_value:
+        strong_value = strong_pipelined(torch, dist, codec, args.workload, args.steps, args.warmup, rank, world,
+                                        full=full, dump=None if args.strong else dump)
         gathered = strong_value.pop("gathered")
-        if rank == 0:
+        strong_value["parity"] = strong_value["parity_check"] = None
+        if rank == 0 and full:
             exact = full_width_merged(torch, codec, args.workload)
             strong_value["parity"] = bool(gathered is not None and np.array_equal(gathered, exact))
             strong_value["parity_check"] = ("rank 0's gathered merged text (every rank's slice) == the full-width "
@@ -892,18 +1010,21 @@ def main():
             if not strong_value["parity"]:
                 print("bench.py: the N-rank merged text differs from the 1-GPU text of the same problem",
                       file=sys.stderr)
-    elif rank == 0:
+    elif rank == 0 and full:
         exact = full_width_merged(torch, codec, args.workload)
-    approx = approx_client_sharded(torch, dist, codec, args.workload, max(3, args.steps // 4), 1, rank, world, exact)
+    approx = None
+    if full:
+        approx = approx_client_sharded(torch, dist, codec, args.workload, max(3, args.steps // 4), 1, rank, world,
+                                       exact)
     # the host-buffer paths before the extras: after the 150 GiB synth4m_4096 extra the
     # process's small pinned-host copies run 2-3x slower (measured on MNIST-64: 0.81 vs
     # 0.30 ms), an allocator-state effect that is not the path's
     e2e = None
-    if world == 1 and not args.no_e2e:
+    if full and world == 1 and not args.no_e2e:
         e2e = {w: end_to_end(torch, codec, w) for w in args.e2e.split(",") if w}
 
     extras = {}
-    if world == 1 and args.extras:
+    if full and world == 1 and args.extras:
         for w in [x for x in args.extras.split(",") if x and x != args.workload]:
             # a few steps of the large extras; the small ones get enough steps that the
             # timed region is not one or two graph launches (mnist64's 17 us step: 4 steps
@@ -912,11 +1033,14 @@ def main():
             extras[w] = time_workload(torch, dist, codec, w, n, 2, rank, world, args.graph)
 
     strong = None
-    if args.strong or not args.no_strong_block:
-        ssteps = max(3, args.steps // 4)
+    if args.strong or (full and not args.no_strong_block):
+        # the block's own step count; as the `value` (--strong), exactly --steps and --warmup
+        ssteps, swarm = (args.steps, args.warmup) if args.strong else (max(3, args.steps // 4), 1)
         strong = {"scaling": "strong", "n_gpus": world,
-                  "device": strong_device(torch, dist, codec, "synth4m_4096", ssteps, 1, rank, world),
-                  "host_staged": strong_host(torch, dist, codec, "cifar100_1024", ssteps, rank, world)}
+                  "device": strong_device(torch, dist, codec, "synth4m_4096", ssteps, swarm, rank, world,
+                                          dump if args.strong else None),
+                  "host_staged": strong_host(torch, dist, codec, "cifar100_1024", ssteps, rank, world)
+                  if full and not args.no_strong_block else None}
 
     if rank != 0:
         if world > 1:
@@ -924,27 +1048,30 @@ def main():
             dist.destroy_process_group()
         return
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if full and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(args.workload, args.cpu_budget)
     r = main_res
-    upd_roof = {"kernel": r["update_kernel"], "achieved": r["update_gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": r["update_gbs"] / HBM_PEAK_GBS, "frac_of_copy_ceiling": r["update_gbs"] / HBM_COPY_GBS,
-                "limiter": LIMITER.get(r["update_kernel"].split("<")[0], "VALU issue"),
-                "bytes_per_launch": r["update_bytes"], "kernel_ms": r["update_kernel_ms"]}
-    traffic = pmc_traffic(args.workload, r["update_kernel"]) if world == 1 else None
-    sq = sq_valu(args.workload, r["update_kernel"])
-    upd_roof.update({"valu_lane_instr_per_element_client": sq[0] if sq else None, "valu_source": sq[1] if sq else None,
-                     "traffic": traffic[0] if traffic else None,
-                     "traffic_source": f"{traffic[2]} ({traffic[1]})" if traffic else None})
+    upd_roof = None  # the roofline rests on per-kernel times: runs of their own (--full)
+    if full:
+        upd_roof = {"kernel": r["update_kernel"], "achieved": r["update_gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": r["update_gbs"] / HBM_PEAK_GBS, "frac_of_copy_ceiling": r["update_gbs"] / HBM_COPY_GBS,
+                    "limiter": LIMITER.get(r["update_kernel"].split("<")[0], "VALU issue"),
+                    "bytes_per_launch": r["update_bytes"], "kernel_ms": r["update_kernel_ms"]}
+        traffic = pmc_traffic(args.workload, r["update_kernel"]) if world == 1 else None
+        sq = sq_valu(args.workload, r["update_kernel"])
+        upd_roof.update({"valu_lane_instr_per_element_client": sq[0] if sq else None,
+                         "valu_source": sq[1] if sq else None,
+                         "traffic": traffic[0] if traffic else None,
+                         "traffic_source": f"{traffic[2]} ({traffic[1]})" if traffic else None})
     pipe = r.get("pipelined") if isinstance(r.get("pipelined"), dict) and "gib_s" in r["pipelined"] else None
     value, ms, scaling = r["gib_s"], r["ms_per_step"], "weak"
     step_form = "sequential: k_encode_f32 then the aggregation kernel, per step"
-    roofline = dict(upd_roof, bound="hbm", workload=args.workload)
+    roofline = dict(upd_roof, bound="hbm", workload=args.workload) if full else None
     if pipe and not args.sequential:
         value, ms = pipe["gib_s"], pipe["ms_per_step"]
         step_form = ("pipelined: step i aggregates batch i and encodes batch i+1 into the other upload buffer, "
                      f"one {pipe['kernel']} launch (fleet_update_encode_device); batch 0 encoded before the clock")
-        if pipe["kernel"].startswith("k_update_encode"):
+        if full and pipe["kernel"].startswith("k_update_encode"):
             fb = r["update_bytes"] + r["encode_bytes"]
             fgbs = fb / (pipe["kernel_ms"] * 1e-3) / 1e9
             ftr = pmc_traffic(args.workload, pipe["kernel"]) if world == 1 else None
@@ -984,6 +1111,7 @@ def main():
         "value": value,
         "unit": "GiB/s",
         "n_gpus": world,
+        "full": full,
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": ms,
@@ -1009,7 +1137,7 @@ def main():
         "strong": strong,
         "weak": weak,
         "strong_value": strong_value,
-        "parity": None if strong_value is None else {"n_rank_equals_1_gpu": strong_value["parity"],
+        "parity": None if strong_value is None or not full else {"n_rank_equals_1_gpu": strong_value["parity"],
                                                      "check": strong_value["parity_check"]},
         "approx": approx,
         "extra": extras,

@@ -8,7 +8,7 @@ for rep in $(seq ${REPS:-2}); do
   for w in $WL; do
     for lp in $LIBS; do
       lab=${lp%%=*}; rest=${lp#*=}; lib=${rest%%,*}; envs=""; [ "$rest" != "$lib" ] && envs=${rest#*,}
-      env ${envs//,/ } FLEET_CODEC_LIB=$PWD/$lib timeout -k 10 300 python bench.py --workload $w --extras= --no-cpu-baseline --no-e2e \
+      env ${envs//,/ } FLEET_CODEC_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --workload $w --extras= --no-cpu-baseline --no-e2e \
         --no-strong-block --steps ${STEPS:-20} --warmup 3 > gpurun_out/abm.json 2>gpurun_out/abm.err || { tail -5 gpurun_out/abm.err; exit 1; }
       python3 -c "
 import json; r=json.loads(open('gpurun_out/abm.json').read().strip().splitlines()[-1])

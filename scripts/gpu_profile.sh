@@ -6,7 +6,7 @@ WL=${*:-"synth1m_256 cifar10_256 mnist64"}
 O=${OUTROOT:-$PWD/gpurun_out}/$TAG; mkdir -p $O
 R=$PWD
 export TMPDIR=/tmp
-B="--extras= --no-cpu-baseline --no-e2e --no-strong-block"
+B="--full --extras= --no-cpu-baseline --no-e2e --no-strong-block"
 for W in $WL; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$W -o run -- python3 $R/bench.py --workload $W $B --steps 100 --warmup 3 > $O/trace_$W.log 2>&1 &&
   timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch_$W -o run -- python3 $R/bench.py --workload $W $B --steps 5 --warmup 1 > $O/fetch_$W.log 2>&1 &&

@@ -6,11 +6,11 @@
 # steps:
 #   tests            full pytest -m gpu
 #   smoke            __graft_entry__.smoke()
-#   bench            the default bench line (bench_default.json)
+#   bench            the default bench line with every block (bench.py --full; bench_default.json)
 #   sqlds:W:N:MODE   LDS counters (bank conflicts, unaligned stalls) of strong_probe W at N, MODE
 #   bin:PATH         a prebuilt dev binary
 #   klibs:W1,W2      Kardam vs plain per library build in LIBS (scripts/gpu_kardam_libs.sh)
-#   benchn:N         bench.py --gpus N with every rank on device 0 over gloo (the N-rank path rehearsed)
+#   benchn:N         bench.py --full --gpus N with every rank on device 0 over gloo (the N-rank path rehearsed)
 #   strong[:W]       per-rank pipelined windows of W (default synth1m_256) at N = 1, 2, 4, 8
 #                    on one GPU (scripts/strong_probe.py), fused / update-only
 #   windows:W        W at N = 1 only: the fused step, the update alone, the encode alone
@@ -46,12 +46,12 @@ for step in "$@"; do
       timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || { tail -20 "$O/smoke.log"; exit 1; }
       tail -1 "$O/smoke.log" ;;
     bench)
-      timeout -k 10 900 python3 bench.py > "$O/bench_default.json" 2> "$O/bench_default.err" || { tail -20 "$O/bench_default.err"; exit 1; }
+      timeout -k 10 900 python3 bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err" || { tail -20 "$O/bench_default.err"; exit 1; }
       cut -c1-400 "$O/bench_default.json" ;;
     benchn)
       # the N-rank bench path rehearsed on one GPU: N ranks on device 0, gloo collectives
       # (a readiness check, its times measure nothing)
-      FLEET_BENCH_SAME_DEVICE=1 FLEET_BENCH_BACKEND=gloo timeout -k 10 1200 python3 bench.py --gpus "$arg" --steps 8 \
+      FLEET_BENCH_SAME_DEVICE=1 FLEET_BENCH_BACKEND=gloo timeout -k 10 1200 python3 bench.py --full --gpus "$arg" --steps 8 \
         --warmup 2 > "$O/bench_n${arg}_same_device.json" 2> "$O/bench_n${arg}_same_device.err" \
         || { tail -20 "$O/bench_n${arg}_same_device.err"; exit 1; }
       cut -c1-300 "$O/bench_n${arg}_same_device.json" ;;

@@ -13,7 +13,7 @@ for v in ${VARIANTS:-"A:FLEET_CODEC_LIB=$PWD/ab/libfleetcodec_prev.so" "B:X=1"};
   k=0
   for P in "$P1" "$P2" "$P3"; do
     k=$((k+1))
-    env $env_ timeout -s KILL 120 rocprofv3 --pmc $P --output-format csv -d $O/${lab}_p$k -o run -- python3 bench.py --workload $W --extras= --no-cpu-baseline --no-e2e --no-strong-block --steps 3 --warmup 1 > $O/${lab}_p$k.log 2>&1 || exit 1
+    env $env_ timeout -s KILL 120 rocprofv3 --pmc $P --output-format csv -d $O/${lab}_p$k -o run -- python3 bench.py --full --workload $W --extras= --no-cpu-baseline --no-e2e --no-strong-block --steps 3 --warmup 1 > $O/${lab}_p$k.log 2>&1 || exit 1
   done
   echo "$lab done"
 done
