@@ -105,6 +105,14 @@ def lib() -> C.CDLL:
         "fleet_update_encode_device": (i32, [vp, vp, sz, sz, i32, vp, vp, i32, vp, vp, vp, sz, vp, vp]),
         "fleet_update_kardam_device": (i32, [vp, vp, sz, sz, i32, vp, vp, i32, C.c_double, vp, vp, vp, sz, vp, vp,
                                              vp, vp, vp]),
+        "fleet_acc_create": (i32, [vp, sz, vp, i32, sz, sz, C.POINTER(vp)]),
+        "fleet_acc_destroy": (None, [vp]),
+        "fleet_acc_push": (i32, [vp, vp, sz, C.c_double]),
+        "fleet_acc_push_device": (i32, [vp, vp, C.c_double, vp]),
+        "fleet_acc_count": (i32, [vp]),
+        "fleet_acc_finish": (i32, [vp, vp, sz, szp, vp]),
+        "fleet_acc_finish_device": (i32, [vp, vp, vp, vp]),
+        "fleet_acc_reset": (i32, [vp]),
         "fleet_update_kernel": (C.c_char_p, [sz]),
         "fleet_update_plan_grid": (i32, [sz, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -435,6 +443,12 @@ class Codec:
             return merged, f32[: b64_count(L)].copy()
         return merged
 
+    def accumulator(self, length: int, header_pos, group_begin: int = 0, group_end: Optional[int] = None):
+        """A streaming accumulator (fleet_acc) for uploads of `length` Base64 bytes with the
+        given layout header positions: each upload is folded into a resident sum when it
+        arrives, and ``finish`` returns what ``update`` returns for the same uploads."""
+        return Accumulator(self, length, header_pos, group_begin, group_end)
+
     def update_rows(self, rows: np.ndarray, length: int, dampen: Sequence[float], want_f32: bool = False):
         """fleet_update over a uint8 host array [M, row_pitch] whose row i holds upload i's
         `length` Base64 chars; page-locked rows (register_host) go to HBM without a host copy."""
@@ -760,6 +774,87 @@ class Codec:
                                                  grad_f32.data_ptr(), ws.ctypes.data, wp.ctypes.data, len(ws),
                                                  bs.ctypes.data, fc.ctypes.data, len(bs), float(lr),
                                                  _stream(stream)))
+
+
+class Accumulator:
+    """Streaming aggregation on one context (fleet_acc, include/fleet_codec.h): the
+    reference's `acc` of buffered uploads (CppNNUpdater.java:383-391) kept as the running
+    sum of the chain instead of the uploads themselves. ``push`` is synchronous and
+    transactional (a rejected upload raises and leaves the batch as it was);
+    ``push_device`` is asynchronous and commits at once, a bad upload surfacing as a
+    sticky error at ``finish*`` or a later push until ``reset``."""
+
+    def __init__(self, codec: Codec, length: int, header_pos, group_begin: int = 0, group_end: Optional[int] = None):
+        self.codec = codec
+        self._L = codec._L
+        self.length = int(length)
+        self.groups = (b64_count(self.length) + 2) // 3
+        self.group_begin = int(group_begin)
+        self.group_end = self.groups if group_end is None else min(int(group_end), self.groups)
+        hp = np.ascontiguousarray(header_pos, dtype=np.int32)
+        h = C.c_void_p()
+        self._h = None
+        codec._check(self._L.fleet_acc_create(codec._h, self.length, hp.ctypes.data, len(hp), self.group_begin,
+                                              self.group_end, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.codec, "_h", None):
+            self._L.fleet_acc_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @property
+    def count(self) -> int:
+        return self._L.fleet_acc_count(self._h)
+
+    def push(self, upload, dampen: float) -> None:
+        s = _as_bytes(upload)
+        self.codec._check(self._L.fleet_acc_push(self._h, s, len(s), float(dampen)))
+
+    def push_device(self, u8_tensor, dampen: float, stream=None) -> None:
+        """u8_tensor: a uint8 CUDA tensor holding the whole upload row (>= length bytes)."""
+        if u8_tensor.numel() < self.length:
+            raise ValueError("the tensor is shorter than the accumulator's uploads")
+        self.codec._check(self._L.fleet_acc_push_device(self._h, u8_tensor.data_ptr(), float(dampen), _stream(stream)))
+
+    def finish(self, want_f32: bool = False):
+        """The merged Base64 of the uploads pushed since the last finish (and, with
+        ``want_f32``, decodeFloat of it); the accumulator is then empty. With a group
+        window only the window's bytes / values of the returned buffers are written."""
+        out = np.zeros(self.length + 16, np.uint8)
+        n = C.c_size_t(0)
+        f32 = np.zeros(b64_count(self.length) + 1, np.float32) if want_f32 else None
+        self.codec._check(self._L.fleet_acc_finish(self._h, out.ctypes.data, len(out), C.byref(n),
+                                                   f32.ctypes.data if want_f32 else None))
+        merged = out[: n.value].tobytes()
+        if want_f32:
+            return merged, f32[: b64_count(self.length)].copy()
+        return merged
+
+    def finish_device(self, merged_u8, merged_f32=None, stream=None) -> None:
+        """merged_u8: uint8 CUDA tensor [>= 16 * groups], merged_f32: float32 [>= n values]
+        (whole-upload coordinates); synchronises the stream to report a bad device push."""
+        if merged_u8.numel() < 16 * self.groups or (
+                merged_f32 is not None and merged_f32.numel() < b64_count(self.length)):
+            raise ValueError("merged tensors smaller than the upload's groups")
+        self.codec._check(self._L.fleet_acc_finish_device(self._h, merged_u8.data_ptr(),
+                                                          merged_f32.data_ptr() if merged_f32 is not None else None,
+                                                          _stream(stream)))
+
+    def reset(self) -> None:
+        self.codec._check(self._L.fleet_acc_reset(self._h))
 
 
 def update_multi(codecs: Sequence["Codec"], uploads: Sequence, dampen: Sequence[float], want_f32: bool = False):

@@ -1,0 +1,215 @@
+// fleet_amd/csrc/acc_kernels.hip -- streaming aggregation: one upload folded into a
+// resident sum per launch (k_acc_push), the merged gradient from the sum (k_acc_finish).
+//
+// CppNNUpdater.update is entered once per upload and only buffers it until M have
+// arrived (CppNNUpdater.java:383-391); the chain it then runs over the picked uploads
+// (:420-421, :463-464, :490-508) is serial over clients and independent per element,
+// so one client's step can run when its upload arrives:
+//   y = Q(dec(code))   p = Q((float)((double)y * d))   A = first ? p : Q(A + p)
+// The state A is one fp32 per upload position of the accumulator's group window, read
+// from one buffer and written to the other, so a rejected upload leaves no trace.
+//
+// The batch kernels recompute a lane's whole chain from all M uploads when a value
+// leaves the table stages' domain (chain_general); a fold step no longer has the
+// earlier uploads, so here every stage falls back to the general codec within the step
+// (q_stage_d16x: wave-uniform behind a ballot, never taken by gradient-like data).
+//
+// This unit takes the stage helpers of kernels.hip and none of its kernels.
+#define FLEET_STREAM_TU
+#define FLEET_ACC_TU
+#include "kernels.hip"
+
+namespace fleet {
+
+namespace {
+
+constexpr int kAccNT = 256;
+// header positions a block keeps in LDS for the per-group search (more: from global memory)
+constexpr int kAccLdsHdr = 1024;
+
+typedef float f3u __attribute__((ext_vector_type(3), aligned(4)));
+
+// first index i with hdr[i] >= p0 (hdr sorted)
+__device__ __forceinline__ int acc_lower_bound(const int32_t* hdr, int n_hdr, int64_t p0) {
+  int lo = 0, hi = n_hdr;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (hdr[mid] < p0) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+struct AccShared {
+  B64Tables tab;
+  D16Table dtab;
+  int32_t hdr[kAccLdsHdr];
+};
+
+// tables and the header positions into LDS; returns the list the group search reads
+__device__ __forceinline__ void acc_init(AccShared& sh, const int32_t* __restrict__ hdr, int n_hdr) {
+  b64_tables_init<kAccNT>(&sh.tab);
+  d16_table_init<kAccNT>(&sh.dtab);
+  if (n_hdr <= kAccLdsHdr)
+    for (int i = threadIdx.x; i < n_hdr; i += kAccNT) sh.hdr[i] = hdr[i];
+  __syncthreads();
+}
+
+// bit e = slot p0 + e is a header slot; *first = the index of the group's first header
+__device__ __forceinline__ uint32_t acc_bits_in(const int32_t* hdr, int n_hdr, int64_t p0, int* first) {
+  const int lo = acc_lower_bound(hdr, n_hdr, p0);
+  *first = lo;
+  uint32_t bits = 0;
+  for (int i = lo; i < n_hdr && hdr[i] < p0 + 3; ++i) bits |= 1u << (hdr[i] - p0);
+  return bits;
+}
+__device__ __forceinline__ uint32_t acc_header_bits(const AccShared& sh, const int32_t* __restrict__ hdr, int n_hdr,
+                                                    int64_t p0, int* first) {
+  return n_hdr <= kAccLdsHdr ? acc_bits_in(sh.hdr, n_hdr, p0, first) : acc_bits_in(hdr, n_hdr, p0, first);
+}
+
+}  // namespace
+
+// One upload's step over the groups [g_begin, g_end); `row`, `st_in` and `st_out` hold
+// the window alone (group g at byte 16 (g - g_begin), value 3 (g - g_begin)). Header
+// slots and slots at or past the walk's end carry no chain (their state stays Q(0) =
+// 0); header codes are recorded in hfirst[] by the first push and compared by the
+// later ones (FLEET_ERRBIT_LAYOUT, as the batch kernels do against client 0). A lane
+// owns a group: one 16-byte row load, one 12-byte state load and store.
+__global__ void __launch_bounds__(kAccNT) k_acc_push(const uint8_t* __restrict__ row, const float* __restrict__ st_in,
+                                                     float* __restrict__ st_out, int first, double dampen,
+                                                     int64_t n_up, int64_t g_begin, int64_t g_end,
+                                                     const int32_t* __restrict__ hdr_block,
+                                                     int32_t* __restrict__ hfirst, int* __restrict__ err) {
+  __shared__ AccShared sh;
+  const int n_hdr = hdr_block[1];
+  const int64_t walk_end = hdr_block[2];
+  const int32_t* hdr = hdr_block + 4;
+  acc_init(sh, hdr, n_hdr);
+  const int64_t ng = g_end - g_begin;
+  uint32_t bad = 0, layout_bad = 0;
+  for (int64_t base = (int64_t)blockIdx.x * kAccNT; base < ng; base += (int64_t)gridDim.x * kAccNT) {
+    const int64_t gl = base + threadIdx.x;
+    const bool live = gl < ng;
+    const int64_t gs = live ? gl : 0, g = g_begin + gs;  // dead lanes read group 0 of the window and store nothing
+    const uint4 w = *reinterpret_cast<const uint4*>(row + 16 * gs);
+    f3u a = f3u{0.f, 0.f, 0.f};
+    if (!first) a = *reinterpret_cast<const f3u*>(st_in + 3 * gs);
+    const uint32_t need = needed_chars_mask((int)min<int64_t>(3, max<int64_t>(0, n_up - 3 * g)));
+    int32_t codes[3];
+    if (need == 0xffffu) bad |= live ? b64_decode_group_full(w, &sh.tab, codes) : 0u;
+    else bad |= live ? (b64_decode_group(w, &sh.tab, codes) & need) : 0u;
+    int h0;
+    const uint32_t hbits = acc_header_bits(sh, hdr, n_hdr, 3 * g, &h0);
+    const uint32_t kbits = keep_bits<3>(hbits, true, 3 * g, walk_end);
+    if (__ballot(kbits != 0) != 0) {  // wave-uniform: few waves hold a header
+      int hi = h0;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        if ((hbits >> i) & 1u) {
+          if (live) {
+            if (first) hfirst[hi] = codes[i];
+            else layout_bad |= (uint32_t)(codes[i] != hfirst[hi]);
+          }
+          ++hi;
+        }
+        if ((kbits >> i) & 1u) codes[i] = 0;
+      }
+    }
+    float y0[3], y[3], p[3];
+    dec_stage_d16<3>(y0, codes, &sh.dtab);
+    q_stage_d16x<3>(y, y0, &sh.dtab, sh.tab.var);
+    dampen_stage<3>(y, dampen);
+    q_stage_d16x<3>(p, y, &sh.dtab, sh.tab.var);
+    if (!first) {  // uniform
+      const float sm[3] = {a.x + p[0], a.y + p[1], a.z + p[2]};
+      q_stage_d16x<3>(p, sm, &sh.dtab, sh.tab.var);
+    }
+    if (live) *reinterpret_cast<f3u*>(st_out + 3 * gs) = f3u{p[0], p[1], p[2]};
+  }
+  if (bad) atomicOr(err, FLEET_ERRBIT_BASE64);
+  if (layout_bad) atomicOr(err, FLEET_ERRBIT_LAYOUT);
+}
+
+// merged_code over the window: Q(f32(f64(A) * inv)) encoded, header slots and slots at
+// or past the walk's end the last accepted upload's own codes (mergeFlatGradient,
+// CppNNUpdater.java:507-508), decoded from the accumulator's copy of that row (window
+// coordinates, like `st`). `merged` and `merged_f32` are addressed by the whole
+// upload's group index: Base64 at byte 16 g, fp32 at value 3 g.
+__global__ void __launch_bounds__(kAccNT) k_acc_finish(const uint8_t* __restrict__ last_row,
+                                                       const float* __restrict__ st, double inv, int64_t n_up,
+                                                       int64_t g_begin, int64_t g_end,
+                                                       const int32_t* __restrict__ hdr_block,
+                                                       uint8_t* __restrict__ merged, float* __restrict__ merged_f32) {
+  __shared__ AccShared sh;
+  const int n_hdr = hdr_block[1];
+  const int64_t walk_end = hdr_block[2];
+  const int32_t* hdr = hdr_block + 4;
+  acc_init(sh, hdr, n_hdr);
+  const int64_t ng = g_end - g_begin;
+  for (int64_t base = (int64_t)blockIdx.x * kAccNT; base < ng; base += (int64_t)gridDim.x * kAccNT) {
+    const int64_t gl = base + threadIdx.x;
+    if (gl >= ng) break;
+    const int64_t g = g_begin + gl;
+    const uint4 w = *reinterpret_cast<const uint4*>(last_row + 16 * gl);
+    const f3u a = *reinterpret_cast<const f3u*>(st + 3 * gl);
+    const float A[3] = {a.x, a.y, a.z};
+    int32_t codes[3], out[3];
+    (void)b64_decode_group(w, &sh.tab, codes);  // checked when the row was pushed
+    int h0;
+    const uint32_t kbits = keep_bits<3>(acc_header_bits(sh, hdr, n_hdr, 3 * g, &h0), true, 3 * g, walk_end);
+    const int r = (int)min<int64_t>(3, n_up - 3 * g);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) out[i] = i < r ? merged_code(A[i], inv, codes[i], (kbits >> i) & 1u, &sh.tab) : 0;
+    *reinterpret_cast<uint4*>(merged + 16 * g) = pad_group(b64_encode_group(out, &sh.tab), r);
+    if (merged_f32) {
+      float* mf = merged_f32 + 3 * g;
+      if (r == 3) {
+        *reinterpret_cast<f3u*>(mf) = f3u{dec_mt(out[0], sh.tab.mt), dec_mt(out[1], sh.tab.mt), dec_mt(out[2], sh.tab.mt)};
+      } else {
+        for (int e = 0; e < r; ++e) mf[e] = dec_mt(out[e], sh.tab.mt);
+      }
+    }
+  }
+}
+
+// Element-wise kernels: a grid of whole blocks per CU (8 x 256 lanes fill a CU's wave
+// slots), striding over the groups, so the tables are copied into LDS once per block.
+static unsigned acc_grid(int64_t groups) {
+  static std::atomic<int> cus_of[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) {
+    (void)hipGetLastError();
+    dev = 0;
+  }
+  const bool cached = dev >= 0 && dev < 64;
+  int cus = cached ? cus_of[dev].load(std::memory_order_relaxed) : 0;
+  if (!cus) {
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
+      (void)hipGetLastError();
+      cus = 256;
+    }
+    if (cached) cus_of[dev].store(cus, std::memory_order_relaxed);
+  }
+  const int64_t need = (groups + kAccNT - 1) / kAccNT;
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, 8LL * cus));
+}
+
+hipError_t launch_acc_push(const uint8_t* row, const float* st_in, float* st_out, int first, double dampen,
+                           int64_t n_up, int64_t g_begin, int64_t g_end, const int32_t* d_hdr_block,
+                           int32_t* d_hfirst, int* d_err, hipStream_t s) {
+  if (g_end <= g_begin) return hipSuccess;
+  hipLaunchKernelGGL(k_acc_push, dim3(acc_grid(g_end - g_begin)), dim3(kAccNT), 0, s, row, st_in, st_out, first, dampen,
+                     n_up, g_begin, g_end, d_hdr_block, d_hfirst, d_err);
+  return hipGetLastError();
+}
+
+hipError_t launch_acc_finish(const uint8_t* last_row, const float* st, double inv, int64_t n_up, int64_t g_begin,
+                             int64_t g_end, const int32_t* d_hdr_block, uint8_t* merged, float* merged_f32,
+                             hipStream_t s) {
+  if (g_end <= g_begin) return hipSuccess;
+  hipLaunchKernelGGL(k_acc_finish, dim3(acc_grid(g_end - g_begin)), dim3(kAccNT), 0, s, last_row, st, inv, n_up,
+                     g_begin, g_end, d_hdr_block, merged, merged_f32);
+  return hipGetLastError();
+}
+
+}  // namespace fleet

@@ -1765,6 +1765,268 @@ int fleet_model_version(fleet_ctx* c, const float* weights, const int32_t* dims,
   return FLEET_OK;
 }
 
+// ------------------------------------------------------ streaming aggregation
+
+// One upload folded into a resident sum per call (acc_kernels.hip). The buffers come
+// in pairs: state[cur] holds the sum and the step writes state[cur ^ 1]; row[last]
+// holds the last accepted upload's window (the merge keeps its header codes) and the
+// incoming upload lands in row[last ^ 1]. A host push flips the two indices only after
+// its error word came back clean. The host finish borrows the two spare buffers for its
+// outputs (the next push overwrites both), so the accumulator holds nothing else.
+struct fleet_acc {
+  fleet_ctx* c = nullptr;
+  size_t len = 0, n = 0, gb = 0, ge = 0, ng = 0, col0 = 0, width = 0;
+  int n_hdr = 0;
+  float* d_state[2] = {nullptr, nullptr};
+  uint8_t* d_row[2] = {nullptr, nullptr};
+  uint8_t* h_row[2] = {nullptr, nullptr};  // pinned
+  int32_t* d_hdr = nullptr;                // {0, count, walk_end, 0, positions}
+  int32_t* d_hfirst = nullptr;             // the batch's first upload's header codes
+  int* d_err = nullptr;
+  volatile int* h_err = nullptr;           // pinned: [0] synchronous reads, [1] written back after device pushes
+  int cur = 0, last = 0, count = 0;
+  int sticky = 0;                          // a device push's error, until fleet_acc_reset
+  bool pending = false;                    // device pushes in flight on pending_stream
+  hipStream_t pending_stream = nullptr;
+};
+
+// (static: a helper in an unnamed namespace inside this file's extern "C" block still gets
+// an unmangled dynamic symbol, and a name such as OpenACC's acc_free, which the OpenMP
+// runtime torch loads exports, would then be called in its place)
+namespace {
+
+constexpr size_t kAccPiece = 1 << 20;  // host push: copy and DMA overlap in pieces
+
+static int acc_code(fleet_ctx* c, int e) {
+  if (e & FLEET_ERRBIT_BASE64) return fail(c, FLEET_ERR_BASE64, "input is not Base64::encode output (alphabet/padding)");
+  if (e & FLEET_ERRBIT_LAYOUT)
+    return fail(c, FLEET_ERR_LAYOUT, "upload's layout header slots differ from the batch's first upload");
+  return FLEET_OK;
+}
+
+static int acc_sticky(fleet_acc* a) {
+  if (a->sticky == FLEET_ERR_BASE64) return acc_code(a->c, FLEET_ERRBIT_BASE64);
+  return acc_code(a->c, FLEET_ERRBIT_LAYOUT);
+}
+
+// Waits for the device pushes in flight (unless they run on `same`, which orders the
+// caller's next work itself) and turns an error they wrote back into the sticky one.
+static int acc_settle(fleet_acc* a, hipStream_t same, bool wait) {
+  fleet_ctx* c = a->c;
+  if (a->pending && (wait || a->pending_stream != same)) {
+    HIP_TRY(c, hipStreamSynchronize(a->pending_stream));
+    a->pending = false;
+  }
+  const int e = a->h_err[1];
+  if (e && !a->sticky) a->sticky = (e & FLEET_ERRBIT_BASE64) ? FLEET_ERR_BASE64 : FLEET_ERR_LAYOUT;
+  return a->sticky ? acc_sticky(a) : FLEET_OK;
+}
+
+static int acc_clear_err(fleet_acc* a, hipStream_t s) {
+  HIP_TRY(a->c, hipMemsetAsync(a->d_err, 0, sizeof(int), s));
+  HIP_TRY(a->c, hipStreamSynchronize(s));
+  a->h_err[0] = 0;
+  a->h_err[1] = 0;
+  return FLEET_OK;
+}
+
+static void release_accumulator(fleet_acc* a) {
+  for (void* p : {(void*)a->d_state[0], (void*)a->d_state[1], (void*)a->d_row[0], (void*)a->d_row[1], (void*)a->d_hdr,
+                  (void*)a->d_hfirst, (void*)a->d_err})
+    if (p) (void)hipFree(p);
+  for (void* p : {(void*)a->h_row[0], (void*)a->h_row[1], (void*)a->h_err})
+    if (p) (void)hipHostFree(p);
+  delete a;
+}
+
+}  // namespace
+
+int fleet_acc_create(fleet_ctx* c, size_t len, const int32_t* header_pos, int n_headers, size_t group_begin,
+                     size_t group_end, fleet_acc** out) {
+  if (!c || !out) return FLEET_ERR_ARG;
+  *out = nullptr;
+  if (len == 0 || n_headers < 0 || n_headers > FLEET_MAX_HEADERS || (n_headers && !header_pos)) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  int rc = check_text_len(c, len);
+  if (rc) return rc;
+  const size_t n = fleet_b64_count(len), groups = groups_of(n);
+  if (16 * groups + 16 >= ((size_t)1 << 31)) return fail(c, FLEET_ERR_ARG, "upload of %zu bytes: 2 GiB or more", len);
+  if (group_end > groups) group_end = groups;
+  if (group_begin > group_end) return fail(c, FLEET_ERR_ARG, "group window [%zu, %zu) is empty or reversed", group_begin, group_end);
+  for (int i = 0; i < n_headers; ++i)  // the kernels search the list: ascending positions inside the upload
+    if (header_pos[i] < 0 || (size_t)header_pos[i] >= n || (i && header_pos[i] <= header_pos[i - 1]))
+      return fail(c, FLEET_ERR_ARG, "header position %d (%d) is not ascending inside the upload", i, header_pos[i]);
+  fleet_acc* a = new fleet_acc();
+  a->c = c;
+  a->len = len;
+  a->n = n;
+  a->gb = group_begin;
+  a->ge = group_end;
+  a->ng = group_end - group_begin;
+  a->col0 = 16 * a->gb;
+  a->width = a->ng ? std::min(len, 16 * a->ge) - a->col0 : 0;
+  a->n_hdr = n_headers;
+  const size_t row_bytes = 16 * a->ng + 64, st_bytes = sizeof(float) * 3 * a->ng + 64;
+  const size_t hdr_bytes = sizeof(int32_t) * ((size_t)n_headers + 4);
+  bool ok = true;
+  for (int i = 0; i < 2 && ok; ++i) {
+    ok = hipMalloc((void**)&a->d_state[i], st_bytes) == hipSuccess && hipMalloc((void**)&a->d_row[i], row_bytes) == hipSuccess &&
+         hipHostMalloc((void**)&a->h_row[i], row_bytes, hipHostMallocDefault) == hipSuccess;
+    // bytes past `len` in a row's last group stay zero: the uploads' copies stop at len
+    if (ok) std::memset(a->h_row[i], 0, row_bytes);
+    ok = ok && hipMemset(a->d_row[i], 0, row_bytes) == hipSuccess && hipMemset(a->d_state[i], 0, st_bytes) == hipSuccess;
+  }
+  ok = ok && hipMalloc((void**)&a->d_hdr, hdr_bytes) == hipSuccess &&
+       hipMalloc((void**)&a->d_hfirst, sizeof(int32_t) * ((size_t)n_headers + 16)) == hipSuccess &&
+       hipMalloc((void**)&a->d_err, 64) == hipSuccess && hipMemset(a->d_err, 0, 64) == hipSuccess &&
+       hipHostMalloc((void**)&a->h_err, 64, hipHostMallocDefault) == hipSuccess;
+  if (ok) {
+    a->h_err[0] = 0;
+    a->h_err[1] = 0;
+    std::vector<int32_t> hw((size_t)n_headers + 4);
+    hw[0] = 0;
+    hw[1] = n_headers;
+    hw[2] = (int32_t)n;  // the caller's layout covers the whole upload (as fleet_update_device)
+    hw[3] = 0;
+    if (n_headers) std::memcpy(hw.data() + 4, header_pos, sizeof(int32_t) * (size_t)n_headers);
+    ok = hipMemcpy(a->d_hdr, hw.data(), hdr_bytes, hipMemcpyHostToDevice) == hipSuccess;
+  }
+  if (!ok) {
+    (void)hipGetLastError();
+    release_accumulator(a);
+    return fail(c, FLEET_ERR_NOMEM, "fleet_acc_create: allocating the accumulator of %zu groups failed", group_end - group_begin);
+  }
+  *out = a;
+  return FLEET_OK;
+}
+
+void fleet_acc_destroy(fleet_acc* a) {
+  if (!a) return;
+  fleet_ctx* c = a->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard dg(c->device);
+  if (a->pending) (void)hipStreamSynchronize(a->pending_stream);
+  (void)hipStreamSynchronize(c->stream);
+  release_accumulator(a);
+}
+
+int fleet_acc_count(const fleet_acc* a) { return a ? a->count : FLEET_ERR_ARG; }
+
+int fleet_acc_push(fleet_acc* a, const char* upload, size_t len, double dampen) {
+  if (!a || !upload) return FLEET_ERR_ARG;
+  fleet_ctx* c = a->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  if (len != a->len) return fail(c, FLEET_ERR_ARG, "upload has length %zu, the accumulator's is %zu", len, a->len);
+  int rc = acc_settle(a, c->stream, true);
+  if (rc) return rc;
+  const int spare = a->last ^ 1;
+  for (size_t o = 0; o < a->width; o += kAccPiece) {
+    const size_t m = std::min(kAccPiece, a->width - o);
+    std::memcpy(a->h_row[spare] + o, upload + a->col0 + o, m);
+    HIP_TRY(c, hipMemcpyAsync(a->d_row[spare] + o, a->h_row[spare] + o, m, hipMemcpyHostToDevice, c->stream));
+  }
+  HIP_TRY(c, fleet::launch_acc_push(a->d_row[spare], a->d_state[a->cur], a->d_state[a->cur ^ 1], a->count == 0, dampen,
+                                    (int64_t)a->n, (int64_t)a->gb, (int64_t)a->ge, a->d_hdr, a->d_hfirst, a->d_err,
+                                    c->stream));
+  HIP_TRY(c, hipMemcpyAsync((void*)a->h_err, a->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const int e = a->h_err[0];
+  if (e) {  // rejected: state[cur], row[last] and the count are as before the call
+    if ((rc = acc_clear_err(a, c->stream))) return rc;
+    return acc_code(c, e);
+  }
+  a->cur ^= 1;
+  a->last = spare;
+  ++a->count;
+  return FLEET_OK;
+}
+
+int fleet_acc_push_device(fleet_acc* a, const void* d_upload, double dampen, void* stream) {
+  if (!a || !d_upload) return FLEET_ERR_ARG;
+  fleet_ctx* c = a->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  hipStream_t s = pick(c, stream);
+  int rc = acc_settle(a, s, false);
+  if (rc) return rc;
+  const int spare = a->last ^ 1;
+  if (a->width)
+    HIP_TRY(c, hipMemcpyAsync(a->d_row[spare], (const uint8_t*)d_upload + a->col0, a->width, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(c, fleet::launch_acc_push(a->d_row[spare], a->d_state[a->cur], a->d_state[a->cur ^ 1], a->count == 0, dampen,
+                                    (int64_t)a->n, (int64_t)a->gb, (int64_t)a->ge, a->d_hdr, a->d_hfirst, a->d_err, s));
+  HIP_TRY(c, hipMemcpyAsync((void*)(a->h_err + 1), a->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
+  a->cur ^= 1;
+  a->last = spare;
+  ++a->count;
+  a->pending = true;
+  a->pending_stream = s;
+  return FLEET_OK;
+}
+
+int fleet_acc_finish(fleet_acc* a, char* merged, size_t cap, size_t* out_len, float* merged_f32) {
+  if (!a || !merged) return FLEET_ERR_ARG;
+  fleet_ctx* c = a->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  int rc = acc_settle(a, c->stream, true);
+  if (rc) return rc;
+  if (a->count == 0) return fail(c, FLEET_ERR_ARG, "fleet_acc_finish: nothing was pushed");
+  if (out_len) *out_len = a->len;
+  if (cap < a->len) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu", cap, a->len);
+  // outputs in the spare row and the spare state (window coordinates: shifted back by
+  // the window's start, as the kernel addresses them by the whole upload's group index)
+  uint8_t* d_out = a->d_row[a->last ^ 1];
+  float* d_f32 = a->d_state[a->cur ^ 1];
+  HIP_TRY(c, fleet::launch_acc_finish(a->d_row[a->last], a->d_state[a->cur], (double)1 / a->count, (int64_t)a->n,
+                                      (int64_t)a->gb, (int64_t)a->ge, a->d_hdr, d_out - a->col0,
+                                      merged_f32 ? d_f32 - 3 * a->gb : nullptr, c->stream));
+  const size_t v0 = 3 * a->gb, v1 = std::max(v0, std::min(a->n, 3 * a->ge));
+  if (a->width) HIP_TRY(c, hipMemcpyAsync(merged + a->col0, d_out, a->width, hipMemcpyDeviceToHost, c->stream));
+  if (merged_f32 && v1 > v0)
+    HIP_TRY(c, hipMemcpyAsync(merged_f32 + v0, d_f32, sizeof(float) * (v1 - v0), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  a->count = 0;
+  return FLEET_OK;
+}
+
+int fleet_acc_finish_device(fleet_acc* a, void* d_merged, void* d_merged_f32, void* stream) {
+  if (!a || !d_merged) return FLEET_ERR_ARG;
+  fleet_ctx* c = a->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  hipStream_t s = pick(c, stream);
+  int rc = acc_settle(a, s, false);
+  if (rc) return rc;
+  if (a->count == 0) return fail(c, FLEET_ERR_ARG, "fleet_acc_finish_device: nothing was pushed");
+  HIP_TRY(c, fleet::launch_acc_finish(a->d_row[a->last], a->d_state[a->cur], (double)1 / a->count, (int64_t)a->n,
+                                      (int64_t)a->gb, (int64_t)a->ge, a->d_hdr, (uint8_t*)d_merged,
+                                      (float*)d_merged_f32, s));
+  HIP_TRY(c, hipMemcpyAsync((void*)(a->h_err + 1), a->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  a->pending = false;
+  if ((rc = acc_settle(a, s, false))) return rc;  // a device push of this batch was malformed
+  a->count = 0;
+  return FLEET_OK;
+}
+
+int fleet_acc_reset(fleet_acc* a) {
+  if (!a) return FLEET_ERR_ARG;
+  fleet_ctx* c = a->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  if (a->pending) {
+    HIP_TRY(c, hipStreamSynchronize(a->pending_stream));
+    a->pending = false;
+  }
+  int rc = acc_clear_err(a, c->stream);
+  if (rc) return rc;
+  a->sticky = 0;
+  a->count = 0;
+  return FLEET_OK;
+}
+
 const char* fleet_update_kernel(size_t len) {
   static thread_local std::string name;
   name = fleet::update_kernel_name((int64_t)groups_of(fleet_b64_count(len)));

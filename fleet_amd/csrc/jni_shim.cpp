@@ -35,6 +35,12 @@
 //                                                          double[] dampen)
 //   boolean apps.cppNN.FleetUpdater.registerDirectNative(ByteBuffer rows)
 //   void apps.cppNN.FleetUpdater.unregisterDirectNative(ByteBuffer rows)
+// and the streaming natives of an updater that folds each upload when it arrives
+// (CppNNUpdater.java:383-391: one call per upload; fleet_acc, first context only):
+//   boolean apps.cppNN.FleetUpdater.pushNative(byte[] upload, double dampen)
+//   byte[] apps.cppNN.FleetUpdater.finishNative()      merged Base64, null when empty
+//   int apps.cppNN.FleetUpdater.pendingNative()        uploads folded since the last finish
+//   void apps.cppNN.FleetUpdater.discardNative()       drops them
 //
 // Environment: FLEET_GPUS = devices the batched natives spread one update over
 // (element sharding, fleet_update_multi; default 1, "all" = every visible GPU);
@@ -85,6 +91,9 @@ double g_sigma = 0.0, g_C = 0.0;
 constexpr int kSeed = 1;  // cppNN_backend.cpp:71
 std::mutex g_rows_mu;
 std::vector<char> g_rows;  // row staging of aggregateNative when the JVM cannot grant M local refs
+std::mutex g_acc_mu;
+fleet_acc* g_acc = nullptr;  // the streaming natives' accumulator (on g_ctxs[0]) and its upload length
+size_t g_acc_len = 0;
 
 void init_contexts() {
   if (g_init) return;
@@ -421,6 +430,85 @@ JNIEXPORT void JNICALL Java_apps_cppNN_FleetUpdater_unregisterDirectNative(JNIEn
     }
   const int rc = fleet_host_unregister(c, p);
   if (rc != FLEET_OK) fail(c, "unregisterDirectNative", rc);
+}
+
+// ------------------------------------------------------- streaming update
+
+// The updater that folds every upload when it arrives: one
+// accumulator per process, like the reference's `acc` (CppNNUpdater.java:383-391), on
+// the first context only (FLEET_GPUS > 1 spreads the batched natives, not these).
+// pushNative creates it from its first upload's parsed layout and re-creates it when
+// an upload of another length arrives while it is empty.
+JNIEXPORT jboolean JNICALL Java_apps_cppNN_FleetUpdater_pushNative(JNIEnv* env, jobject, jbyteArray g, jdouble dampen) {
+  fleet_ctx* c = ctx();
+  if (!c) return JNI_FALSE;
+  if (!g) {
+    fail(c, "pushNative (null upload)", FLEET_ERR_ARG);
+    return JNI_FALSE;
+  }
+  const size_t len = (size_t)env->GetArrayLength(g);
+  std::lock_guard<std::mutex> lk(g_acc_mu);
+  // the array is read in place: nothing but the Get/Release pair is a JNI call in here
+  const char* p = static_cast<const char*>(env->GetPrimitiveArrayCritical(g, nullptr));
+  if (!p) {
+    fail(c, "pushNative (array not granted)", FLEET_ERR_NOMEM);
+    return JNI_FALSE;
+  }
+  int rc = FLEET_OK;
+  const char* what = "pushNative";
+  if (g_acc && g_acc_len != len && fleet_acc_count(g_acc) == 0) {
+    fleet_acc_destroy(g_acc);
+    g_acc = nullptr;
+  }
+  if (!g_acc) {
+    std::vector<int32_t> pos(FLEET_MAX_HEADERS);
+    int nh = 0;
+    size_t walk = 0;
+    rc = fleet_layout_parse(c, p, len, pos.data(), FLEET_MAX_HEADERS, &nh, &walk);
+    if (rc == FLEET_OK && walk != fleet_b64_count(len)) {
+      // the accumulator takes the layout as covering the whole upload (fleet_codec.h)
+      what = "pushNative (the upload is longer than its layout: use aggregateNative)";
+      rc = FLEET_ERR_LAYOUT;
+    }
+    if (rc == FLEET_OK) rc = fleet_acc_create(c, len, pos.data(), nh, 0, (size_t)-1, &g_acc);
+    if (rc == FLEET_OK) g_acc_len = len;
+  }
+  if (rc == FLEET_OK) rc = fleet_acc_push(g_acc, p, len, (double)dampen);
+  env->ReleasePrimitiveArrayCritical(g, const_cast<char*>(p), JNI_ABORT);
+  if (rc != FLEET_OK) {
+    fail(c, what, rc);
+    return JNI_FALSE;
+  }
+  return JNI_TRUE;
+}
+
+// The merged Base64 of everything pushed since the last finish (CppNNUpdater.java:
+// 490-508's result for those uploads); null when nothing was pushed.
+JNIEXPORT jbyteArray JNICALL Java_apps_cppNN_FleetUpdater_finishNative(JNIEnv* env, jobject) {
+  fleet_ctx* c = ctx();
+  if (!c) return nullptr;
+  std::vector<char> out;
+  size_t n = 0;
+  {
+    std::lock_guard<std::mutex> lk(g_acc_mu);
+    if (!g_acc || fleet_acc_count(g_acc) <= 0) return nullptr;
+    out.resize(g_acc_len + 16);
+    const int rc = fleet_acc_finish(g_acc, out.data(), out.size(), &n, nullptr);
+    if (rc != FLEET_OK) return fail(c, "finishNative", rc);
+  }
+  return to_java(env, out.data(), n);
+}
+
+JNIEXPORT jint JNICALL Java_apps_cppNN_FleetUpdater_pendingNative(JNIEnv*, jobject) {
+  std::lock_guard<std::mutex> lk(g_acc_mu);
+  return g_acc ? std::max(0, fleet_acc_count(g_acc)) : 0;
+}
+
+JNIEXPORT void JNICALL Java_apps_cppNN_FleetUpdater_discardNative(JNIEnv*, jobject) {
+  std::lock_guard<std::mutex> lk(g_acc_mu);
+  if (!g_acc) return;
+  const int rc = fleet_acc_reset(g_acc);
+  if (rc != FLEET_OK) fail(ctx(), "discardNative", rc);
 }
 
 // ------------------------------------------------------------------- model

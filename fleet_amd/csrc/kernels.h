@@ -88,6 +88,18 @@ hipError_t launch_update_encode(const uint8_t* uploads, size_t pitch, int M, con
                                 int* d_err, const float* values, size_t vpitch, uint8_t* enc_out, hipStream_t s);
 hipError_t launch_encode_f32(const float* values, int64_t n, size_t vpitch, int rows, uint8_t* out, size_t pitch,
                              hipStream_t s);
+// Streaming aggregation (acc_kernels.hip): one upload's step of the chain over the
+// groups [g_begin, g_end) -- row, st_in, st_out hold that window alone (group g at byte
+// 16 (g - g_begin), value 3 (g - g_begin)); st_in is not read when `first`; d_hfirst
+// (n_headers codes) is written by the first step and compared by the later ones -- and
+// the merged gradient from the state and the last accepted row (merged / merged_f32
+// addressed by the whole upload's group index, as launch_update's).
+hipError_t launch_acc_push(const uint8_t* row, const float* st_in, float* st_out, int first, double dampen,
+                           int64_t n_up, int64_t g_begin, int64_t g_end, const int32_t* d_hdr_block,
+                           int32_t* d_hfirst, int* d_err, hipStream_t s);
+hipError_t launch_acc_finish(const uint8_t* last_row, const float* st, double inv, int64_t n_up, int64_t g_begin,
+                             int64_t g_end, const int32_t* d_hdr_block, uint8_t* merged, float* merged_f32,
+                             hipStream_t s);
 hipError_t launch_encode_minibatch(const float* images, int64_t n_images, int F, const int32_t* labels,
                                    const int32_t* idx, int B, const float* teacher, int NL, const float header[7],
                                    uint8_t* out, int* err, hipStream_t s);

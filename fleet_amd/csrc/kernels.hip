@@ -2231,7 +2231,8 @@ __global__ void __launch_bounds__(NT) k_update_encode(const uint8_t* __restrict_
 // machine scheduler, which helps them (VALU-issue bound at 5-6 waves per SIMD)
 // and hurts the tiled and pipelined kernels; the main unit only
 // declares their instantiations.
-#if defined(FLEET_STREAM_TU) || defined(FLEET_DEV_ALL_KERNELS)  // (dev tools that include this file: all here)
+// (acc_kernels.hip includes this file for the stage helpers alone: FLEET_ACC_TU)
+#if (defined(FLEET_STREAM_TU) && !defined(FLEET_ACC_TU)) || defined(FLEET_DEV_ALL_KERNELS)  // (dev tools that include this file: all here)
 template __global__ void k_update_mixed<256, false>(const uint8_t* __restrict__, size_t, int,
                                                     const double* __restrict__, double, int64_t, int64_t, int64_t,
                                                     const int32_t* __restrict__, uint8_t* __restrict__,

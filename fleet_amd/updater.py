@@ -8,7 +8,9 @@ the average into the last picked upload's layout (:508) and calls
 ``descentNative`` (:509). :class:`FleetUpdater` keeps that control logic on the
 host (it is O(M) and O(labels)) and runs the per-element work as two device
 calls: ``Codec.update`` (the exact re-quantised dampen/sum/average/merge chain)
-and ``Codec.descent`` (sgd on the resident model).
+and ``Codec.descent`` (sgd on the resident model). With ``streaming=True`` every
+upload is instead folded into a resident sum when it arrives (``Codec.accumulator``),
+and the M-th call is left with its own push, the finish and the model step.
 
 Scope: the ``staleSize == 0`` branch (``aggregated = acc``, :408-411) with the
 pruning thresholds at 0 (their defaults in the quick start). Staleness
@@ -131,6 +133,7 @@ class Pending:
     labels: List[int]
     epoch: int
     client_id: int
+    dampen: Optional[float] = None  # streaming: the pick's factor, computed when it arrived
 
 
 class FleetUpdater:
@@ -142,7 +145,8 @@ class FleetUpdater:
     (cppNN_backend.cpp:161-172)."""
 
     def __init__(self, codec, layout, M: int, lrates: Sequence[float], weights, fc_bias, policy: int = 0,
-                 alpha: float = 0.0, stale_size: int = 0, num_labels: int = 10, has_outlier: bool = False):
+                 alpha: float = 0.0, stale_size: int = 0, num_labels: int = 10, has_outlier: bool = False,
+                 streaming: bool = False):
         if stale_size != 0:
             raise NotImplementedError("staleness simulation (StalenessSimulator) is not rebuilt: staleSize must be 0")
         self.codec = codec
@@ -160,27 +164,55 @@ class FleetUpdater:
         self.acc: List[Pending] = []
         self.global_labels = [0] * num_labels
         self.last_merged: Optional[bytes] = None
+        # streaming: every upload is folded into a resident sum when it arrives
+        # (Codec.accumulator), so the M-th call is left with one push, the finish and the
+        # model step. With staleSize == 0 picking order is arrival order (:409, :421) and
+        # getDampen reads only curr_epoch and global_labels, which change inside the M-th
+        # call alone (:502-504, descentNative): the factor computed at arrival is the one
+        # the loop below computes for that pick.
+        self.streaming = bool(streaming)
+        self._stream_acc = None
+
+    def _dampen_of(self, p: "Pending") -> float:
+        """getDampen for one pick (:463-464) from the current epoch and label vector."""
+        tau = self.curr_epoch - p.epoch
+        sim = similarity(p.labels, self.global_labels)
+        return get_dampen(self.policy, tau, sim, self.stale_size, self.alpha, self.has_outlier)
+
+    def _push(self, p: "Pending") -> None:
+        a = self._stream_acc
+        if a is None or (a.length != len(p.upload) and a.count == 0):
+            if a is not None:
+                a.close()
+            a = self._stream_acc = self.codec.accumulator(len(p.upload), self.layout.header_positions())
+        p.dampen = self._dampen_of(p)
+        a.push(p.upload, p.dampen)  # a malformed upload raises here and joins nothing
+        p.upload = b""
 
     def update(self, upload: bytes, labels: Sequence[int], epoch: int, client_id: int = 0) -> Optional[bytes]:
         """One client upload (CppNNUpdater.update, :330-518). Returns the merged
         gradient when this upload completed a batch of M (and the model stepped),
         else None."""
-        self.acc.append(Pending(bytes(upload), list(labels), int(epoch), int(client_id)))
+        p = Pending(bytes(upload), list(labels), int(epoch), int(client_id))
+        if self.streaming:
+            self._push(p)
+        self.acc.append(p)
         if len(self.acc) < self.M:  # M-softsync (:388-391)
             return None
         picked, dampen = [], []
         window = [0] * len(self.global_labels)
         for _ in range(self.M):  # FIFO (:420-421)
             p = self.acc.pop(0)
-            tau = self.curr_epoch - p.epoch
-            sim = similarity(p.labels, self.global_labels)
             picked.append(p.upload)
-            dampen.append(get_dampen(self.policy, tau, sim, self.stale_size, self.alpha, self.has_outlier))
+            dampen.append(self._dampen_of(p) if p.dampen is None else p.dampen)
             for j, v in enumerate(p.labels[: len(window)]):
                 window[j] += v
         for j, v in enumerate(window):
             self.global_labels[j] += v
-        merged, grad = self.codec.update(picked, dampen, want_f32=True)
+        if self.streaming:
+            merged, grad = self._stream_acc.finish(want_f32=True)
+        else:
+            merged, grad = self.codec.update(picked, dampen, want_f32=True)
         # descentNative (cppNN_backend.cpp:329-353): lr from the schedule, then the model step
         if self.curr_epoch < len(self.lrates):
             self.lr = np.float32(self.lrates[self.curr_epoch])

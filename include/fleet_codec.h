@@ -237,6 +237,75 @@ int fleet_synth_window_device(fleet_ctx* ctx, uint64_t seed, int M, int client0,
  * until fleet_destroy. */
 int fleet_check(fleet_ctx* ctx, void* stream);
 
+/* Streaming aggregation: each upload folded into a resident sum on arrival ----
+ * CppNNUpdater.update is entered once per upload; it buffers the upload
+ * (CppNNUpdater.java:383-391) and, once M have arrived, picks them in arrival
+ * order (:420-421), dampens each (:463-464), sums, averages and merges them
+ * (:490-508). The chain is serial over the picked uploads and independent per
+ * element, so a fleet_acc runs one upload's step when that upload arrives and
+ * keeps only the running sum: after the M-th arrival what is left is one
+ * upload's copy, one step and the finish, and the device holds two fp32 states
+ * and two upload rows instead of M rows. The bytes are fleet_update's. Valid
+ * for the branch fleet_update covers (staleSize == 0: picking order = arrival
+ * order; pruning thresholds 0), where getDampen's inputs (getCurrEpoch, the
+ * global label vector) change only inside the M-th call (:502-504, descentNative),
+ * so the factor known at arrival is the one the batch loop would compute. For
+ * staleSize > 0, pruning thresholds above 0 or Kardam's side outputs keep the
+ * batch entry points.
+ *
+ * An accumulator belongs to its context (same mutex and device; destroy it
+ * before fleet_destroy; errors through fleet_last_error(ctx)) and owns its memory
+ * -- two state buffers, two device rows (the incoming and the last accepted
+ * upload), two pinned host rows, its error word, the first upload's header
+ * codes -- so fleet_update* calls on the same context are unaffected. `len`, the
+ * header positions and the group window are fixed at creation; [0, ceil(len/16))
+ * = everything. header_pos is, as for fleet_update_device, a layout that covers
+ * the whole upload, and a window behaves exactly like fleet_update_device's: the
+ * accumulator reads and writes only the window's bytes and values, so one rank
+ * may hold one accumulator over its window. */
+typedef struct fleet_acc fleet_acc;
+int fleet_acc_create(fleet_ctx* ctx, size_t len, const int32_t* header_pos, int n_headers, size_t group_begin,
+                     size_t group_end, fleet_acc** out);
+void fleet_acc_destroy(fleet_acc* acc);
+/* One arrival of CppNNUpdater.update (CppNNUpdater.java:383-391) with its pick's
+ * step of the loop at :420-421, :463-464, :490-508 run at once; `upload` is the
+ * whole upload (host buffer, `len` chars; another length is FLEET_ERR_ARG),
+ * `dampen` its getDampen factor. Synchronous and transactional: the window's
+ * bytes go through the spare pinned row to the spare device row, the step
+ * writes the spare state, and only after the error word was read back clean do
+ * the state and the "last upload" flip and the count grow. On FLEET_ERR_BASE64
+ * or FLEET_ERR_LAYOUT (a header slot differs from the batch's first upload) the
+ * accumulator is exactly as before the call. */
+int fleet_acc_push(fleet_acc* acc, const char* upload, size_t len, double dampen);
+/* The same step for an upload already in HBM (d_upload: the whole row, of which
+ * only the window's bytes are read), on the caller's stream. Asynchronous, no
+ * synchronisation: the window is copied device-to-device into the accumulator's
+ * own spare row on that stream and folded, so the caller may reuse d_upload as
+ * soon as the stream allows. Unlike fleet_acc_push it cannot wait to learn
+ * whether the upload was sound, so it commits at once (state and last upload
+ * flip, the count grows on return), and a bad upload leaves a STICKY error: once
+ * it is known (fleet_acc_finish*, which read the error word, or a later push
+ * that finds the word already written back) every further push and finish
+ * returns that code until fleet_acc_reset. Not for graph capture. */
+int fleet_acc_push_device(fleet_acc* acc, const void* d_upload, double dampen, void* stream);
+/* Uploads folded since the last finish / reset (the reference's acc.size(),
+ * CppNNUpdater.java:383-391); FLEET_ERR_ARG for NULL. */
+int fleet_acc_count(const fleet_acc* acc);
+/* The merged gradient of the uploads pushed since the last finish: the sum's
+ * scalarMultiply(1.0 / count) merged into the last accepted upload (CppNNUpdater.java:
+ * 490-508), fleet_update's `merged` (len chars; this accumulator's window of them)
+ * and optionally decodeFloat(merged) in merged_f32. count == 0: FLEET_ERR_ARG.
+ * On success the count returns to 0: the accumulator is ready for the next batch
+ * (:420-421 leave `acc` empty). The host form is synchronous; the device form
+ * writes Base64 at byte 16*g and fp32 at value 3*g of the caller's buffers
+ * (fleet_update_device's addressing, d_merged >= 16*ceil(len/16) bytes) on
+ * `stream` and synchronises it to read the error word. */
+int fleet_acc_finish(fleet_acc* acc, char* merged, size_t cap, size_t* out_len, float* merged_f32);
+int fleet_acc_finish_device(fleet_acc* acc, void* d_merged, void* d_merged_f32, void* stream);
+/* Drops what was pushed (a half-filled batch, CppNNUpdater.java:383-391's `acc`
+ * cleared) and clears a sticky error; waits for the accumulator's device work. */
+int fleet_acc_reset(fleet_acc* acc);
+
 /* Self-test of the device codec arithmetic over whole input domains: an
  * order-independent 64-bit digest sum_i splitmix64(i<<32 | f(i)) of
  *   fn 0: int2float over all 2^32 codes      fn 1: float2int over all 2^32 bit patterns
