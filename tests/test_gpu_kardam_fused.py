@@ -32,9 +32,12 @@ def test_kardam_side_outputs(codec, oracle, layout, M):
     check_side_outputs(codec, oracle, layout, M)
 
 
-@pytest.mark.parametrize("spec", ["update=stream,grid=plain", "update=stream,grid=lanes", "update=stream",
-                                  "update=tiled", "update=tiled,flat_w2=16", "update=tiled,flat_w2=32",
-                                  "update=tiled,flat_w2=21", "update=tiled,tile=classic", "update=pipe"])
+PLANS = ["update=stream,grid=plain", "update=stream,grid=lanes", "update=stream", "update=tiled",
+         "update=tiled,flat_w2=16", "update=tiled,flat_w2=32", "update=tiled,flat_w2=21", "update=tiled,tile=classic",
+         "update=pipe"]
+
+
+@pytest.mark.parametrize("spec", PLANS)
 def test_kardam_side_outputs_under_plans(codec, oracle, plan, spec):
     """Every launch plan's Kardam form on ragged sizes: the stream kernel's group-per-
     lane and value-per-lane blocks (k_update_mixed<256, true>), the flat tiles with each
@@ -45,10 +48,13 @@ def test_kardam_side_outputs_under_plans(codec, oracle, plan, spec):
         check_side_outputs(codec, oracle, layout, M)
 
 
-def check_side_outputs(codec, oracle, layout, M):
+def check_side_outputs(codec, oracle, layout, M, dampen=None, rounds=("none", "alternate", "all")):
+    """rounds: the prev of each round in turn -- "none", "alternate" (prev on every other
+    client) or "all" (prev on every client, replaced in place by this round's G)."""
     dev = torch.device("cuda", 0)
     lr = 0.05
-    d = [1.0 / ((c % 3) + 1) for c in range(M)]
+    d = [1.0 / ((c % 3) + 1) for c in range(M)] if dampen is None else list(dampen)
+    assert len(d) == M
     L = F.b64_len(layout.n_up)
     pitch = 16 * ((L + 15) // 16)
     vpitch = layout.n_up + 3
@@ -86,10 +92,16 @@ def check_side_outputs(codec, oracle, layout, M):
                     assert np.isnan(nd[c])
         return g_texts, g_out
 
-    g1, g1_dev = round_(31, None, None, None)
-    has = [c % 2 == 0 for c in range(M)]
-    g2, g2_dev = round_(32, g1, g1_dev, has)
-    round_(33, g2, g2_dev, [True] * M, in_place=True)
+    g, g_dev = None, None
+    for k, kind in enumerate(rounds):
+        if g is None:
+            assert kind == "none"
+            g, g_dev = round_(31 + k, None, None, None)
+        elif kind == "alternate":
+            g, g_dev = round_(31 + k, g, g_dev, [c % 2 == 0 for c in range(M)])
+        else:
+            assert kind == "all"
+            g, g_dev = round_(31 + k, g, g_dev, [True] * M, in_place=True)
 
 
 def test_kardam_pipelined_flags_across_sizes(codec, oracle, plan):
