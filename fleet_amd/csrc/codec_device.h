@@ -51,7 +51,7 @@ FLEET_HDC B64Tables make_b64_tables() {
 static __constant__ B64Tables g_b64_tables = make_b64_tables();
 
 // Copy the tables into the block's LDS (call from every thread of an NT-thread
-// block, then __syncthreads()): 308 16-byte loads from an L2-resident image.
+// block, then __syncthreads()): 324 16-byte loads from an L2-resident image.
 template <int NT = 256>
 __device__ __forceinline__ void b64_tables_init(B64Tables* t) {
   constexpr int n16 = (int)(sizeof(B64Tables) / 16);

@@ -116,10 +116,32 @@ FLEET_HD bool dec9_ok(int32_t c) {
   return r <= 0x19999999u;
 }
 
+// Nine /10 steps at one fma each. Scaling by a power of two commutes with RNE
+// (nothing here overflows or goes subnormal), so the chain runs on
+// W_j = U_j * 2^s_j, U_j the reference's chain: a step multiplies by 8*RN(0.1) =
+// 0.8f or 16*RN(0.1) = 1.6f (both exact), in the pattern 8, 16, 8 that keeps W
+// within [0.8, 1.35] of t (10^3 ~ 2^10), and 2^-30 = 2^-(6*3 + 3*4) takes the
+// scale off at the end. Step j's small term is then W_{j-1} * kTenthLo * (8 or
+// 16) = t * kTenthLo * (8 ... 13.43) over the nine steps, and div10's margin
+// (t/10 stays 2^-27.3 off a rounding midpoint, the term is 2^-26 of it) lets a
+// taken step's addend be anywhere within 40 % of the true one: ONE addend,
+// t * RN(kTenthLo * 10.36), is within 30 % at every step. |W| <= 1.35 * 2^31
+// for |t| <= 2^31, and the result stays normal for |t| >= 2^-90.
+// d9(-0.0) = +0.0 like div10. Checked against the division chain for every
+// input (tests/native/check_div10.cpp).
+constexpr float kNineLo = -0x1.09374cp-26f;  // RN(kTenthLo * 10.36)
 FLEET_HD float d9(float t) {
-#pragma unroll
-  for (int j = 0; j < 9; ++j) t = div10(t);
-  return t;
+  const float a = t * kNineLo;
+  t = __builtin_fmaf(t, 0.8f, a);
+  t = __builtin_fmaf(t, 1.6f, a);
+  t = __builtin_fmaf(t, 0.8f, a);
+  t = __builtin_fmaf(t, 0.8f, a);
+  t = __builtin_fmaf(t, 1.6f, a);
+  t = __builtin_fmaf(t, 0.8f, a);
+  t = __builtin_fmaf(t, 0.8f, a);
+  t = __builtin_fmaf(t, 1.6f, a);
+  t = __builtin_fmaf(t, 0.8f, a);
+  return t * 0x1p-30f;
 }
 FLEET_HD f2 d9x2(f2 t) {
 #pragma unroll
@@ -368,22 +390,40 @@ FLEET_HD float q_lat(float x) {
 // ops in ~4, packed f32 ops in ~8 (slower than two scalar ops). So the step
 // selection is done with multiplications instead of selects: every value runs
 // the full 9-step chains, and a step that the reference does not take
-// multiplies by 1 (x10 chain) or computes fma(t, 1, t*0) = t (/10 chain), both
-// exact identities. The per-value step multipliers (groups of 2, 1, 2 and 4
+// multiplies by 1 (x10 chain) or computes fma(t, 1, a) = t with an addend a
+// under half an ulp of t (/10 chain, below), both exact identities. The per-value step multipliers (groups of 2, 1, 2 and 4
 // steps, Steps) come from a 16-entry LDS table indexed by the digit count d;
 // d itself from a 512-entry table indexed by the top 9 bits of x (sign and
 // biased exponent) plus one compare with the power of ten inside that binade.
 struct alignas(16) MulEntry {
   float m[4];  // x10 chain group multipliers: 10 (step taken) or 1
-  float h[4];  // /10 chain: fma(t, h, t*kTenthLo) = div10(t) (h = RN(0.1), taken) or t (h = 1)
+  float h[4];  // scaled /10 chain (div10_mt): 0.8 = 8*RN(0.1) (step taken) or 1
+  float s;     // the chain's descale 2^(-3k), k = 9 - d taken steps
+  float pad[3];
 };
-// One small term for both kinds of /10 step: a taken step needs t*lo within
-// 40 % of t*(0.1 - RN(0.1)) (div10's 2^-27.3 midpoint margin, 2^-26 scale of
-// the term), and an identity step fma(t, 1, t*kTenthLo) = RN(t*(1 - 1.5e-9))
-// = t because |t*kTenthLo| < half an ulp of t (2^-25 |t| at least); t is never
-// +-0 in a chain with identity steps (codes there end in a digit count >= 1).
-// Checked over every input by the multiplier-table digests (fn 13-15) and
-// tests/native/check_math.cpp mt.
+// The /10 chain at one fma per step (div10_mt). Scaling by a power of two
+// commutes with RNE while nothing overflows or goes subnormal, so the chain
+// runs on W = U * 8^(steps taken so far), U the reference's chain: a taken
+// step is fma(W, 0.8f, A) with 0.8f = 8*RN(0.1) exactly, and one multiply by
+// s = 2^(-3k) takes the scale off at the end. W therefore shrinks by 0.8 per
+// taken step, not by 10, and so does the small term the step needs,
+// 8*kTenthLo*W. div10's margin (t/10 stays 2^-27.3, relative, off a rounding
+// midpoint; the term is 2^-26 of it) lets a taken step's addend be anywhere
+// within 40 % of the true one, so ONE addend serves a window of three slots:
+// A = W*kWinLo = 0.8 * 8*kTenthLo*W, while over the window the needed term
+// falls from 1 to 0.64 of 8*kTenthLo*W as steps are taken -- A is off by 25 %
+// at most (A's own rounding, 2^-24 of it, is nothing). An identity slot keeps
+// h = 1: fma(W, 1, A) = W because |A| = 1.28 * 2^-27 |W0| <= 2^-26 |W|
+// (|W| >= 0.64 |W0| inside the window), under half an ulp of W even at a
+// power of two (2^-25 |W| there, the addend points toward zero). W never exceeds
+// |t| <= 2^31 and the scale is only taken off by the last multiply, so the
+// result is the first value that could go subnormal (it does not:
+// |t| * 10^-k >= 2^-3 * 10^-9). +-0 gives +0, as div10 does; the order of
+// taken and identity slots is free, as before.
+// Checked against the division chain for every digit row and every input
+// (tests/native/check_div10.cpp), and as part of Q / int2float by
+// tests/native/check_math.cpp mt / d16 and the digests (fn 13-15, 19-23).
+constexpr float kWinLo = -0x1.47ae14p-27f;  // RN(kTenthLo * 8 * 0.8)
 FLEET_HDC MulEntry mul_entry(uint32_t d) {  // d = numDigits; d > 9 (slow marker): identity
   MulEntry e{};
   const bool ok = d <= 9u;
@@ -391,8 +431,10 @@ FLEET_HDC MulEntry mul_entry(uint32_t d) {  // d = numDigits; d > 9 (slow marker
   const bool g[4] = {ok && s.e, ok && s.b0, ok && s.b1, ok && s.b2};
   for (int i = 0; i < 4; ++i) {
     e.m[i] = g[i] ? 10.0f : 1.0f;
-    e.h[i] = g[i] ? kTenthHi : 1.0f;
+    e.h[i] = g[i] ? 0.8f : 1.0f;
   }
+  e.s = 1.0f;
+  for (uint32_t k = ok ? 9u - d : 0u; k > 0; --k) e.s *= 0.125f;
   return e;
 }
 
@@ -455,16 +497,22 @@ FLEET_HD float mul10_mt(float X, const MulEntry& e) {
   X = X * e.m[3];
   return X * e.m[3];
 }
+// 13 instructions for the nine steps: three windows of one small term and three
+// slots, and the descale (see MulEntry)
 FLEET_HD float div10_mt(float t, const MulEntry& e) {
-  t = __builtin_fmaf(t, e.h[0], t * kTenthLo);
-  t = __builtin_fmaf(t, e.h[0], t * kTenthLo);
-  t = __builtin_fmaf(t, e.h[1], t * kTenthLo);
-  t = __builtin_fmaf(t, e.h[2], t * kTenthLo);
-  t = __builtin_fmaf(t, e.h[2], t * kTenthLo);
-  t = __builtin_fmaf(t, e.h[3], t * kTenthLo);
-  t = __builtin_fmaf(t, e.h[3], t * kTenthLo);
-  t = __builtin_fmaf(t, e.h[3], t * kTenthLo);
-  return __builtin_fmaf(t, e.h[3], t * kTenthLo);
+  float a = t * kWinLo;
+  t = __builtin_fmaf(t, e.h[0], a);
+  t = __builtin_fmaf(t, e.h[0], a);
+  t = __builtin_fmaf(t, e.h[1], a);
+  a = t * kWinLo;
+  t = __builtin_fmaf(t, e.h[2], a);
+  t = __builtin_fmaf(t, e.h[2], a);
+  t = __builtin_fmaf(t, e.h[3], a);
+  a = t * kWinLo;
+  t = __builtin_fmaf(t, e.h[3], a);
+  t = __builtin_fmaf(t, e.h[3], a);
+  t = __builtin_fmaf(t, e.h[3], a);
+  return t * e.s;
 }
 
 // |code| = 10*floor(n/10) + d, n = trunc(X): floor(n/10) = mulhi(n, ceil(2^32/10))
@@ -541,7 +589,7 @@ FLEET_HDC uint8_t d16_entry(uint32_t i) {  // i = bits >> 19
 struct alignas(16) StepTables {
   float m[16][4];     // x10 chain group multipliers (MulEntry::m)
   float h[16][4];     // /10 chain group multipliers (MulEntry::h)
-  uint32_t d[16][4];  // d itself (the code's last digit), in .x
+  uint32_t d[16][4];  // d itself (the code's last digit) in .x, the bits of MulEntry::s in .y
 };
 FLEET_HDC StepTables make_step_tables() {
   StepTables t{};
@@ -552,6 +600,7 @@ FLEET_HDC StepTables make_step_tables() {
       t.h[d][k] = e.h[k];
       t.d[d][k] = d;
     }
+    t.d[d][1] = __builtin_bit_cast(uint32_t, e.s);
   }
   return t;
 }
@@ -584,7 +633,13 @@ FLEET_HD float dec_d16(int32_t c, uint32_t r16, const StepTables* st) {
   typedef float f4 __attribute__((ext_vector_type(4)));
   const char* base = reinterpret_cast<const char*>(st);
   const f4 h = *static_cast<const f4*>(__builtin_assume_aligned(base + sizeof(st->m) + r16, 16));
-  const MulEntry me{{1.0f, 1.0f, 1.0f, 1.0f}, {h.x, h.y, h.z, h.w}};
+  // the descale from the row's .y: one more 4-byte read. Its integer form (the bits
+  // are (100 + 3r) << 23, one multiply-add on r16 = 16r) costs the stream kernels a
+  // 73rd VGPR, the seventh wave per SIMD and 7 % of the step; held to 7 waves it
+  // times the same as the read
+  const float s = u2f(*static_cast<const uint32_t*>(
+      __builtin_assume_aligned(base + sizeof(st->m) + sizeof(st->h) + r16 + 4, 4)));
+  const MulEntry me{{1.0f, 1.0f, 1.0f, 1.0f}, {h.x, h.y, h.z, h.w}, s};
   return div10_mt((float)c, me);
 }
 // the marker lanes' digit offset (the compare of var_digits_ab)
@@ -608,9 +663,10 @@ FLEET_HD float q_d16(float x, uint32_t e, const StepTables* st) {
   const char* base = reinterpret_cast<const char*>(st);
   const f4 m = *static_cast<const f4*>(__builtin_assume_aligned(base + e, 16));
   const f4 h = *static_cast<const f4*>(__builtin_assume_aligned(base + sizeof(st->m) + e, 16));
-  const uint32_t d = *static_cast<const uint32_t*>(__builtin_assume_aligned(base + sizeof(st->m) + sizeof(st->h) + e, 16));
-  const MulEntry me{{m.x, m.y, m.z, m.w}, {h.x, h.y, h.z, h.w}};
-  return div10_mt(code_float_mt(mul10_mt(__builtin_fabsf(x), me), d, x), me);
+  // d and the descale in one 8-byte load
+  const u2 ds = *static_cast<const u2*>(__builtin_assume_aligned(base + sizeof(st->m) + sizeof(st->h) + e, 16));
+  const MulEntry me{{m.x, m.y, m.z, m.w}, {h.x, h.y, h.z, h.w}, u2f(ds.y)};
+  return div10_mt(code_float_mt(mul10_mt(__builtin_fabsf(x), me), ds.x, x), me);
 }
 
 // float2int(x) given e = 16 * numDigits((int)x) <= 144 (the client encode's form
