@@ -113,6 +113,11 @@ def lib() -> C.CDLL:
         "fleet_acc_finish": (i32, [vp, vp, sz, szp, vp]),
         "fleet_acc_finish_device": (i32, [vp, vp, vp, vp]),
         "fleet_acc_reset": (i32, [vp]),
+        "fleet_acc_push_many": (i32, [vp, vp, vp, i32, vp]),
+        "fleet_acc_push_many_device": (i32, [vp, vp, sz, i32, vp, vp]),
+        "fleet_acc_push_finish": (i32, [vp, vp, vp, i32, vp, vp, sz, szp, vp]),
+        "fleet_acc_push_finish_device": (i32, [vp, vp, sz, i32, vp, vp, vp, vp]),
+        "fleet_acc_burst": (i32, []),
         "fleet_update_kernel": (C.c_char_p, [sz]),
         "fleet_update_plan_grid": (i32, [sz, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -188,6 +193,15 @@ def lib() -> C.CDLL:
     _ = i64
     _lib = L
     return L
+
+
+def __getattr__(name):
+    # ACC_BURST: uploads one k_acc_push_many launch folds (fleet_acc_burst), read from the
+    # library when first asked for, so importing the package does not load it
+    if name == "ACC_BURST":
+        v = globals()["ACC_BURST"] = int(lib().fleet_acc_burst())
+        return v
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def exported_symbols_from_header(path: str = HEADER_PATH):
@@ -782,7 +796,10 @@ class Accumulator:
     sum of the chain instead of the uploads themselves. ``push`` is synchronous and
     transactional (a rejected upload raises and leaves the batch as it was);
     ``push_device`` is asynchronous and commits at once, a bad upload surfacing as a
-    sticky error at ``finish*`` or a later push until ``reset``."""
+    sticky error at ``finish*`` or a later push until ``reset``. Uploads that are at
+    hand together go in as a burst (``push_many`` / ``push_many_device``: one kernel per
+    ``ACC_BURST`` of them, the same bytes as pushing each), and ``push_finish`` /
+    ``push_finish_device`` fold the burst that completes a batch and finish in one call."""
 
     def __init__(self, codec: Codec, length: int, header_pos, group_begin: int = 0, group_end: Optional[int] = None):
         self.codec = codec
@@ -855,6 +872,71 @@ class Accumulator:
 
     def reset(self) -> None:
         self.codec._check(self._L.fleet_acc_reset(self._h))
+
+    # bursts: K uploads folded by one kernel per ACC_BURST of them
+
+    @staticmethod
+    def _burst_args(uploads, dampens):
+        ups = [_as_bytes(u) for u in uploads]
+        if not ups:
+            raise ValueError("no uploads")
+        if len(dampens) != len(ups):
+            raise ValueError("one dampening factor per upload")
+        arr = (C.c_char_p * len(ups))(*ups)
+        lens = np.array([len(u) for u in ups], dtype=np.uint64)
+        d = np.ascontiguousarray(dampens, dtype=np.float64)
+        return ups, arr, lens, d
+
+    def _device_rows(self, u8_tensor, dampens):
+        if u8_tensor.dim() != 2 or u8_tensor.stride(1) != 1:
+            raise ValueError("expected a uint8 CUDA tensor [K, pitch] with contiguous rows")
+        K = int(u8_tensor.shape[0])
+        if K == 0:
+            raise ValueError("no uploads")
+        if len(dampens) != K:
+            raise ValueError("one dampening factor per upload")
+        if u8_tensor.shape[1] < (self.length if K == 1 else 16 * self.groups):
+            raise ValueError("the rows are shorter than the accumulator's uploads")
+        return K, int(u8_tensor.stride(0)) if K > 1 else 0, np.ascontiguousarray(dampens, dtype=np.float64)
+
+    def push_many(self, uploads, dampens) -> None:
+        """Folds the uploads in order, as ``push`` on each would, in one synchronous call;
+        all or nothing: if one is rejected the call raises and the batch is as before."""
+        ups, arr, lens, d = self._burst_args(uploads, dampens)
+        self.codec._check(self._L.fleet_acc_push_many(self._h, arr, lens.ctypes.data, len(ups), d.ctypes.data))
+
+    def push_many_device(self, u8_tensor, dampens, stream=None) -> None:
+        """u8_tensor: a uint8 CUDA tensor [K, pitch] of whole upload rows (pitch a multiple of
+        16, >= 16 * groups); asynchronous, errors are sticky as with ``push_device``."""
+        K, pitch, d = self._device_rows(u8_tensor, dampens)
+        self.codec._check(self._L.fleet_acc_push_many_device(self._h, u8_tensor.data_ptr(), pitch, K, d.ctypes.data,
+                                                             _stream(stream)))
+
+    def push_finish(self, uploads, dampens, want_f32: bool = False):
+        """``push_many`` and ``finish`` in one call: the kernel that folds the last uploads
+        also writes the merged gradient. Transactional like ``push_many``."""
+        ups, arr, lens, d = self._burst_args(uploads, dampens)
+        out = np.zeros(self.length + 16, np.uint8)
+        n = C.c_size_t(0)
+        f32 = np.zeros(b64_count(self.length) + 1, np.float32) if want_f32 else None
+        self.codec._check(self._L.fleet_acc_push_finish(self._h, arr, lens.ctypes.data, len(ups), d.ctypes.data,
+                                                        out.ctypes.data, len(out), C.byref(n),
+                                                        f32.ctypes.data if want_f32 else None))
+        merged = out[: n.value].tobytes()
+        if want_f32:
+            return merged, f32[: b64_count(self.length)].copy()
+        return merged
+
+    def push_finish_device(self, u8_tensor, dampens, merged_u8, merged_f32=None, stream=None) -> None:
+        """``push_many_device`` and ``finish_device`` in one call; synchronises the stream,
+        and a bad row of the burst leaves the accumulator as before the call."""
+        K, pitch, d = self._device_rows(u8_tensor, dampens)
+        if merged_u8.numel() < 16 * self.groups or (
+                merged_f32 is not None and merged_f32.numel() < b64_count(self.length)):
+            raise ValueError("merged tensors smaller than the upload's groups")
+        self.codec._check(self._L.fleet_acc_push_finish_device(
+            self._h, u8_tensor.data_ptr(), pitch, K, d.ctypes.data, merged_u8.data_ptr(),
+            merged_f32.data_ptr() if merged_f32 is not None else None, _stream(stream)))
 
 
 def update_multi(codecs: Sequence["Codec"], uploads: Sequence, dampen: Sequence[float], want_f32: bool = False):

@@ -172,6 +172,124 @@ __global__ void __launch_bounds__(kAccNT) k_acc_finish(const uint8_t* __restrict
   }
 }
 
+// A burst: the steps of K <= kAccBurst uploads over the window in one launch, the
+// running value in registers across the K clients, so the state is read and written
+// once per lane instead of once per upload. Each step is k_acc_push's (every Q is
+// q_stage_d16x: the per-step fallback holds inside a burst, no earlier row is re-read).
+// Rows 0..K-2 are rows + k * pitch, row K-1 is `last_row` (the accumulator's spare row
+// when the burst ends there, so the finish finds "the last accepted upload"; a chunk of
+// a longer burst passes rows + (K-1) * pitch); all in window coordinates. `first`: the
+// batch's first upload is row 0 -- st_in is not read, row 0's header codes are kept in
+// registers for the comparison and recorded in hfirst[]; otherwise the rows are compared
+// with hfirst[]. The factors travel by value: the index is wave-uniform, so
+// dampen_stage's test stays scalar. st_in and st_out may be the same buffer (the later
+// chunks of a long burst): a lane reads its 12 bytes before it writes them.
+//
+// FINISH: k_acc_finish's epilogue on the registers after the last client -- merged_code
+// with inv = 1 / (count + K), header and unwalked slots row K-1's own codes -- written to
+// merged / merged_f32 (whole-upload addressing); no state is stored. `merged` may be
+// `last_row` shifted back by the window's start and merged_f32 likewise `st_in` (the
+// host form borrows the spare buffers): a lane reads its group before it writes it, and
+// dead lanes load nothing.
+struct AccDampen {
+  double d[kAccBurst];
+};
+
+template <bool FINISH>
+__global__ void __launch_bounds__(kAccNT) k_acc_push_many(const uint8_t* rows, size_t pitch, const uint8_t* last_row,
+                                                          const float* st_in, float* st_out, int first, int K,
+                                                          AccDampen dampen, double inv, int64_t n_up, int64_t g_begin,
+                                                          int64_t g_end, const int32_t* __restrict__ hdr_block,
+                                                          int32_t* hfirst, int* __restrict__ err, uint8_t* merged,
+                                                          float* merged_f32) {
+  __shared__ AccShared sh;
+  const int n_hdr = hdr_block[1];
+  const int64_t walk_end = hdr_block[2];
+  const int32_t* hdr = hdr_block + 4;
+  acc_init(sh, hdr, n_hdr);
+  const int64_t ng = g_end - g_begin;
+  uint32_t bad = 0, layout_bad = 0;
+  for (int64_t base = (int64_t)blockIdx.x * kAccNT; base < ng; base += (int64_t)gridDim.x * kAccNT) {
+    const int64_t gl = base + threadIdx.x;
+    const bool live = gl < ng;
+    const int64_t gs = live ? gl : 0, g = g_begin + gs;  // dead lanes run the chain on zero bytes and store nothing
+    float A[3] = {0.f, 0.f, 0.f};
+    if (!first && live) {
+      const f3u a = *reinterpret_cast<const f3u*>(st_in + 3 * gs);
+      A[0] = a.x, A[1] = a.y, A[2] = a.z;
+    }
+    const uint32_t need = needed_chars_mask((int)min<int64_t>(3, max<int64_t>(0, n_up - 3 * g)));
+    int h0;
+    const uint32_t hbits = acc_header_bits(sh, hdr, n_hdr, 3 * g, &h0);
+    const uint32_t kbits = keep_bits<3>(hbits, true, 3 * g, walk_end);
+    const bool wave_keep = __ballot(kbits != 0) != 0;  // wave-uniform: few waves hold a header
+    int32_t href[3] = {0, 0, 0}, keepc[3] = {0, 0, 0};
+    if (wave_keep && !first) {
+      int hi = h0;
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        if ((hbits >> i) & 1u) href[i] = hfirst[hi++];
+    }
+    for (int k = 0; k < K; ++k) {
+      const uint8_t* src = (k == K - 1 ? last_row : rows + (size_t)k * pitch) + 16 * gs;
+      uint4 w = uint4{0u, 0u, 0u, 0u};
+      if (live) w = *reinterpret_cast<const uint4*>(src);
+      int32_t codes[3];
+      if (need == 0xffffu) bad |= live ? b64_decode_group_full(w, &sh.tab, codes) : 0u;
+      else bad |= live ? (b64_decode_group(w, &sh.tab, codes) & need) : 0u;
+      const bool is_first = first && k == 0;  // uniform
+      if (!live) codes[0] = codes[1] = codes[2] = 0;
+      if (wave_keep) {
+        int hi = h0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          if ((hbits >> i) & 1u) {
+            if (is_first) {
+              href[i] = codes[i];
+              if (live) hfirst[hi] = codes[i];
+            } else if (live) {
+              layout_bad |= (uint32_t)(codes[i] != href[i]);
+            }
+            ++hi;
+          }
+          if (FINISH) keepc[i] = codes[i];  // row K-1's are the ones left after the loop
+          if ((kbits >> i) & 1u) codes[i] = 0;
+        }
+      }
+      float y0[3], y[3], p[3];
+      dec_stage_d16<3>(y0, codes, &sh.dtab);
+      q_stage_d16x<3>(y, y0, &sh.dtab, sh.tab.var);
+      dampen_stage<3>(y, dampen.d[k]);
+      q_stage_d16x<3>(p, y, &sh.dtab, sh.tab.var);
+      if (is_first) {
+        A[0] = p[0], A[1] = p[1], A[2] = p[2];
+      } else {
+        const float sm[3] = {A[0] + p[0], A[1] + p[1], A[2] + p[2]};
+        q_stage_d16x<3>(A, sm, &sh.dtab, sh.tab.var);
+      }
+    }
+    if (!FINISH) {
+      if (live) *reinterpret_cast<f3u*>(st_out + 3 * gs) = f3u{A[0], A[1], A[2]};
+    } else if (live) {
+      const int r = (int)min<int64_t>(3, n_up - 3 * g);
+      int32_t out[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) out[i] = i < r ? merged_code(A[i], inv, keepc[i], (kbits >> i) & 1u, &sh.tab) : 0;
+      *reinterpret_cast<uint4*>(merged + 16 * g) = pad_group(b64_encode_group(out, &sh.tab), r);
+      if (merged_f32) {
+        float* mf = merged_f32 + 3 * g;
+        if (r == 3) {
+          *reinterpret_cast<f3u*>(mf) = f3u{dec_mt(out[0], sh.tab.mt), dec_mt(out[1], sh.tab.mt), dec_mt(out[2], sh.tab.mt)};
+        } else {
+          for (int e = 0; e < r; ++e) mf[e] = dec_mt(out[e], sh.tab.mt);
+        }
+      }
+    }
+  }
+  if (bad) atomicOr(err, FLEET_ERRBIT_BASE64);
+  if (layout_bad) atomicOr(err, FLEET_ERRBIT_LAYOUT);
+}
+
 // Element-wise kernels: a grid of whole blocks per CU (8 x 256 lanes fill a CU's wave
 // slots), striding over the groups, so the tables are copied into LDS once per block.
 static unsigned acc_grid(int64_t groups) {
@@ -209,6 +327,24 @@ hipError_t launch_acc_finish(const uint8_t* last_row, const float* st, double in
   if (g_end <= g_begin) return hipSuccess;
   hipLaunchKernelGGL(k_acc_finish, dim3(acc_grid(g_end - g_begin)), dim3(kAccNT), 0, s, last_row, st, inv, n_up,
                      g_begin, g_end, d_hdr_block, merged, merged_f32);
+  return hipGetLastError();
+}
+
+hipError_t launch_acc_push_many(const uint8_t* rows, size_t pitch, const uint8_t* last_row, const float* st_in,
+                                float* st_out, int first, int K, const double* dampen, bool finish, double inv,
+                                int64_t n_up, int64_t g_begin, int64_t g_end, const int32_t* d_hdr_block,
+                                int32_t* d_hfirst, int* d_err, uint8_t* merged, float* merged_f32, hipStream_t s) {
+  if (K <= 0 || K > kAccBurst) return hipErrorInvalidValue;
+  if (g_end <= g_begin) return hipSuccess;
+  AccDampen d;
+  for (int k = 0; k < kAccBurst; ++k) d.d[k] = k < K ? dampen[k] : 1.0;
+  const dim3 grid(acc_grid(g_end - g_begin)), block(kAccNT);
+  if (finish)
+    hipLaunchKernelGGL(k_acc_push_many<true>, grid, block, 0, s, rows, pitch, last_row, st_in, st_out, first, K, d, inv,
+                       n_up, g_begin, g_end, d_hdr_block, d_hfirst, d_err, merged, merged_f32);
+  else
+    hipLaunchKernelGGL(k_acc_push_many<false>, grid, block, 0, s, rows, pitch, last_row, st_in, st_out, first, K, d, inv,
+                       n_up, g_begin, g_end, d_hdr_block, d_hfirst, d_err, merged, merged_f32);
   return hipGetLastError();
 }
 

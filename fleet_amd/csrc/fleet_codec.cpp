@@ -1788,6 +1788,11 @@ struct fleet_acc {
   int sticky = 0;                          // a device push's error, until fleet_acc_reset
   bool pending = false;                    // device pushes in flight on pending_stream
   hipStream_t pending_stream = nullptr;
+  // host bursts: rows 0..K-2 of a launch, window bytes at stage_pitch apart; grown on
+  // demand to at most kAccBurst rows and kept until fleet_acc_destroy
+  uint8_t* d_stage = nullptr;
+  uint8_t* h_stage = nullptr;  // pinned
+  size_t stage_rows = 0, stage_pitch = 0;
 };
 
 // (static: a helper in an unnamed namespace inside this file's extern "C" block still gets
@@ -1832,9 +1837,9 @@ static int acc_clear_err(fleet_acc* a, hipStream_t s) {
 
 static void release_accumulator(fleet_acc* a) {
   for (void* p : {(void*)a->d_state[0], (void*)a->d_state[1], (void*)a->d_row[0], (void*)a->d_row[1], (void*)a->d_hdr,
-                  (void*)a->d_hfirst, (void*)a->d_err})
+                  (void*)a->d_hfirst, (void*)a->d_err, (void*)a->d_stage})
     if (p) (void)hipFree(p);
-  for (void* p : {(void*)a->h_row[0], (void*)a->h_row[1], (void*)a->h_err})
+  for (void* p : {(void*)a->h_row[0], (void*)a->h_row[1], (void*)a->h_err, (void*)a->h_stage})
     if (p) (void)hipHostFree(p);
   delete a;
 }
@@ -2007,6 +2012,214 @@ int fleet_acc_finish_device(fleet_acc* a, void* d_merged, void* d_merged_f32, vo
   HIP_TRY(c, hipStreamSynchronize(s));
   a->pending = false;
   if ((rc = acc_settle(a, s, false))) return rc;  // a device push of this batch was malformed
+  a->count = 0;
+  return FLEET_OK;
+}
+
+// --- bursts: K uploads per call, kAccBurst per launch (k_acc_push_many)
+
+namespace {
+
+static int acc_stage_reserve(fleet_acc* a, size_t rows) {
+  fleet_ctx* c = a->c;
+  if (rows <= a->stage_rows || a->ng == 0) return FLEET_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (a->d_stage) (void)hipFree(a->d_stage);
+  if (a->h_stage) (void)hipHostFree(a->h_stage);
+  a->d_stage = a->h_stage = nullptr;
+  a->stage_rows = 0;
+  a->stage_pitch = 16 * a->ng + 64;
+  const size_t bytes = rows * a->stage_pitch;
+  if (hipMalloc((void**)&a->d_stage, bytes) != hipSuccess ||
+      hipHostMalloc((void**)&a->h_stage, bytes, hipHostMallocDefault) != hipSuccess ||
+      hipMemsetAsync(a->d_stage, 0, bytes, c->stream) != hipSuccess) {  // on the stream the rows' copies follow on
+    (void)hipGetLastError();
+    if (a->d_stage) (void)hipFree(a->d_stage);
+    if (a->h_stage) (void)hipHostFree(a->h_stage);
+    a->d_stage = a->h_stage = nullptr;
+    return fail(c, FLEET_ERR_NOMEM, "burst staging of %zu rows of %zu bytes failed", rows, a->stage_pitch);
+  }
+  // bytes past `len` in a row's last group stay zero: the uploads' copies stop at len
+  std::memset(a->h_stage, 0, bytes);
+  a->stage_rows = rows;
+  return FLEET_OK;
+}
+
+// Enqueues the burst's copies and launches on `s` and commits nothing: the steps go
+// from state[cur] into state[cur ^ 1] (a burst longer than kAccBurst: the first launch
+// reads state[cur], the later ones read and write state[cur ^ 1] in place), row K-1
+// lands in the spare row. Host rows (`uploads`) go through the staging; device rows
+// (`d_rows`: the window's first byte of row 0, `pitch` apart) are read in place. With
+// `finish` the last launch is the finish form, writing d_merged / d_f32.
+static int acc_fold(fleet_acc* a, const char* const* uploads, const uint8_t* d_rows, size_t pitch, int K,
+                    const double* dampen, hipStream_t s, bool finish, uint8_t* d_merged, float* d_f32) {
+  fleet_ctx* c = a->c;
+  if (a->ng == 0) return FLEET_OK;
+  constexpr int B = fleet::kAccBurst;
+  const int spare = a->last ^ 1;
+  if (uploads) {
+    // a launch's rows but the burst's last one, which goes to the spare row
+    const int rc = acc_stage_reserve(a, (size_t)(K > B ? B : K - 1));
+    if (rc) return rc;
+  }
+  const double inv = (double)1 / (a->count + K);
+  for (int k0 = 0; k0 < K; k0 += B) {
+    const int kc = std::min(B, K - k0);
+    const bool last_chunk = k0 + kc == K;
+    const uint8_t *rows, *last_row;
+    size_t rp;
+    if (uploads) {
+      if (k0) HIP_TRY(c, hipStreamSynchronize(s));  // the pinned staging is read by the previous chunk's copies
+      for (int k = 0; k < kc; ++k) {
+        const bool to_spare = last_chunk && k == kc - 1;
+        uint8_t* h = to_spare ? a->h_row[spare] : a->h_stage + (size_t)k * a->stage_pitch;
+        uint8_t* d = to_spare ? a->d_row[spare] : a->d_stage + (size_t)k * a->stage_pitch;
+        for (size_t o = 0; o < a->width; o += kAccPiece) {  // copy and DMA overlap in pieces, as fleet_acc_push
+          const size_t m = std::min(kAccPiece, a->width - o);
+          std::memcpy(h + o, uploads[k0 + k] + a->col0 + o, m);
+          HIP_TRY(c, hipMemcpyAsync(d + o, h + o, m, hipMemcpyHostToDevice, s));
+        }
+      }
+      rows = a->d_stage;
+      rp = a->stage_pitch;
+    } else {
+      rows = d_rows + (size_t)k0 * pitch;
+      rp = pitch;
+      if (last_chunk)
+        HIP_TRY(c, hipMemcpyAsync(a->d_row[spare], rows + (size_t)(kc - 1) * pitch, a->width, hipMemcpyDeviceToDevice, s));
+    }
+    last_row = last_chunk ? a->d_row[spare] : rows + (size_t)(kc - 1) * rp;
+    const bool fin = finish && last_chunk;
+    HIP_TRY(c, fleet::launch_acc_push_many(rows, rp, last_row, a->d_state[k0 ? a->cur ^ 1 : a->cur], a->d_state[a->cur ^ 1],
+                                           k0 == 0 && a->count == 0, kc, dampen + k0, fin, inv, (int64_t)a->n,
+                                           (int64_t)a->gb, (int64_t)a->ge, a->d_hdr, a->d_hfirst, a->d_err,
+                                           fin ? d_merged : nullptr, fin ? d_f32 : nullptr, s));
+  }
+  return FLEET_OK;
+}
+
+static int acc_host_args(fleet_acc* a, const char* const* uploads, const size_t* lens, int K, const char* what) {
+  for (int k = 0; k < K; ++k) {
+    if (!uploads[k]) return fail(a->c, FLEET_ERR_ARG, "%s: upload %d is NULL", what, k);
+    if (lens[k] != a->len)
+      return fail(a->c, FLEET_ERR_ARG, "%s: upload %d has length %zu, the accumulator's is %zu", what, k, lens[k], a->len);
+  }
+  return FLEET_OK;
+}
+
+// rows 0..K-2 are read in place with 16-byte loads
+static int acc_device_args(fleet_acc* a, const void* d_uploads, size_t pitch, int K, const char* what) {
+  if (K > 1 && (pitch % 16 != 0 || pitch < 16 * groups_of(a->n) || (uintptr_t)d_uploads % 16 != 0))
+    return fail(a->c, FLEET_ERR_ARG, "%s: rows must be 16-byte aligned, the pitch a multiple of 16 covering the upload's groups", what);
+  return FLEET_OK;
+}
+
+// the error word of the burst just enqueued on `s`, read synchronously; an error
+// leaves nothing committed
+static int acc_burst_verdict(fleet_acc* a, hipStream_t s) {
+  fleet_ctx* c = a->c;
+  HIP_TRY(c, hipMemcpyAsync((void*)a->h_err, a->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  const int e = a->h_err[0];
+  if (e) {
+    const int rc = acc_clear_err(a, s);
+    return rc ? rc : acc_code(c, e);
+  }
+  return FLEET_OK;
+}
+
+}  // namespace
+
+int fleet_acc_burst(void) { return fleet::kAccBurst; }
+
+int fleet_acc_push_many(fleet_acc* a, const char* const* uploads, const size_t* lens, int K, const double* dampen) {
+  if (!a || !uploads || !lens || !dampen || K <= 0) return FLEET_ERR_ARG;
+  fleet_ctx* c = a->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  int rc = acc_host_args(a, uploads, lens, K, "fleet_acc_push_many");
+  if (rc) return rc;
+  if ((rc = acc_settle(a, c->stream, true))) return rc;
+  if ((rc = acc_fold(a, uploads, nullptr, 0, K, dampen, c->stream, false, nullptr, nullptr))) return rc;
+  if ((rc = acc_burst_verdict(a, c->stream))) return rc;  // rejected: state[cur], row[last] and the count are as before
+  a->cur ^= 1;
+  a->last ^= 1;
+  a->count += K;
+  return FLEET_OK;
+}
+
+int fleet_acc_push_many_device(fleet_acc* a, const void* d_uploads, size_t pitch, int K, const double* dampen,
+                               void* stream) {
+  if (!a || !d_uploads || !dampen || K <= 0) return FLEET_ERR_ARG;
+  fleet_ctx* c = a->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  int rc = acc_device_args(a, d_uploads, pitch, K, "fleet_acc_push_many_device");
+  if (rc) return rc;
+  hipStream_t s = pick(c, stream);
+  if ((rc = acc_settle(a, s, false))) return rc;
+  if ((rc = acc_fold(a, nullptr, (const uint8_t*)d_uploads + a->col0, pitch, K, dampen, s, false, nullptr, nullptr)))
+    return rc;
+  HIP_TRY(c, hipMemcpyAsync((void*)(a->h_err + 1), a->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
+  a->cur ^= 1;
+  a->last ^= 1;
+  a->count += K;
+  a->pending = true;
+  a->pending_stream = s;
+  return FLEET_OK;
+}
+
+int fleet_acc_push_finish(fleet_acc* a, const char* const* uploads, const size_t* lens, int K, const double* dampen,
+                          char* merged, size_t cap, size_t* out_len, float* merged_f32) {
+  if (!a || !uploads || !lens || !dampen || !merged || K <= 0) return FLEET_ERR_ARG;
+  fleet_ctx* c = a->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  int rc = acc_host_args(a, uploads, lens, K, "fleet_acc_push_finish");
+  if (rc) return rc;
+  if ((rc = acc_settle(a, c->stream, true))) return rc;
+  if (out_len) *out_len = a->len;
+  if (cap < a->len) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu", cap, a->len);
+  // outputs in the spare row (over row K-1, which the lane has read by then) and the
+  // spare state, as fleet_acc_finish
+  uint8_t* d_out = a->d_row[a->last ^ 1];
+  float* d_f32 = a->d_state[a->cur ^ 1];
+  if ((rc = acc_fold(a, uploads, nullptr, 0, K, dampen, c->stream, true, d_out - a->col0,
+                     merged_f32 ? d_f32 - 3 * a->gb : nullptr)))
+    return rc;
+  const size_t v0 = 3 * a->gb, v1 = std::max(v0, std::min(a->n, 3 * a->ge));
+  if (a->width) HIP_TRY(c, hipMemcpyAsync(merged + a->col0, d_out, a->width, hipMemcpyDeviceToHost, c->stream));
+  if (merged_f32 && v1 > v0)
+    HIP_TRY(c, hipMemcpyAsync(merged_f32 + v0, d_f32, sizeof(float) * (v1 - v0), hipMemcpyDeviceToHost, c->stream));
+  if ((rc = acc_burst_verdict(a, c->stream))) return rc;  // rejected: nothing committed (the outputs are not meaningful)
+  a->count = 0;
+  return FLEET_OK;
+}
+
+int fleet_acc_push_finish_device(fleet_acc* a, const void* d_uploads, size_t pitch, int K, const double* dampen,
+                                 void* d_merged, void* d_merged_f32, void* stream) {
+  if (!a || !d_uploads || !dampen || !d_merged || K <= 0) return FLEET_ERR_ARG;
+  fleet_ctx* c = a->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  int rc = acc_device_args(a, d_uploads, pitch, K, "fleet_acc_push_finish_device");
+  if (rc) return rc;
+  hipStream_t s = pick(c, stream);
+  if ((rc = acc_settle(a, s, false))) return rc;
+  if ((rc = acc_fold(a, nullptr, (const uint8_t*)d_uploads + a->col0, pitch, K, dampen, s, true, (uint8_t*)d_merged,
+                     (float*)d_merged_f32)))
+    return rc;
+  // device pushes of this batch still in flight are on `s` and wrote their error word
+  // back before this burst ran: theirs is sticky and comes first, the burst's own is not
+  HIP_TRY(c, hipMemcpyAsync((void*)a->h_err, a->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  a->pending = false;
+  if ((rc = acc_settle(a, s, false))) return rc;
+  const int e = a->h_err[0];
+  if (e) {
+    rc = acc_clear_err(a, s);
+    return rc ? rc : acc_code(c, e);
+  }
   a->count = 0;
   return FLEET_OK;
 }

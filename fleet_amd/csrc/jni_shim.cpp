@@ -38,6 +38,7 @@
 // and the streaming natives of an updater that folds each upload when it arrives
 // (CppNNUpdater.java:383-391: one call per upload; fleet_acc, first context only):
 //   boolean apps.cppNN.FleetUpdater.pushNative(byte[] upload, double dampen)
+//   boolean apps.cppNN.FleetUpdater.pushBatchNative(byte[][] uploads, double[] dampen)   a burst, all or nothing
 //   byte[] apps.cppNN.FleetUpdater.finishNative()      merged Base64, null when empty
 //   int apps.cppNN.FleetUpdater.pendingNative()        uploads folded since the last finish
 //   void apps.cppNN.FleetUpdater.discardNative()       drops them
@@ -439,6 +440,29 @@ JNIEXPORT void JNICALL Java_apps_cppNN_FleetUpdater_unregisterDirectNative(JNIEn
 // the first context only (FLEET_GPUS > 1 spreads the batched natives, not these).
 // pushNative creates it from its first upload's parsed layout and re-creates it when
 // an upload of another length arrives while it is empty.
+// (g_acc_mu held; `p`: an upload of `len` bytes whose layout header the accumulator takes)
+static int process_acc(fleet_ctx* c, const char* p, size_t len, const char** what, const char* what_longer) {
+  int rc = FLEET_OK;
+  if (g_acc && g_acc_len != len && fleet_acc_count(g_acc) == 0) {
+    fleet_acc_destroy(g_acc);
+    g_acc = nullptr;
+  }
+  if (!g_acc) {
+    std::vector<int32_t> pos(FLEET_MAX_HEADERS);
+    int nh = 0;
+    size_t walk = 0;
+    rc = fleet_layout_parse(c, p, len, pos.data(), FLEET_MAX_HEADERS, &nh, &walk);
+    if (rc == FLEET_OK && walk != fleet_b64_count(len)) {
+      // the accumulator takes the layout as covering the whole upload (fleet_codec.h)
+      *what = what_longer;
+      rc = FLEET_ERR_LAYOUT;
+    }
+    if (rc == FLEET_OK) rc = fleet_acc_create(c, len, pos.data(), nh, 0, (size_t)-1, &g_acc);
+    if (rc == FLEET_OK) g_acc_len = len;
+  }
+  return rc;
+}
+
 JNIEXPORT jboolean JNICALL Java_apps_cppNN_FleetUpdater_pushNative(JNIEnv* env, jobject, jbyteArray g, jdouble dampen) {
   fleet_ctx* c = ctx();
   if (!c) return JNI_FALSE;
@@ -454,27 +478,93 @@ JNIEXPORT jboolean JNICALL Java_apps_cppNN_FleetUpdater_pushNative(JNIEnv* env, 
     fail(c, "pushNative (array not granted)", FLEET_ERR_NOMEM);
     return JNI_FALSE;
   }
-  int rc = FLEET_OK;
   const char* what = "pushNative";
-  if (g_acc && g_acc_len != len && fleet_acc_count(g_acc) == 0) {
-    fleet_acc_destroy(g_acc);
-    g_acc = nullptr;
-  }
-  if (!g_acc) {
-    std::vector<int32_t> pos(FLEET_MAX_HEADERS);
-    int nh = 0;
-    size_t walk = 0;
-    rc = fleet_layout_parse(c, p, len, pos.data(), FLEET_MAX_HEADERS, &nh, &walk);
-    if (rc == FLEET_OK && walk != fleet_b64_count(len)) {
-      // the accumulator takes the layout as covering the whole upload (fleet_codec.h)
-      what = "pushNative (the upload is longer than its layout: use aggregateNative)";
-      rc = FLEET_ERR_LAYOUT;
-    }
-    if (rc == FLEET_OK) rc = fleet_acc_create(c, len, pos.data(), nh, 0, (size_t)-1, &g_acc);
-    if (rc == FLEET_OK) g_acc_len = len;
-  }
+  int rc = process_acc(c, p, len, &what, "pushNative (the upload is longer than its layout: use aggregateNative)");
   if (rc == FLEET_OK) rc = fleet_acc_push(g_acc, p, len, (double)dampen);
   env->ReleasePrimitiveArrayCritical(g, const_cast<char*>(p), JNI_ABORT);
+  if (rc != FLEET_OK) {
+    fail(c, what, rc);
+    return JNI_FALSE;
+  }
+  return JNI_TRUE;
+}
+
+// Several uploads that arrived together, folded in array order by one kernel per
+// fleet_acc_burst() of them (fleet_acc_push_many): all or nothing -- false, and the
+// batch as it was, when one of them is null, of another length, malformed or of another
+// layout. The arrays are read as aggregateNative reads them: in place inside one
+// critical region when the JVM grants K local references, else copied one at a time.
+JNIEXPORT jboolean JNICALL Java_apps_cppNN_FleetUpdater_pushBatchNative(JNIEnv* env, jobject, jobjectArray uploads,
+                                                                        jdoubleArray dampen) {
+  fleet_ctx* c = ctx();
+  if (!c) return JNI_FALSE;
+  if (!uploads || !dampen) {
+    fail(c, "pushBatchNative (null argument)", FLEET_ERR_ARG);
+    return JNI_FALSE;
+  }
+  const jsize K = env->GetArrayLength(uploads);
+  if (K <= 0 || env->GetArrayLength(dampen) != K) {
+    fail(c, "pushBatchNative (argument sizes)", FLEET_ERR_ARG);
+    return JNI_FALSE;
+  }
+  std::vector<double> d((size_t)K);
+  env->GetDoubleArrayRegion(dampen, 0, K, d.data());
+  std::vector<const char*> ptrs((size_t)K, nullptr);
+  std::vector<size_t> lens((size_t)K, 0);
+  const char* what = "pushBatchNative";
+  const char* longer = "pushBatchNative (the upload is longer than its layout: use aggregateNative)";
+  int rc = FLEET_OK;
+  std::lock_guard<std::mutex> lk(g_acc_mu);
+  if (env->EnsureLocalCapacity(K) == JNI_OK) {
+    std::vector<jbyteArray> arrs((size_t)K, nullptr);
+    for (jsize i = 0; i < K && rc == FLEET_OK; ++i) {
+      arrs[(size_t)i] = (jbyteArray)env->GetObjectArrayElement(uploads, i);
+      if (!arrs[(size_t)i]) rc = FLEET_ERR_ARG;
+      else lens[(size_t)i] = (size_t)env->GetArrayLength(arrs[(size_t)i]);
+      if (rc == FLEET_OK && lens[(size_t)i] != lens[0]) rc = FLEET_ERR_ARG;
+    }
+    if (rc != FLEET_OK) what = "pushBatchNative (null or ragged upload)";
+    jsize pinned = 0;
+    if (rc == FLEET_OK) {
+      for (; pinned < K; ++pinned) {
+        ptrs[(size_t)pinned] = static_cast<const char*>(env->GetPrimitiveArrayCritical(arrs[(size_t)pinned], nullptr));
+        if (!ptrs[(size_t)pinned]) break;
+      }
+      rc = pinned == K ? process_acc(c, ptrs[0], lens[0], &what, longer) : FLEET_ERR_NOMEM;
+      if (rc == FLEET_OK) rc = fleet_acc_push_many(g_acc, ptrs.data(), lens.data(), (int)K, d.data());
+      for (jsize i = pinned; i-- > 0;)
+        env->ReleasePrimitiveArrayCritical(arrs[(size_t)i], const_cast<char*>(ptrs[(size_t)i]), JNI_ABORT);
+    }
+    for (jsize i = 0; i < K; ++i)
+      if (arrs[(size_t)i]) env->DeleteLocalRef(arrs[(size_t)i]);
+  } else {
+    env->ExceptionClear();  // the OutOfMemoryError of the refused capacity
+    std::lock_guard<std::mutex> rows_lk(g_rows_mu);
+    size_t len = 0, pitch = 0;
+    for (jsize i = 0; i < K && rc == FLEET_OK; ++i) {
+      jbyteArray a = (jbyteArray)env->GetObjectArrayElement(uploads, i);
+      if (!a) {
+        rc = FLEET_ERR_ARG;
+        break;
+      }
+      const size_t li = (size_t)env->GetArrayLength(a);
+      if (i == 0) {
+        len = li;
+        pitch = (len + 15) / 16 * 16;
+        if (g_rows.size() < pitch * (size_t)K) g_rows.resize(pitch * (size_t)K);
+      }
+      if (li != len) rc = FLEET_ERR_ARG;
+      else env->GetByteArrayRegion(a, 0, (jsize)len, reinterpret_cast<jbyte*>(g_rows.data() + (size_t)i * pitch));
+      env->DeleteLocalRef(a);
+    }
+    if (rc != FLEET_OK) what = "pushBatchNative (null or ragged upload)";
+    for (jsize i = 0; i < K && rc == FLEET_OK; ++i) {
+      ptrs[(size_t)i] = g_rows.data() + (size_t)i * pitch;
+      lens[(size_t)i] = len;
+    }
+    if (rc == FLEET_OK) rc = process_acc(c, ptrs[0], len, &what, longer);
+    if (rc == FLEET_OK) rc = fleet_acc_push_many(g_acc, ptrs.data(), lens.data(), (int)K, d.data());
+  }
   if (rc != FLEET_OK) {
     fail(c, what, rc);
     return JNI_FALSE;

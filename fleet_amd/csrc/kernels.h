@@ -100,6 +100,17 @@ hipError_t launch_acc_push(const uint8_t* row, const float* st_in, float* st_out
 hipError_t launch_acc_finish(const uint8_t* last_row, const float* st, double inv, int64_t n_up, int64_t g_begin,
                              int64_t g_end, const int32_t* d_hdr_block, uint8_t* merged, float* merged_f32,
                              hipStream_t s);
+// A burst of K <= kAccBurst uploads folded by one launch (k_acc_push_many): rows 0..K-2
+// at rows + k * pitch, row K-1 at last_row, all in window coordinates; dampen holds K
+// factors (host memory: they travel in the kernel arguments). `first`: row 0 is the
+// batch's first upload (st_in unread, hfirst[] written). st_in may equal st_out. With
+// `finish` the launch ends in k_acc_finish's epilogue (inv = 1 / uploads of the batch;
+// merged / merged_f32 in whole-upload addressing) and stores no state.
+constexpr int kAccBurst = 64;
+hipError_t launch_acc_push_many(const uint8_t* rows, size_t pitch, const uint8_t* last_row, const float* st_in,
+                                float* st_out, int first, int K, const double* dampen, bool finish, double inv,
+                                int64_t n_up, int64_t g_begin, int64_t g_end, const int32_t* d_hdr_block,
+                                int32_t* d_hfirst, int* d_err, uint8_t* merged, float* merged_f32, hipStream_t s);
 hipError_t launch_encode_minibatch(const float* images, int64_t n_images, int F, const int32_t* labels,
                                    const int32_t* idx, int B, const float* teacher, int NL, const float header[7],
                                    uint8_t* out, int* err, hipStream_t s);

@@ -199,6 +199,12 @@ class FleetUpdater:
         self.acc.append(p)
         if len(self.acc) < self.M:  # M-softsync (:388-391)
             return None
+        return self._finish_batch()
+
+    def _finish_batch(self, fused=None) -> bytes:
+        """The M-th call's part after the arrival (:420-421, :463-464, :490-516): picks the
+        batch, merges it (``fused``: the (merged, grad) a push_finish already produced) and
+        steps the model."""
         picked, dampen = [], []
         window = [0] * len(self.global_labels)
         for _ in range(self.M):  # FIFO (:420-421)
@@ -209,7 +215,9 @@ class FleetUpdater:
                 window[j] += v
         for j, v in enumerate(window):
             self.global_labels[j] += v
-        if self.streaming:
+        if fused is not None:
+            merged, grad = fused
+        elif self.streaming:
             merged, grad = self._stream_acc.finish(want_f32=True)
         else:
             merged, grad = self.codec.update(picked, dampen, want_f32=True)
@@ -221,3 +229,43 @@ class FleetUpdater:
         self.acc.clear()  # aggregated.clear() (:516)
         self.last_merged = merged
         return merged
+
+    def update_many(self, arrivals) -> List[Optional[bytes]]:
+        """Several uploads that are at hand together: ``arrivals`` is a list of ``(upload,
+        labels, epoch, client_id)``, the result the list of what ``update`` returns for each
+        in turn. With ``streaming=True`` the list is cut at batch boundaries and each run is
+        folded by one call: ``push_many`` for a run that leaves the batch open,
+        ``push_finish`` (the fold and the merged gradient from one kernel) followed by the
+        model step for a run that completes it. The factors are computed at arrival, as
+        ``update`` does; ``_dampen_of`` reads ``curr_epoch`` and ``global_labels``, which the
+        model step changes, so a run's factors are computed after the previous run's step.
+        A run is all or nothing: a malformed upload raises and none of its run joins the
+        batch (the runs before it stay)."""
+        arrivals = list(arrivals)
+        if not self.streaming:
+            return [self.update(*a) for a in arrivals]
+        out: List[Optional[bytes]] = []
+        i = 0
+        while i < len(arrivals):
+            room = self.M - len(self.acc)
+            run = [Pending(bytes(u), list(l), int(e), int(cid)) for u, l, e, cid in arrivals[i: i + room]]
+            i += len(run)
+            a = self._stream_acc
+            if a is None or (a.length != len(run[0].upload) and a.count == 0):
+                if a is not None:
+                    a.close()
+                a = self._stream_acc = self.codec.accumulator(len(run[0].upload), self.layout.header_positions())
+            for p in run:
+                p.dampen = self._dampen_of(p)
+            ups, d = [p.upload for p in run], [p.dampen for p in run]
+            fused = None
+            if len(run) == room:
+                fused = a.push_finish(ups, d, want_f32=True)
+            else:
+                a.push_many(ups, d)
+            for p in run:
+                p.upload = b""
+            self.acc.extend(run)
+            out += [None] * (len(run) - 1)
+            out.append(self._finish_batch(fused) if fused is not None else None)
+        return out

@@ -305,6 +305,51 @@ int fleet_acc_finish_device(fleet_acc* acc, void* d_merged, void* d_merged_f32, 
 /* Drops what was pushed (a half-filled batch, CppNNUpdater.java:383-391's `acc`
  * cleared) and clears a sticky error; waits for the accumulator's device work. */
 int fleet_acc_reset(fleet_acc* acc);
+/* Bursts: K >= 1 uploads that are at hand together (a server draining its request
+ * queue, a device-side producer) folded in arrival order by one kernel per
+ * fleet_acc_burst() uploads, the running value held in registers across the
+ * clients, so the state is read and written once per launch instead of once per
+ * upload. Each step is fleet_acc_push's, so the bytes are those of K single pushes;
+ * dampen[k] is upload k's getDampen factor (the K factors travel in the kernel
+ * arguments). FLEET_ERR_ARG, before anything is copied: K <= 0, a NULL array or entry,
+ * lens[k] != len, and for the device forms with K > 1 a base or pitch that is not a
+ * multiple of 16 or a pitch below 16*ceil(len/16) (rows 0..K-2 are read in place
+ * with 16-byte loads; only row K-1's window is copied into the accumulator's spare
+ * row, where the finish finds the last accepted upload).
+ *
+ * fleet_acc_push_many is synchronous and all-or-nothing: the windows go through
+ * pinned staging to device staging (at most fleet_acc_burst() rows of the window's
+ * 16*groups + 64 bytes each on both sides, grown on demand, kept until
+ * fleet_acc_destroy; a burst longer than that is staged and launched in chunks), one
+ * stream synchronisation reads the error word, and on FLEET_ERR_BASE64 or
+ * FLEET_ERR_LAYOUT from any of the K uploads the state, the last row and the count
+ * are exactly as before the call; on success the count grows by K. (DMA straight
+ * from page-locked rows the caller registered is not offered.)
+ * fleet_acc_push_many_device is asynchronous on the caller's stream and commits at
+ * once, a bad upload leaving a sticky error, exactly like fleet_acc_push_device; the
+ * caller may reuse d_uploads as soon as the stream allows. Not for graph capture.
+ *
+ * fleet_acc_push_finish* fold the burst and produce fleet_acc_finish's outputs in the
+ * same launch: the last kernel applies the average and the merge to its registers and
+ * stores no state (the arrival that completes a batch pays one launch, not two). Both
+ * forms synchronise to read the error word, so both are transactional: on an error of
+ * one of the K uploads nothing is committed, the count is unchanged and the outputs
+ * are not meaningful; an error left by an earlier fleet_acc_push_device of the same
+ * batch stays sticky and comes first. On success the count returns to 0. The device
+ * form uses fleet_acc_finish_device's addressing.
+ *
+ * Resident bytes of an accumulator over G groups: two states (2 * 12 G), two device
+ * rows and two pinned rows (4 * 16 G), and after a host burst of K uploads the staging,
+ * min(K - 1, fleet_acc_burst()) rows of 16 G bytes in HBM and as many pinned. */
+int fleet_acc_push_many(fleet_acc* acc, const char* const* uploads, const size_t* lens, int K, const double* dampen);
+int fleet_acc_push_many_device(fleet_acc* acc, const void* d_uploads, size_t pitch, int K, const double* dampen,
+                               void* stream);
+int fleet_acc_push_finish(fleet_acc* acc, const char* const* uploads, const size_t* lens, int K, const double* dampen,
+                          char* merged, size_t cap, size_t* out_len, float* merged_f32);
+int fleet_acc_push_finish_device(fleet_acc* acc, const void* d_uploads, size_t pitch, int K, const double* dampen,
+                                 void* d_merged, void* d_merged_f32, void* stream);
+/* B: uploads folded per launch. */
+int fleet_acc_burst(void);
 
 /* Self-test of the device codec arithmetic over whole input domains: an
  * order-independent 64-bit digest sum_i splitmix64(i<<32 | f(i)) of

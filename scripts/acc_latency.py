@@ -11,6 +11,12 @@ workloads, the rows page-locked with fleet_host_register), per workload:
                  registered rows, the best host path without an accumulator.
   total          all M pushes + the finish against that same batch call: what streaming
                  costs in throughput.
+  burst          beside those, alternating with them in the same repetitions: the batch
+                 folded in bursts of K in {4, 16, 64, M} (fleet_acc_push_many, the last burst
+                 through fleet_acc_push_finish), the post-arrival time of push_finish with
+                 K = 1, and the device-resident fold in bursts of fleet_acc_burst() uploads
+                 (push_many_device, the last through push_finish_device) against M
+                 push_device calls. Compare them with the single-push lines of the same run.
   resident       device bytes each path holds (from the shapes; the accumulator's two
                  states and two rows against the batch call's M rows and outputs).
 
@@ -24,7 +30,8 @@ the identical call). No fallback: without a GPU the script fails.
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o run -- \
       python scripts/acc_latency.py --trace-only       # per-kernel times, a run of its own
   python scripts/acc_latency.py --kernel-stats DIR/.../run_kernel_stats.csv --out FILE.json
-      # adds k_acc_push / k_acc_finish achieved TB/s (algorithmic bytes from the shapes)
+      # adds k_acc_push / k_acc_finish / k_acc_push_many achieved TB/s (algorithmic bytes from
+      # the shapes; the trace's bursts are launches of fleet_acc_burst() uploads each)
 """
 import argparse
 import csv
@@ -86,6 +93,32 @@ def measure(torch, codec, name, reps, trace_only=False):
         codec._check(lib.fleet_acc_finish(acc._h, out.ctypes.data, len(out), C.byref(n), None))
         return out[:L].tobytes()
 
+    # bursts: the C entry points on slices of one pointer / length / factor array
+    B = F.ACC_BURST
+    P = (C.c_void_p * M)(*ptr)
+    lens = np.full(M, L, np.uint64)
+    dd = np.ascontiguousarray(d, np.float64)
+    # (addresses taken once: numpy's .ctypes costs microseconds, which a 60 us call would show)
+    p_at, lens_at, dd_at, out_at = C.addressof(P), lens.ctypes.data, dd.ctypes.data, out.ctypes.data
+
+    def push_many(i, k):
+        codec._check(lib.fleet_acc_push_many(acc._h, p_at + 8 * i, lens_at + 8 * i, k, dd_at + 8 * i))
+
+    def push_finish(i, k):
+        codec._check(lib.fleet_acc_push_finish(acc._h, p_at + 8 * i, lens_at + 8 * i, k, dd_at + 8 * i, out_at, len(out),
+                                               C.byref(n), None))
+        return out[:L].tobytes()
+
+    def in_bursts(K):
+        """The whole batch in bursts of K, the last one through push_finish."""
+        i = 0
+        while M - i > K:
+            push_many(i, K)
+            i += K
+        return push_finish(i, M - i)
+
+    burst_ks = sorted({k for k in (4, 16, 64, M) if k <= M})
+
     codec.register_host(rows)
     try:
         expect = codec.update_rows(rows, L, d)  # warm-up of the batch path (staging, allocations)
@@ -93,13 +126,18 @@ def measure(torch, codec, name, reps, trace_only=False):
             push(c)
         if finish() != expect:
             raise RuntimeError("streaming result differs from fleet_update_rows")
+        for K in ([B] if trace_only else burst_ks + [1]):  # (a trace holds launches of B uploads alone)
+            if in_bursts(K) != expect:
+                raise RuntimeError(f"bursts of {K} differ from fleet_update_rows")
         if trace_only:
             for _ in range(3):
                 for c in range(M):
                     push(c)
                 finish()
+                in_bursts(B)  # launches of B uploads each (M a multiple of B) for the kernel's bytes
             return None
         post_s, post_b, tot_s, tot_b = [], [], [], []
+        post_f, tot_k = [], {K: [] for K in burst_ks}
         for _ in range(reps):  # the two paths alternate
             for c in range(M - 1):
                 push(c)
@@ -118,6 +156,16 @@ def measure(torch, codec, name, reps, trace_only=False):
             t0 = time.perf_counter()
             codec.update_rows(rows, L, d)
             tot_b.append(time.perf_counter() - t0)
+            # the M-th arrival through the fused call (M - 1 uploads folded before the clock)
+            if M > 1:
+                push_many(0, M - 1)
+            t0 = time.perf_counter()
+            push_finish(M - 1, 1)
+            post_f.append(time.perf_counter() - t0)
+            for K in burst_ks:
+                t0 = time.perf_counter()
+                in_bursts(K)
+                tot_k[K].append(time.perf_counter() - t0)
     finally:
         codec.unregister_host(rows)
     # the device-resident fold, by device events: M push_device + finish_device on rows in HBM
@@ -126,8 +174,8 @@ def measure(torch, codec, name, reps, trace_only=False):
     dev[:, :L] = torch.from_numpy(rows).cuda()
     merged = torch.zeros(pitch, dtype=torch.uint8, device="cuda")
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    dev_ms = []
-    for r in range(reps + 1):
+    dev_ms, dev_burst_ms = [], []
+    for r in range(reps + 1):  # single device pushes and bursts of B alternate
         a.record()
         for c in range(M):
             acc.push_device(dev[c], d[c])
@@ -136,10 +184,24 @@ def measure(torch, codec, name, reps, trace_only=False):
         b.synchronize()
         if r:
             dev_ms.append(a.elapsed_time(b) * 1e-3)
-    if merged.cpu().numpy()[:L].tobytes() != expect:
+        else:
+            single = merged.cpu().numpy()[:L].tobytes()
+            merged.zero_()
+        a.record()
+        i = 0
+        while M - i > B:
+            acc.push_many_device(dev[i: i + B], d[i: i + B])
+            i += B
+        acc.push_finish_device(dev[i:], d[i:], merged)
+        b.record()
+        b.synchronize()
+        if r:
+            dev_burst_ms.append(a.elapsed_time(b) * 1e-3)
+    if single != expect or merged.cpu().numpy()[:L].tobytes() != expect:
         raise RuntimeError("device-resident streaming result differs from fleet_update_rows")
     acc.close()
     res_stream = 2 * 12 * groups + 2 * 16 * groups
+    launches = (M + B - 1) // B
     res_batch = M * 16 * groups + 16 * groups + 8 * M
     return {
         "workload": name, "M": M, "upload_bytes": L, "groups": groups,
@@ -148,6 +210,23 @@ def measure(torch, codec, name, reps, trace_only=False):
         "total": {"streaming_M_pushes_plus_finish": spread(tot_s), "batch_update_rows_registered": spread(tot_b),
                   "streaming_over_batch": min(tot_s) / min(tot_b)},
         "device_resident_fold_M_pushes_plus_finish": spread(dev_ms),
+        "burst": {
+            "uploads_per_launch": B,
+            "total_in_bursts_of_K_last_through_push_finish": {str(K): spread(ts) for K, ts in tot_k.items()},
+            "bursts_of_16_over_single_pushes": min(tot_k[16]) / min(tot_s) if 16 in tot_k else None,
+            "post_arrival_push_finish_K1": spread(post_f),
+            "post_arrival_push_finish_over_push_plus_finish": min(post_f) / min(post_s),
+            "device_resident_fold_in_bursts_of_B": spread(dev_burst_ms),
+            "device_burst_fold_over_single_fold": min(dev_burst_ms) / min(dev_ms),
+            # staging of a host burst: min(K - 1, B) window rows in HBM (and as many pinned on the host)
+            "resident_device_bytes_with_staging": {str(K): res_stream + min(K - 1, B) * 16 * groups for K in burst_ks},
+            # per launch of K = B uploads: 16 K row bytes, the 12-byte state read (not by a batch's first launch)
+            # and written (the finish form writes the 16-byte merged group instead)
+            "algorithmic_bytes": {"k_acc_push_many_K": B, "k_acc_push_many": groups * (16 * B + 12 + 12),
+                                  "k_acc_push_many_mean_of_batch": groups * (16 * B + 12 + 12) - (
+                                      groups * 12 / (launches - 1) if launches > 1 else 0),
+                                  "k_acc_push_many_finish_form": groups * (16 * B + (12 if launches > 1 else 0) + 16)},
+        },
         "resident_device_bytes": {"streaming": res_stream, "batch": res_batch, "batch_over_streaming": res_batch / res_stream},
         "algorithmic_bytes": algorithmic_bytes(groups, M),
     }
@@ -162,8 +241,14 @@ def kernel_rates(stats_csv, results):
         for r in csv.DictReader(f):
             rows[r["Name"].split("(")[0]] = r
     out = {}
-    for k in ("k_acc_push", "k_acc_finish"):
-        hit = next((v for n, v in rows.items() if k in n), None)
+    names = {"k_acc_push": lambda n: "k_acc_push" in n and "k_acc_push_many" not in n,
+             "k_acc_finish": lambda n: "k_acc_finish" in n,
+             "k_acc_push_many": lambda n: "k_acc_push_many<false>" in n or "k_acc_push_manyILb0" in n,
+             "k_acc_push_many_finish_form": lambda n: "k_acc_push_many<true>" in n or "k_acc_push_manyILb1" in n}
+    for k, match in names.items():
+        hit = next((v for n, v in rows.items() if match(n)), None)
+        if hit is None and k.startswith("k_acc_push_many"):
+            continue  # a trace of a batch of at most one launch's uploads holds the finish form alone
         if hit is None:
             raise RuntimeError(f"{k} is not in {stats_csv}: the native kernels did not run")
         out[k] = {"calls": int(hit["Calls"]), "avg_us": float(hit["AverageNs"]) / 1e3, "min_us": float(hit["MinNs"]) / 1e3,
@@ -200,6 +285,11 @@ def main():
             ab = r["algorithmic_bytes"]
             k["k_acc_push"]["tb_s"] = ab["k_acc_push_mean_of_M"] / (k["k_acc_push"]["avg_us"] * 1e-6) / 1e12
             k["k_acc_finish"]["tb_s"] = ab["k_acc_finish"] / (k["k_acc_finish"]["avg_us"] * 1e-6) / 1e12
+            bb = r["burst"]["algorithmic_bytes"]
+            for kk, key in (("k_acc_push_many", "k_acc_push_many_mean_of_batch"),
+                            ("k_acc_push_many_finish_form", "k_acc_push_many_finish_form")):
+                if kk in k:
+                    k[kk]["tb_s"] = bb[key] / (k[kk]["avg_us"] * 1e-6) / 1e12
             for v in k.values():
                 v["fraction_of_8_tb_s"] = v["tb_s"] * 1e12 / HBM_PEAK
             r["kernels"] = k
