@@ -484,7 +484,12 @@ class Codec:
         window=False: the tensors hold whole rows (group 0 at column 0).
         window=True: they hold only the groups [group_begin, group_end) of every
         row (uploads [M, >= 16*(ge-gb)], merged [16*(ge-gb)], merged_f32
-        [3*(ge-gb)]); header_pos stay in whole-upload coordinates."""
+        [3*(ge-gb)]); header_pos stay in whole-upload coordinates.
+
+        header_pos (here and in update_encode_device / update_kardam_device / accumulator):
+        strictly ascending positions inside [0, b64_count(length)), at most
+        FLEET_MAX_HEADERS; any other list raises FleetError (FLEET_ERR_ARG), nothing is
+        launched and the context keeps the parameters of its last accepted call."""
         M, pitch = uploads_u8.shape
         groups = (b64_count(length) + 2) // 3
         ge = groups if group_end is None else min(group_end, groups)
@@ -566,7 +571,8 @@ class Codec:
     def synth_device(self, seed: int, values_f32, n_up: int, header_pos, header_val, client0: int = 0,
                      stream=None, elem0: int = 0):
         """Synthetic buckets (fleet_synth_window_device): rows client0.. of a problem whose
-        elements elem0 .. elem0 + n_up this tensor holds; header_pos in its coordinates."""
+        elements elem0 .. elem0 + n_up this tensor holds; header_pos in its coordinates,
+        each inside [0, n_up) (else FleetError, FLEET_ERR_ARG, before anything is launched)."""
         M, vpitch = values_f32.shape
         hp = np.ascontiguousarray(header_pos, dtype=np.int32)
         hv = np.ascontiguousarray(header_val, dtype=np.float32)

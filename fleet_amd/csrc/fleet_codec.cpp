@@ -958,6 +958,22 @@ int fleet_host_unregister(fleet_ctx* c, void* ptr) {
 
 namespace {
 
+struct DevMem {
+  void* p = nullptr;
+  ~DevMem() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+// A caller's header list for an upload of n values: the kernels search it, so the
+// positions are strictly ascending and inside [0, n).
+int check_header_positions(fleet_ctx* c, const int32_t* header_pos, int n_headers, size_t n) {
+  for (int i = 0; i < n_headers; ++i)
+    if (header_pos[i] < 0 || (size_t)header_pos[i] >= n || (i && header_pos[i] <= header_pos[i - 1]))
+      return fail(c, FLEET_ERR_ARG, "header position %d (%d) is not ascending inside the upload", i, header_pos[i]);
+  return FLEET_OK;
+}
+
 // The device-resident update's parameters ({status, count, walk_end, 0, positions}
 // and dampen): kept resident in the context's own buffers and re-uploaded (one
 // sync) only when they change, so steady-state calls are pure kernel launches.
@@ -972,6 +988,10 @@ int dev_params(fleet_ctx* c, hipStream_t s, size_t n, int M, const double* dampe
   if (!c->dev_params_valid || c->dev_hdr != hdr_words || c->dev_dampen.size() != (size_t)M ||
       std::memcmp(c->dev_dampen.data(), dampen, sizeof(double) * (size_t)M) != 0) {
     int rc;
+    // the stream kernels binary-search the list and the tiles stride over it: strictly
+    // ascending positions inside the upload (fleet_codec.h), as fleet_acc_create asks.
+    // Checked here, where the list is new; a steady-state call compares and launches.
+    if ((rc = check_header_positions(c, header_pos, n_headers, n))) return rc;
     // new parameters are uploaded synchronously, which a stream under capture
     // cannot do (it would invalidate the capture): the caller makes one eager
     // call with them first (fleet_codec.h, device-resident entry points)
@@ -1180,21 +1200,24 @@ int fleet_synth_window_device(fleet_ctx* c, uint64_t seed, int M, int client0, s
   if (!c || !d_values || M <= 0 || n_headers < 0 || n_headers > FLEET_MAX_HEADERS || vpitch < n_up)
     return FLEET_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
+  if (n_headers && (!header_pos || !header_val))
+    return fail(c, FLEET_ERR_ARG, "synth: %d headers without positions or values", n_headers);
+  // k_synth_headers stores at row * vpitch + position: every position inside this tensor's columns
+  for (int i = 0; i < n_headers; ++i)
+    if (header_pos[i] < 0 || (size_t)header_pos[i] >= n_up)
+      return fail(c, FLEET_ERR_ARG, "synth: header position %d (%d) is outside [0, %zu)", i, header_pos[i], n_up);
   DEVICE_SCOPE(c);
   hipStream_t s = pick(c, stream);
-  int32_t* d_pos = nullptr;
-  float* d_val = nullptr;
+  DevMem d_pos, d_val;  // freed on every path
   if (n_headers) {
-    HIP_TRY(c, hipMalloc((void**)&d_pos, sizeof(int32_t) * (size_t)n_headers));
-    HIP_TRY(c, hipMalloc((void**)&d_val, sizeof(float) * (size_t)n_headers));
-    HIP_TRY(c, hipMemcpy(d_pos, header_pos, sizeof(int32_t) * (size_t)n_headers, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(d_val, header_val, sizeof(float) * (size_t)n_headers, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMalloc(&d_pos.p, sizeof(int32_t) * (size_t)n_headers));
+    HIP_TRY(c, hipMalloc(&d_val.p, sizeof(float) * (size_t)n_headers));
+    HIP_TRY(c, hipMemcpy(d_pos.p, header_pos, sizeof(int32_t) * (size_t)n_headers, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_val.p, header_val, sizeof(float) * (size_t)n_headers, hipMemcpyHostToDevice));
   }
-  HIP_TRY(c, fleet::launch_synth(seed, client0, (int64_t)elem0, M, (int64_t)n_up, (float*)d_values, vpitch, d_pos,
-                                 d_val, n_headers, s));
+  HIP_TRY(c, fleet::launch_synth(seed, client0, (int64_t)elem0, M, (int64_t)n_up, (float*)d_values, vpitch,
+                                 (const int32_t*)d_pos.p, (const float*)d_val.p, n_headers, s));
   HIP_TRY(c, hipStreamSynchronize(s));
-  if (d_pos) (void)hipFree(d_pos);
-  if (d_val) (void)hipFree(d_val);
   return FLEET_OK;
 }
 
@@ -1213,13 +1236,6 @@ static int model_total(fleet_ctx* c, const int32_t* dims, int n_mats, size_t* n)
   *n = t;
   return FLEET_OK;
 }
-
-struct DevMem {
-  void* p = nullptr;
-  ~DevMem() {
-    if (p) (void)hipFree(p);
-  }
-};
 
 // quantize + dictionary on the device; leaves d_index and the dictionary on the host
 static int model_run(fleet_ctx* c, const float* weights, const int32_t* dims, int n_mats, size_t n, float* quantized,
@@ -1382,6 +1398,8 @@ int fleet_kardam_grads(fleet_ctx* c, const char* const* uploads, const size_t* l
     if (!uploads[i] || lens[i] != len)
       return fail(c, FLEET_ERR_ARG, "upload %d has length %zu, expected %zu (one model layout)", i, lens[i], len);
   const size_t n = fleet_b64_count(len);
+  // no caller positions here: the list k_kardam_grads counts over is this walk's own,
+  // ascending and inside [0, n) by construction (host_layout_parse), so nothing to validate
   std::vector<int32_t> hw(kHdrWords);
   host_layout_parse(uploads[M - 1], len, (int64_t)n, FLEET_MAX_HEADERS, hw.data());
   if (hw[0] != 0) return fail(c, FLEET_ERR_LAYOUT, "last upload's header does not describe a gradient layout");
@@ -1859,9 +1877,7 @@ int fleet_acc_create(fleet_ctx* c, size_t len, const int32_t* header_pos, int n_
   if (16 * groups + 16 >= ((size_t)1 << 31)) return fail(c, FLEET_ERR_ARG, "upload of %zu bytes: 2 GiB or more", len);
   if (group_end > groups) group_end = groups;
   if (group_begin > group_end) return fail(c, FLEET_ERR_ARG, "group window [%zu, %zu) is empty or reversed", group_begin, group_end);
-  for (int i = 0; i < n_headers; ++i)  // the kernels search the list: ascending positions inside the upload
-    if (header_pos[i] < 0 || (size_t)header_pos[i] >= n || (i && header_pos[i] <= header_pos[i - 1]))
-      return fail(c, FLEET_ERR_ARG, "header position %d (%d) is not ascending inside the upload", i, header_pos[i]);
+  if ((rc = check_header_positions(c, header_pos, n_headers, n))) return rc;
   fleet_acc* a = new fleet_acc();
   a->c = c;
   a->len = len;

@@ -170,6 +170,18 @@ int fleet_last_ingress(fleet_ctx* ctx);
  * rank holding just its window of every upload passes the window's address
  * minus 16*group_begin (3*group_begin floats for merged_f32) and pitch >=
  * 16*(group_end - group_begin): fleet_amd/shard.py does exactly that.
+ * header_pos (a host array, whole-upload coordinates, at most FLEET_MAX_HEADERS
+ * entries; fleet_layout_from_sizes / fleet_layout_parse produce it) holds
+ * strictly ascending positions inside [0, fleet_b64_count(len)): the kernels
+ * search the list. fleet_update_device, fleet_update_encode_device,
+ * fleet_update_kardam_device and fleet_acc_create return FLEET_ERR_ARG for any
+ * other list (unsorted, duplicate, negative, past the upload) and launch
+ * nothing; the context's resident parameters stay those of the last accepted
+ * call. The list is checked when it differs from the resident one, so a
+ * steady-state call makes no extra pass over it. fleet_synth(_window)_device's
+ * header_pos are store targets in the tensor's own columns: each inside
+ * [0, n_up), any order, header_pos and header_val non-NULL when n_headers > 0,
+ * else FLEET_ERR_ARG before anything is allocated or launched.
  * Graph capture: the dampen and header words live in ONE device buffer per
  * context, re-uploaded (synchronously) whenever a call passes different ones.
  * Every graph captured on the context therefore replays with the parameters of
@@ -223,7 +235,8 @@ int fleet_synth_device(fleet_ctx* ctx, uint64_t seed, int M, int client0, const 
                        void* stream);
 /* The same for a column window of a larger synthetic problem: values n_up columns
  * from element elem0 (the counter is the global element index, so a rank's window
- * holds exactly the fixed problem's values there); header_pos in window coordinates. */
+ * holds exactly the fixed problem's values there); header_pos in window coordinates,
+ * each inside [0, n_up) (see the device-resident entry points above). */
 int fleet_synth_window_device(fleet_ctx* ctx, uint64_t seed, int M, int client0, size_t elem0,
                               const int32_t* header_pos, const float* header_val, int n_headers, size_t n_up,
                               void* d_values, size_t vpitch, void* stream);
