@@ -67,7 +67,8 @@ def test_plan_overrides_validated_on_host():
     """fleet_set_plan is host-only: a spec with an unknown key or value is rejected
     as a whole (the plan stays as it was), a valid one is normalised, "" restores
     the default. No environment variable other than FLEET_EXPERIMENTS (read once)
-    reaches the launch path (kernels.hip reads no other)."""
+    reaches the launch path (no kernel unit, header or fleet_codec.cpp reads another)."""
+    import glob
     import os
     F.set_plan("")
     for bad in ("update=fast", "k_update=stream", "grid", "stage_pieces=0", "fused=1", "update=stream,tile_mix=off",
@@ -79,9 +80,12 @@ def test_plan_overrides_validated_on_host():
     assert F.plan() == "update=pipe,fused=off,stage_threads=3"
     F.set_plan("")
     assert F.plan() == ""
-    src = open(os.path.join(F.ROOT, "fleet_amd", "csrc", "kernels.hip")).read()
+    csrc = os.path.join(F.ROOT, "fleet_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(files) >= 10  # the kernel units and their headers are all here
+    src = "".join(open(f).read() for f in files + [os.path.join(csrc, "fleet_codec.cpp")])
     assert src.count("getenv(") == 1 and 'getenv("FLEET_EXPERIMENTS")' in src
-    assert "getenv(" not in open(os.path.join(F.ROOT, "fleet_amd", "csrc", "fleet_codec.cpp")).read()
+    assert 'getenv("FLEET_EXPERIMENTS")' in open(os.path.join(csrc, "kernels.hip")).read()
 
 
 GRID_SIZES = [1, 2, 16, 17, 83, 84, 85, 255, 256, 257, 6_667, 7_654, 16_668, 32_768, 50_001, 65_537, 100_001,
