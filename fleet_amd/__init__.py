@@ -118,6 +118,16 @@ def lib() -> C.CDLL:
         "fleet_acc_push_finish": (i32, [vp, vp, vp, i32, vp, vp, sz, szp, vp]),
         "fleet_acc_push_finish_device": (i32, [vp, vp, sz, i32, vp, vp, vp, vp]),
         "fleet_acc_burst": (i32, []),
+        "fleet_pool_create": (i32, [vp, sz, vp, i32, sz, sz, i32, C.POINTER(vp)]),
+        "fleet_pool_destroy": (None, [vp]),
+        "fleet_pool_slots": (i32, [vp]),
+        "fleet_pool_occupied": (i32, [vp, i32]),
+        "fleet_pool_put": (i32, [vp, i32, vp, sz]),
+        "fleet_pool_put_device": (i32, [vp, i32, vp, vp]),
+        "fleet_pool_drop": (i32, [vp, i32]),
+        "fleet_pool_update": (i32, [vp, vp, i32, vp, vp, sz, szp, vp]),
+        "fleet_pool_update_device": (i32, [vp, vp, i32, vp, vp, vp, vp]),
+        "fleet_pool_slot_status": (i32, [vp, i32]),
         "fleet_update_kernel": (C.c_char_p, [sz]),
         "fleet_update_plan_grid": (i32, [sz, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -462,6 +472,12 @@ class Codec:
         given layout header positions: each upload is folded into a resident sum when it
         arrives, and ``finish`` returns what ``update`` returns for the same uploads."""
         return Accumulator(self, length, header_pos, group_begin, group_end)
+
+    def pool(self, length: int, header_pos, slots: int, group_begin: int = 0, group_end: Optional[int] = None):
+        """An upload pool (fleet_pool) of `slots` resident uploads of `length` Base64 bytes:
+        uploads are put into slots when they arrive, and ``update`` over any subset of the
+        slots, in any order, returns what ``update`` returns for those uploads in that order."""
+        return Pool(self, length, header_pos, slots, group_begin, group_end)
 
     def update_rows(self, rows: np.ndarray, length: int, dampen: Sequence[float], want_f32: bool = False):
         """fleet_update over a uint8 host array [M, row_pitch] whose row i holds upload i's
@@ -943,6 +959,124 @@ class Accumulator:
         self.codec._check(self._L.fleet_acc_push_finish_device(
             self._h, u8_tensor.data_ptr(), pitch, K, d.ctypes.data, merged_u8.data_ptr(),
             merged_f32.data_ptr() if merged_f32 is not None else None, _stream(stream)))
+
+
+class Pool:
+    """Buffered uploads kept in HBM (fleet_pool, include/fleet_codec.h): the reference's
+    `acc` in the staleSize > 0 branch (CppNNUpdater.java:383-411), where
+    StalenessSimulator.stalenessSim picks, at update time, which buffered uploads to
+    aggregate and in which order. ``put`` / ``put_device`` store an arrival in a slot,
+    ``update`` / ``update_device`` aggregate any subset of occupied slots in the given
+    order and change no slot, ``drop`` frees one. When an update raises ``Base64Error`` or
+    ``LayoutError`` the pool is as before, and the exception's ``slots`` lists the picked
+    slots whose uploads were at fault (``slot_status``)."""
+
+    def __init__(self, codec: Codec, length: int, header_pos, slots: int, group_begin: int = 0,
+                 group_end: Optional[int] = None):
+        self.codec = codec
+        self._L = codec._L
+        self.length = int(length)
+        self.groups = (b64_count(self.length) + 2) // 3
+        self.group_begin = int(group_begin)
+        self.group_end = self.groups if group_end is None else min(int(group_end), self.groups)
+        hp = np.ascontiguousarray(header_pos, dtype=np.int32)
+        h = C.c_void_p()
+        self._h = None
+        codec._check(self._L.fleet_pool_create(codec._h, self.length, hp.ctypes.data, len(hp), self.group_begin,
+                                               self.group_end, int(slots), C.byref(h)))
+        self._h = h
+        self.slots = int(self._L.fleet_pool_slots(h))
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.codec, "_h", None):
+            self._L.fleet_pool_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _check(self, rc: int, picks=()):
+        try:
+            self.codec._check(rc)
+        except (Base64Error, LayoutError) as e:
+            e.slots = [int(s) for s in picks if self.slot_status(int(s)) > 0]
+            raise
+
+    def _slot_query(self, fn, slot: int) -> int:
+        v = fn(self._h, int(slot))
+        if v < 0:
+            raise FleetError(v, f"slot {slot} outside [0, {self.slots})")
+        return v
+
+    def occupied(self, slot: int) -> bool:
+        return bool(self._slot_query(self._L.fleet_pool_occupied, slot))
+
+    def free_slot(self) -> Optional[int]:
+        """The lowest free slot, or None when the pool is full."""
+        for s in range(self.slots):
+            if not self._L.fleet_pool_occupied(self._h, s):
+                return s
+        return None
+
+    def slot_status(self, slot: int) -> int:
+        """Error bits the last update saw in the slot's upload (1 Base64, 2 layout header)."""
+        return self._slot_query(self._L.fleet_pool_slot_status, slot)
+
+    def put(self, slot: int, upload) -> None:
+        s = _as_bytes(upload)
+        self._check(self._L.fleet_pool_put(self._h, int(slot), s, len(s)))
+
+    def put_device(self, slot: int, u8_tensor, stream=None) -> None:
+        """u8_tensor: a uint8 CUDA tensor holding the whole upload row (>= length bytes)."""
+        if u8_tensor.numel() < self.length:
+            raise ValueError("the tensor is shorter than the pool's uploads")
+        self._check(self._L.fleet_pool_put_device(self._h, int(slot), u8_tensor.data_ptr(), _stream(stream)))
+
+    def drop(self, slot: int) -> None:
+        self._check(self._L.fleet_pool_drop(self._h, int(slot)))
+
+    @staticmethod
+    def _pick_args(picks, dampens):
+        pk = np.ascontiguousarray(picks, dtype=np.int32)
+        if len(dampens) != len(pk):
+            raise ValueError("one dampening factor per pick")
+        return pk, np.ascontiguousarray(dampens, dtype=np.float64)
+
+    def update(self, picks, dampens, want_f32: bool = False):
+        """The merged Base64 of the uploads in the slots ``picks``, in that order (and, with
+        ``want_f32``, decodeFloat of it). With a group window only the window's bytes /
+        values of the returned buffers are written."""
+        pk, d = self._pick_args(picks, dampens)
+        out = np.zeros(self.length + 16, np.uint8)
+        n = C.c_size_t(0)
+        f32 = np.zeros(b64_count(self.length) + 1, np.float32) if want_f32 else None
+        self._check(self._L.fleet_pool_update(self._h, pk.ctypes.data, len(pk), d.ctypes.data, out.ctypes.data, len(out),
+                                              C.byref(n), f32.ctypes.data if want_f32 else None), pk)
+        merged = out[: n.value].tobytes()
+        if want_f32:
+            return merged, f32[: b64_count(self.length)].copy()
+        return merged
+
+    def update_device(self, picks, dampens, merged_u8, merged_f32=None, stream=None) -> None:
+        """merged_u8: uint8 CUDA tensor [>= 16 * groups], merged_f32: float32 [>= n values]
+        (whole-upload coordinates); synchronises the stream to read the slots' status."""
+        pk, d = self._pick_args(picks, dampens)
+        if merged_u8.numel() < 16 * self.groups or (
+                merged_f32 is not None and merged_f32.numel() < b64_count(self.length)):
+            raise ValueError("merged tensors smaller than the upload's groups")
+        self._check(self._L.fleet_pool_update_device(self._h, pk.ctypes.data, len(pk), d.ctypes.data,
+                                                     merged_u8.data_ptr(),
+                                                     merged_f32.data_ptr() if merged_f32 is not None else None,
+                                                     _stream(stream)), pk)
 
 
 def update_multi(codecs: Sequence["Codec"], uploads: Sequence, dampen: Sequence[float], want_f32: bool = False):

@@ -1,5 +1,7 @@
 // fleet_amd/csrc/acc_kernels.hip -- streaming aggregation: one upload folded into a
-// resident sum per launch (k_acc_push), the merged gradient from the sum (k_acc_finish).
+// resident sum per launch (k_acc_push), the merged gradient from the sum (k_acc_finish),
+// a burst of uploads per launch (k_acc_push_many), and the upload pool's fold over picked
+// resident rows (k_pool_fold).
 //
 // CppNNUpdater.update is entered once per upload and only buffers it until M have
 // arrived (CppNNUpdater.java:383-391); the chain it then runs over the picked uploads
@@ -195,6 +197,74 @@ struct AccDampen {
   double d[kAccBurst];
 };
 
+// One upload's step on a lane's group of the pool's fold (k_pool_fold), the running value A in
+// registers: k_acc_push_many's step, which is k_acc_push's, every Q q_stage_d16x.
+// `src` is the lane's 16 bytes of the row; dead lanes load nothing and run the chain on
+// code 0. `is_first` (uniform): the batch's first upload -- its header codes go to href
+// and hfirst[], the later ones are compared with href. FINISH keeps the row's own codes
+// in keepc (the last row's are the ones left after the loop). bad / layout_bad collect
+// the Base64 check's and the header comparison's failures.
+template <bool FINISH>
+__device__ __forceinline__ void acc_lane_step(const AccShared& sh, const uint8_t* src, bool live, uint32_t need,
+                                              bool wave_keep, uint32_t hbits, uint32_t kbits, int h0, bool is_first,
+                                              double d, int32_t* hfirst, int32_t (&href)[3], int32_t (&keepc)[3],
+                                              float (&A)[3], uint32_t& bad, uint32_t& layout_bad) {
+  uint4 w = uint4{0u, 0u, 0u, 0u};
+  if (live) w = *reinterpret_cast<const uint4*>(src);
+  int32_t codes[3];
+  if (need == 0xffffu) bad |= live ? b64_decode_group_full(w, &sh.tab, codes) : 0u;
+  else bad |= live ? (b64_decode_group(w, &sh.tab, codes) & need) : 0u;
+  if (!live) codes[0] = codes[1] = codes[2] = 0;
+  if (wave_keep) {
+    int hi = h0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      if ((hbits >> i) & 1u) {
+        if (is_first) {
+          href[i] = codes[i];
+          if (live) hfirst[hi] = codes[i];
+        } else if (live) {
+          layout_bad |= (uint32_t)(codes[i] != href[i]);
+        }
+        ++hi;
+      }
+      if (FINISH) keepc[i] = codes[i];
+      if ((kbits >> i) & 1u) codes[i] = 0;
+    }
+  }
+  float y0[3], y[3], p[3];
+  dec_stage_d16<3>(y0, codes, &sh.dtab);
+  q_stage_d16x<3>(y, y0, &sh.dtab, sh.tab.var);
+  dampen_stage<3>(y, d);
+  q_stage_d16x<3>(p, y, &sh.dtab, sh.tab.var);
+  if (is_first) {
+    A[0] = p[0], A[1] = p[1], A[2] = p[2];
+  } else {
+    const float sm[3] = {A[0] + p[0], A[1] + p[1], A[2] + p[2]};
+    q_stage_d16x<3>(A, sm, &sh.dtab, sh.tab.var);
+  }
+}
+
+// k_acc_finish's epilogue on a lane's registers: merged_code with `inv`, header and
+// unwalked slots the codes in keepc, stored to merged / merged_f32 (whole-upload addressing)
+__device__ __forceinline__ void acc_lane_finish(const AccShared& sh, const float (&A)[3], const int32_t (&keepc)[3],
+                                                uint32_t kbits, double inv, int64_t n_up, int64_t g, uint8_t* merged,
+                                                float* merged_f32) {
+  const int r = (int)min<int64_t>(3, n_up - 3 * g);
+  int32_t out[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) out[i] = i < r ? merged_code(A[i], inv, keepc[i], (kbits >> i) & 1u, &sh.tab) : 0;
+  *reinterpret_cast<uint4*>(merged + 16 * g) = pad_group(b64_encode_group(out, &sh.tab), r);
+  if (merged_f32) {
+    float* mf = merged_f32 + 3 * g;
+    if (r == 3) {
+      *reinterpret_cast<f3u*>(mf) = f3u{dec_mt(out[0], sh.tab.mt), dec_mt(out[1], sh.tab.mt), dec_mt(out[2], sh.tab.mt)};
+    } else {
+      for (int e = 0; e < r; ++e) mf[e] = dec_mt(out[e], sh.tab.mt);
+    }
+  }
+}
+
 template <bool FINISH>
 __global__ void __launch_bounds__(kAccNT) k_acc_push_many(const uint8_t* rows, size_t pitch, const uint8_t* last_row,
                                                           const float* st_in, float* st_out, int first, int K,
@@ -290,6 +360,83 @@ __global__ void __launch_bounds__(kAccNT) k_acc_push_many(const uint8_t* rows, s
   if (layout_bad) atomicOr(err, FLEET_ERRBIT_LAYOUT);
 }
 
+// The upload pool's fold: the steps of K <= kAccBurst picked rows of a pool of resident
+// uploads in one launch (the reference's `acc` with staleSize > 0, CppNNUpdater.java:
+// 394-407: the server picks, at update time, which buffered uploads to aggregate). Pick
+// k's row is pool + slot[k] * pitch, in window coordinates; the slots travel by value
+// beside the factors, the pick index is wave-uniform, so the row address and
+// dampen_stage's test stay scalar. The step is k_acc_push_many's (acc_lane_step): no
+// chain_general, no re-read of an earlier row. A longer pick list runs as consecutive
+// launches over the one state buffer `st`: every launch but the first (`first`) reads the
+// lane's 12 bytes, every launch but the last (FINISH) writes them; K <= kAccBurst picks
+// move no state. The first launch keeps pick 0's header codes in registers and records
+// them in hfirst[], the later launches load hfirst[]. FINISH: the epilogue of
+// k_acc_push_many<true> with inv = 1 / picks of the whole update, header and unwalked
+// slots the last pick's own codes; merged_f32 may be `st` shifted back by the window's
+// start (a lane reads its 12 bytes before it writes them).
+// Errors are attributed per pick: a lane remembers in two 64-bit masks which picks failed
+// the Base64 check or differed from the first pick's header codes and after all its
+// groups ORs FLEET_ERRBIT_* into status[slot[k]]; clean data pays no atomics.
+struct PoolPicks {
+  int32_t slot[kAccBurst];
+};
+
+template <bool FINISH>
+__global__ void __launch_bounds__(kAccNT) k_pool_fold(const uint8_t* pool, size_t pitch, PoolPicks picks, float* st,
+                                                      int first, int K, AccDampen dampen, double inv, int64_t n_up,
+                                                      int64_t g_begin, int64_t g_end,
+                                                      const int32_t* __restrict__ hdr_block, int32_t* hfirst,
+                                                      int* __restrict__ status, uint8_t* merged, float* merged_f32) {
+  __shared__ AccShared sh;
+  const int n_hdr = hdr_block[1];
+  const int64_t walk_end = hdr_block[2];
+  const int32_t* hdr = hdr_block + 4;
+  acc_init(sh, hdr, n_hdr);
+  const int64_t ng = g_end - g_begin;
+  uint64_t bad_picks = 0, layout_picks = 0;
+  for (int64_t base = (int64_t)blockIdx.x * kAccNT; base < ng; base += (int64_t)gridDim.x * kAccNT) {
+    const int64_t gl = base + threadIdx.x;
+    const bool live = gl < ng;
+    const int64_t gs = live ? gl : 0, g = g_begin + gs;  // dead lanes run the chain on zero bytes and store nothing
+    float A[3] = {0.f, 0.f, 0.f};
+    if (!first && live) {
+      const f3u a = *reinterpret_cast<const f3u*>(st + 3 * gs);
+      A[0] = a.x, A[1] = a.y, A[2] = a.z;
+    }
+    const uint32_t need = needed_chars_mask((int)min<int64_t>(3, max<int64_t>(0, n_up - 3 * g)));
+    int h0;
+    const uint32_t hbits = acc_header_bits(sh, hdr, n_hdr, 3 * g, &h0);
+    const uint32_t kbits = keep_bits<3>(hbits, true, 3 * g, walk_end);
+    const bool wave_keep = __ballot(kbits != 0) != 0;  // wave-uniform: few waves hold a header
+    int32_t href[3] = {0, 0, 0}, keepc[3] = {0, 0, 0};
+    if (wave_keep && !first) {
+      int hi = h0;
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        if ((hbits >> i) & 1u) href[i] = hfirst[hi++];
+    }
+    for (int k = 0; k < K; ++k) {
+      const uint8_t* src = pool + (size_t)picks.slot[k] * pitch + 16 * gs;
+      uint32_t bad = 0, layout_bad = 0;
+      acc_lane_step<FINISH>(sh, src, live, need, wave_keep, hbits, kbits, h0, first && k == 0, dampen.d[k], hfirst, href,
+                            keepc, A, bad, layout_bad);
+      bad_picks |= (uint64_t)(bad != 0) << k;
+      layout_picks |= (uint64_t)(layout_bad != 0) << k;
+    }
+    if (!FINISH) {
+      if (live) *reinterpret_cast<f3u*>(st + 3 * gs) = f3u{A[0], A[1], A[2]};
+    } else if (live) {
+      acc_lane_finish(sh, A, keepc, kbits, inv, n_up, g, merged, merged_f32);
+    }
+  }
+  if (bad_picks | layout_picks) {
+    for (int k = 0; k < K; ++k) {
+      const int e = (((bad_picks >> k) & 1) ? FLEET_ERRBIT_BASE64 : 0) | (((layout_picks >> k) & 1) ? FLEET_ERRBIT_LAYOUT : 0);
+      if (e) atomicOr(status + picks.slot[k], e);
+    }
+  }
+}
+
 // Element-wise kernels: a grid of whole blocks per CU (8 x 256 lanes fill a CU's wave
 // slots), striding over the groups, so the tables are copied into LDS once per block.
 static unsigned acc_grid(int64_t groups) {
@@ -345,6 +492,28 @@ hipError_t launch_acc_push_many(const uint8_t* rows, size_t pitch, const uint8_t
   else
     hipLaunchKernelGGL(k_acc_push_many<false>, grid, block, 0, s, rows, pitch, last_row, st_in, st_out, first, K, d, inv,
                        n_up, g_begin, g_end, d_hdr_block, d_hfirst, d_err, merged, merged_f32);
+  return hipGetLastError();
+}
+
+hipError_t launch_pool_fold(const uint8_t* pool, size_t pitch, const int32_t* slots, float* st, int first, int K,
+                            const double* dampen, bool finish, double inv, int64_t n_up, int64_t g_begin, int64_t g_end,
+                            const int32_t* d_hdr_block, int32_t* d_hfirst, int* d_status, uint8_t* merged,
+                            float* merged_f32, hipStream_t s) {
+  if (K <= 0 || K > kAccBurst) return hipErrorInvalidValue;
+  if (g_end <= g_begin) return hipSuccess;
+  AccDampen d;
+  PoolPicks p;
+  for (int k = 0; k < kAccBurst; ++k) {
+    d.d[k] = k < K ? dampen[k] : 1.0;
+    p.slot[k] = k < K ? slots[k] : 0;
+  }
+  const dim3 grid(acc_grid(g_end - g_begin)), block(kAccNT);
+  if (finish)
+    hipLaunchKernelGGL(k_pool_fold<true>, grid, block, 0, s, pool, pitch, p, st, first, K, d, inv, n_up, g_begin, g_end,
+                       d_hdr_block, d_hfirst, d_status, merged, merged_f32);
+  else
+    hipLaunchKernelGGL(k_pool_fold<false>, grid, block, 0, s, pool, pitch, p, st, first, K, d, inv, n_up, g_begin, g_end,
+                       d_hdr_block, d_hfirst, d_status, merged, merged_f32);
   return hipGetLastError();
 }
 

@@ -2256,6 +2256,274 @@ int fleet_acc_reset(fleet_acc* a) {
   return FLEET_OK;
 }
 
+// ---------------------------------------------------------------- upload pool
+
+// The reference's `acc` for staleSize > 0 (CppNNUpdater.java:394-407) kept in HBM: uploads
+// go into slots when they arrive, an update folds any subset of the slots in any order
+// (k_pool_fold) and leaves every slot as it was. d_rows holds slots + 1 rows of the
+// window's bytes: row `slots` receives the host update's merged bytes, whose fp32 go over
+// the state (the finish launch reads a lane's 12 bytes before it writes them).
+struct fleet_pool {
+  fleet_ctx* c = nullptr;
+  size_t len = 0, n = 0, gb = 0, ge = 0, ng = 0, col0 = 0, width = 0, pitch = 0;
+  int n_hdr = 0, slots = 0;
+  uint8_t* d_rows = nullptr;
+  float* d_state = nullptr;     // the running value between the launches of an update of more than kAccBurst picks
+  int32_t* d_hdr = nullptr;     // {0, count, walk_end, 0, positions}
+  int32_t* d_hfirst = nullptr;  // the update's first pick's header codes
+  int* d_status = nullptr;      // one error word per slot, cleared by every update
+  int* h_status = nullptr;      // pinned: what the last update left in d_status
+  uint8_t* h_row = nullptr;     // pinned: a host put's way in
+  std::vector<uint8_t> occupied;
+  std::vector<uint8_t> seen;    // update: the picks so far
+  bool pending = false;         // device puts in flight on pending_stream
+  hipStream_t pending_stream = nullptr;
+};
+
+namespace {
+
+static void release_pool(fleet_pool* p) {
+  for (void* d : {(void*)p->d_rows, (void*)p->d_state, (void*)p->d_hdr, (void*)p->d_hfirst, (void*)p->d_status})
+    if (d) (void)hipFree(d);
+  for (void* h : {(void*)p->h_status, (void*)p->h_row})
+    if (h) (void)hipHostFree(h);
+  delete p;
+}
+
+// waits for the device puts in flight unless they run on `same`, which orders the caller's next work itself
+static int pool_settle(fleet_pool* p, hipStream_t same, bool wait) {
+  if (p->pending && (wait || p->pending_stream != same)) {
+    HIP_TRY(p->c, hipStreamSynchronize(p->pending_stream));
+    p->pending = false;
+  }
+  return FLEET_OK;
+}
+
+static int pool_slot_arg(fleet_pool* p, int slot, const char* what) {
+  if (slot < 0 || slot >= p->slots) return fail(p->c, FLEET_ERR_ARG, "%s: slot %d outside [0, %d)", what, slot, p->slots);
+  return FLEET_OK;
+}
+
+// FLEET_ERR_ARG before anything is launched: a pick outside the pool, of an empty slot, or repeated
+static int pool_update_args(fleet_pool* p, const int32_t* picks, int K, const char* what) {
+  std::fill(p->seen.begin(), p->seen.end(), 0);
+  for (int k = 0; k < K; ++k) {
+    const int rc = pool_slot_arg(p, picks[k], what);
+    if (rc) return rc;
+    if (!p->occupied[picks[k]]) return fail(p->c, FLEET_ERR_ARG, "%s: pick %d names slot %d, which holds no upload", what, k, picks[k]);
+    if (p->seen[picks[k]]) return fail(p->c, FLEET_ERR_ARG, "%s: slot %d is picked twice", what, picks[k]);
+    p->seen[picks[k]] = 1;
+  }
+  return FLEET_OK;
+}
+
+// Enqueues an update on `s`: status[] cleared, the picks folded kAccBurst per launch (the
+// last launch the finish form), status[] copied back. Nothing in the pool but the state,
+// hfirst[] and status[] is written.
+static int pool_fold(fleet_pool* p, const int32_t* picks, int K, const double* dampen, hipStream_t s, uint8_t* d_merged,
+                     float* d_f32) {
+  fleet_ctx* c = p->c;
+  constexpr int B = fleet::kAccBurst;
+  HIP_TRY(c, hipMemsetAsync(p->d_status, 0, sizeof(int) * (size_t)p->slots, s));
+  for (int k0 = 0; k0 < K; k0 += B) {
+    const int kc = std::min(B, K - k0);
+    HIP_TRY(c, fleet::launch_pool_fold(p->d_rows, p->pitch, picks + k0, p->d_state, k0 == 0, kc, dampen + k0, k0 + kc == K,
+                                       (double)1 / K, (int64_t)p->n, (int64_t)p->gb, (int64_t)p->ge, p->d_hdr,
+                                       p->d_hfirst, p->d_status, d_merged, d_f32, s));
+  }
+  HIP_TRY(c, hipMemcpyAsync(p->h_status, p->d_status, sizeof(int) * (size_t)p->slots, hipMemcpyDeviceToHost, s));
+  return FLEET_OK;
+}
+
+// after the stream was synchronised: BASE64 before LAYOUT, as acc_code
+static int pool_verdict(fleet_pool* p, const int32_t* picks, int K) {
+  int all = 0, bad_slot = -1, layout_slot = -1;
+  for (int k = K - 1; k >= 0; --k) {
+    const int e = p->h_status[picks[k]];
+    all |= e;
+    if (e & FLEET_ERRBIT_BASE64) bad_slot = picks[k];
+    if (e & FLEET_ERRBIT_LAYOUT) layout_slot = picks[k];
+  }
+  if (all & FLEET_ERRBIT_BASE64)
+    return fail(p->c, FLEET_ERR_BASE64, "slot %d: input is not Base64::encode output (alphabet/padding)", bad_slot);
+  if (all & FLEET_ERRBIT_LAYOUT)
+    return fail(p->c, FLEET_ERR_LAYOUT, "slot %d: upload's layout header slots differ from the update's first pick", layout_slot);
+  return FLEET_OK;
+}
+
+}  // namespace
+
+int fleet_pool_create(fleet_ctx* c, size_t len, const int32_t* header_pos, int n_headers, size_t group_begin,
+                      size_t group_end, int slots, fleet_pool** out) {
+  if (!c || !out) return FLEET_ERR_ARG;
+  *out = nullptr;
+  if (len == 0 || n_headers < 0 || n_headers > FLEET_MAX_HEADERS || (n_headers && !header_pos) || slots < 1)
+    return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  int rc = check_text_len(c, len);
+  if (rc) return rc;
+  const size_t n = fleet_b64_count(len), groups = groups_of(n);
+  if (16 * groups + 16 >= ((size_t)1 << 31)) return fail(c, FLEET_ERR_ARG, "upload of %zu bytes: 2 GiB or more", len);
+  if (group_end > groups) group_end = groups;
+  if (group_begin > group_end) return fail(c, FLEET_ERR_ARG, "group window [%zu, %zu) is empty or reversed", group_begin, group_end);
+  if ((rc = check_header_positions(c, header_pos, n_headers, n))) return rc;
+  fleet_pool* p = new fleet_pool();
+  p->c = c;
+  p->len = len;
+  p->n = n;
+  p->gb = group_begin;
+  p->ge = group_end;
+  p->ng = group_end - group_begin;
+  p->col0 = 16 * p->gb;
+  p->width = p->ng ? std::min(len, 16 * p->ge) - p->col0 : 0;
+  p->pitch = 16 * p->ng + 64;
+  p->n_hdr = n_headers;
+  p->slots = slots;
+  p->occupied.assign((size_t)slots, 0);
+  p->seen.assign((size_t)slots, 0);
+  const size_t rows_bytes = ((size_t)slots + 1) * p->pitch, st_bytes = sizeof(float) * 3 * p->ng + 64;
+  const size_t hdr_bytes = sizeof(int32_t) * ((size_t)n_headers + 4), status_bytes = sizeof(int) * (size_t)slots;
+  // the rows are zeroed once: bytes past `len` in a row's last group stay zero, the puts' copies stop at len
+  bool ok = hipMalloc((void**)&p->d_rows, rows_bytes) == hipSuccess && hipMemset(p->d_rows, 0, rows_bytes) == hipSuccess &&
+            hipMalloc((void**)&p->d_state, st_bytes) == hipSuccess && hipMemset(p->d_state, 0, st_bytes) == hipSuccess &&
+            hipMalloc((void**)&p->d_hdr, hdr_bytes) == hipSuccess &&
+            hipMalloc((void**)&p->d_hfirst, sizeof(int32_t) * ((size_t)n_headers + 16)) == hipSuccess &&
+            hipMalloc((void**)&p->d_status, status_bytes) == hipSuccess &&
+            hipMemset(p->d_status, 0, status_bytes) == hipSuccess &&
+            hipHostMalloc((void**)&p->h_status, status_bytes, hipHostMallocDefault) == hipSuccess &&
+            hipHostMalloc((void**)&p->h_row, p->pitch, hipHostMallocDefault) == hipSuccess;
+  if (ok) {
+    std::memset(p->h_status, 0, status_bytes);
+    std::vector<int32_t> hw((size_t)n_headers + 4);
+    hw[0] = 0;
+    hw[1] = n_headers;
+    hw[2] = (int32_t)n;  // the caller's layout covers the whole upload (as fleet_acc_create)
+    hw[3] = 0;
+    if (n_headers) std::memcpy(hw.data() + 4, header_pos, sizeof(int32_t) * (size_t)n_headers);
+    ok = hipMemcpy(p->d_hdr, hw.data(), hdr_bytes, hipMemcpyHostToDevice) == hipSuccess;
+  }
+  if (!ok) {
+    (void)hipGetLastError();
+    release_pool(p);
+    return fail(c, FLEET_ERR_NOMEM, "fleet_pool_create: allocating %d slots of %zu groups failed", slots, group_end - group_begin);
+  }
+  *out = p;
+  return FLEET_OK;
+}
+
+void fleet_pool_destroy(fleet_pool* p) {
+  if (!p) return;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard dg(c->device);
+  if (p->pending) (void)hipStreamSynchronize(p->pending_stream);
+  (void)hipStreamSynchronize(c->stream);
+  release_pool(p);
+}
+
+int fleet_pool_slots(const fleet_pool* p) { return p ? p->slots : FLEET_ERR_ARG; }
+
+int fleet_pool_occupied(const fleet_pool* p, int slot) {
+  if (!p || slot < 0 || slot >= p->slots) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(p->c->mu);
+  return p->occupied[slot] ? 1 : 0;
+}
+
+int fleet_pool_slot_status(const fleet_pool* p, int slot) {
+  if (!p || slot < 0 || slot >= p->slots) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(p->c->mu);
+  return p->h_status[slot];
+}
+
+int fleet_pool_put(fleet_pool* p, int slot, const char* upload, size_t len) {
+  if (!p || !upload) return FLEET_ERR_ARG;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  int rc = pool_slot_arg(p, slot, "fleet_pool_put");
+  if (rc) return rc;
+  if (len != p->len) return fail(c, FLEET_ERR_ARG, "upload has length %zu, the pool's is %zu", len, p->len);
+  if ((rc = pool_settle(p, c->stream, true))) return rc;
+  uint8_t* d = p->d_rows + (size_t)slot * p->pitch;
+  for (size_t o = 0; o < p->width; o += kAccPiece) {  // copy and DMA overlap in pieces, as fleet_acc_push
+    const size_t m = std::min(kAccPiece, p->width - o);
+    std::memcpy(p->h_row + o, upload + p->col0 + o, m);
+    HIP_TRY(c, hipMemcpyAsync(d + o, p->h_row + o, m, hipMemcpyHostToDevice, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  p->occupied[slot] = 1;
+  return FLEET_OK;
+}
+
+int fleet_pool_put_device(fleet_pool* p, int slot, const void* d_upload, void* stream) {
+  if (!p || !d_upload) return FLEET_ERR_ARG;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  int rc = pool_slot_arg(p, slot, "fleet_pool_put_device");
+  if (rc) return rc;
+  hipStream_t s = pick(c, stream);
+  if ((rc = pool_settle(p, s, false))) return rc;
+  if (p->width)
+    HIP_TRY(c, hipMemcpyAsync(p->d_rows + (size_t)slot * p->pitch, (const uint8_t*)d_upload + p->col0, p->width,
+                              hipMemcpyDeviceToDevice, s));
+  p->occupied[slot] = 1;
+  p->pending = true;
+  p->pending_stream = s;
+  return FLEET_OK;
+}
+
+int fleet_pool_drop(fleet_pool* p, int slot) {
+  if (!p) return FLEET_ERR_ARG;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  const int rc = pool_slot_arg(p, slot, "fleet_pool_drop");
+  if (rc) return rc;
+  p->occupied[slot] = 0;  // the bytes stay until the next put: every upload has the pool's length
+  return FLEET_OK;
+}
+
+int fleet_pool_update(fleet_pool* p, const int32_t* picks, int K, const double* dampen, char* merged, size_t cap,
+                      size_t* out_len, float* merged_f32) {
+  if (!p || !picks || !dampen || !merged || K <= 0) return FLEET_ERR_ARG;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  int rc = pool_update_args(p, picks, K, "fleet_pool_update");
+  if (rc) return rc;
+  if (out_len) *out_len = p->len;
+  if (cap < p->len) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu", cap, p->len);
+  if ((rc = pool_settle(p, c->stream, true))) return rc;
+  // outputs in the pool's spare row and over the state (window coordinates: shifted back by
+  // the window's start, as the kernel addresses them by the whole upload's group index)
+  uint8_t* d_out = p->d_rows + (size_t)p->slots * p->pitch;
+  if ((rc = pool_fold(p, picks, K, dampen, c->stream, d_out - p->col0, merged_f32 ? p->d_state - 3 * p->gb : nullptr)))
+    return rc;
+  const size_t v0 = 3 * p->gb, v1 = std::max(v0, std::min(p->n, 3 * p->ge));
+  if (p->width) HIP_TRY(c, hipMemcpyAsync(merged + p->col0, d_out, p->width, hipMemcpyDeviceToHost, c->stream));
+  if (merged_f32 && v1 > v0)
+    HIP_TRY(c, hipMemcpyAsync(merged_f32 + v0, p->d_state, sizeof(float) * (v1 - v0), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return pool_verdict(p, picks, K);  // on an error the outputs are not meaningful; the pool is as before
+}
+
+int fleet_pool_update_device(fleet_pool* p, const int32_t* picks, int K, const double* dampen, void* d_merged,
+                             void* d_merged_f32, void* stream) {
+  if (!p || !picks || !dampen || !d_merged || K <= 0) return FLEET_ERR_ARG;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  int rc = pool_update_args(p, picks, K, "fleet_pool_update_device");
+  if (rc) return rc;
+  hipStream_t s = pick(c, stream);
+  if ((rc = pool_settle(p, s, false))) return rc;
+  if ((rc = pool_fold(p, picks, K, dampen, s, (uint8_t*)d_merged, (float*)d_merged_f32))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(s));
+  p->pending = false;
+  return pool_verdict(p, picks, K);
+}
+
 const char* fleet_update_kernel(size_t len) {
   static thread_local std::string name;
   name = fleet::update_kernel_name((int64_t)groups_of(fleet_b64_count(len)));

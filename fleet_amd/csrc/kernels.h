@@ -111,6 +111,17 @@ hipError_t launch_acc_push_many(const uint8_t* rows, size_t pitch, const uint8_t
                                 float* st_out, int first, int K, const double* dampen, bool finish, double inv,
                                 int64_t n_up, int64_t g_begin, int64_t g_end, const int32_t* d_hdr_block,
                                 int32_t* d_hfirst, int* d_err, uint8_t* merged, float* merged_f32, hipStream_t s);
+// The upload pool's fold (k_pool_fold): K <= kAccBurst picked rows of a pool of resident
+// uploads, pick k at pool + slots[k] * pitch (window coordinates, pitch a multiple of 16);
+// slots and dampen are host arrays of K entries (they travel in the kernel arguments).
+// `first`: pick 0 is the update's first (st unread, hfirst[] written); without `finish`
+// the launch stores the running value in st, with it the launch ends in the finish
+// epilogue (inv = 1 / picks of the whole update; merged / merged_f32 in whole-upload
+// addressing) and stores no state. d_status: one error word per slot of the pool.
+hipError_t launch_pool_fold(const uint8_t* pool, size_t pitch, const int32_t* slots, float* st, int first, int K,
+                            const double* dampen, bool finish, double inv, int64_t n_up, int64_t g_begin, int64_t g_end,
+                            const int32_t* d_hdr_block, int32_t* d_hfirst, int* d_status, uint8_t* merged,
+                            float* merged_f32, hipStream_t s);
 hipError_t launch_encode_minibatch(const float* images, int64_t n_images, int F, const int32_t* labels,
                                    const int32_t* idx, int B, const float* teacher, int NL, const float header[7],
                                    uint8_t* out, int* err, hipStream_t s);

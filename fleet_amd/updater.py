@@ -13,10 +13,14 @@ upload is instead folded into a resident sum when it arrives (``Codec.accumulato
 and the M-th call is left with its own push, the finish and the model step.
 
 Scope: the ``staleSize == 0`` branch (``aggregated = acc``, :408-411) with the
-pruning thresholds at 0 (their defaults in the quick start). Staleness
-simulation (StalenessSimulator), percentile pruning and Kardam's bookkeeping are
-the reference's host-side experiment controls and are not rebuilt (SURVEY.md §2
-rows 11-13); their O(N) natives (getNorm, subtract) are on :class:`Codec`.
+pruning thresholds at 0 (their defaults in the quick start), and the
+``staleSize > 0`` branch (:394-407) with the caller's ``picker`` in the place of
+StalenessSimulator.stalenessSim: the buffered uploads then live in an upload pool
+in HBM (``Codec.pool``), the picker names which of them an update aggregates and
+in which order, and the rest stay buffered. Staleness simulation itself
+(StalenessSimulator), percentile pruning and Kardam's bookkeeping are the
+reference's host-side experiment controls and are not rebuilt (SURVEY.md §2 rows
+11-13); their O(N) natives (getNorm, subtract) are on :class:`Codec`.
 """
 from __future__ import annotations
 
@@ -134,6 +138,7 @@ class Pending:
     epoch: int
     client_id: int
     dampen: Optional[float] = None  # streaming: the pick's factor, computed when it arrived
+    slot: Optional[int] = None      # picker: the upload's slot in the pool
 
 
 class FleetUpdater:
@@ -146,9 +151,12 @@ class FleetUpdater:
 
     def __init__(self, codec, layout, M: int, lrates: Sequence[float], weights, fc_bias, policy: int = 0,
                  alpha: float = 0.0, stale_size: int = 0, num_labels: int = 10, has_outlier: bool = False,
-                 streaming: bool = False):
-        if stale_size != 0:
-            raise NotImplementedError("staleness simulation (StalenessSimulator) is not rebuilt: staleSize must be 0")
+                 streaming: bool = False, picker=None, pool_slots: Optional[int] = None):
+        if stale_size != 0 and picker is None:
+            raise NotImplementedError("staleness simulation (StalenessSimulator) is not rebuilt: staleSize != 0 needs a "
+                                      "picker")
+        if picker is not None and streaming:
+            raise ValueError("a picker chooses among buffered uploads; streaming folds them on arrival")
         self.codec = codec
         self.layout = layout
         self.M = M
@@ -172,6 +180,16 @@ class FleetUpdater:
         # the loop below computes for that pick.
         self.streaming = bool(streaming)
         self._stream_acc = None
+        # picker: the staleSize > 0 branch (:394-407). ``picker(pending, curr_epoch)`` stands
+        # where staleSim.stalenessSim stands: called at every arrival once M uploads are
+        # buffered, it returns ``(picks, discard)`` -- ``picks`` None when no update is
+        # possible yet (:405-406), else M distinct indices into ``pending`` in pick order;
+        # ``discard`` the indices of buffered uploads to drop unpicked (the simulator's
+        # too-old gradients, which it removes whether or not it picks). The uploads wait in
+        # a pool of ``pool_slots`` slots in HBM and the update folds the picked slots there.
+        self.picker = picker
+        self.pool_slots = 4 * M if pool_slots is None else int(pool_slots)
+        self._pool = None
 
     def _dampen_of(self, p: "Pending") -> float:
         """getDampen for one pick (:463-464) from the current epoch and label vector."""
@@ -194,12 +212,67 @@ class FleetUpdater:
         gradient when this upload completed a batch of M (and the model stepped),
         else None."""
         p = Pending(bytes(upload), list(labels), int(epoch), int(client_id))
+        if self.picker is not None:
+            return self._update_pooled(p)
         if self.streaming:
             self._push(p)
         self.acc.append(p)
         if len(self.acc) < self.M:  # M-softsync (:388-391)
             return None
         return self._finish_batch()
+
+    def _update_pooled(self, p: "Pending") -> Optional[bytes]:
+        """One arrival with a picker (:383-411, then :420-516 over the picked uploads)."""
+        pool = self._pool
+        if pool is None:
+            pool = self._pool = self.codec.pool(len(p.upload), self.layout.header_positions(), self.pool_slots)
+        slot = pool.free_slot()
+        if slot is None:  # before anything changes
+            raise RuntimeError(f"the upload pool's {pool.slots} slots are all occupied")
+        pool.put(slot, p.upload)
+        p.slot, p.upload = slot, b""
+        self.acc.append(p)
+        if len(self.acc) < self.M:  # M-softsync (:388-391)
+            return None
+        picks, discard = self.picker(list(self.acc), self.curr_epoch)
+        picks = None if picks is None else [int(i) for i in picks]
+        discard = sorted({int(i) for i in discard or ()})
+        n = len(self.acc)
+        if any(i < 0 or i >= n for i in discard) or (picks is not None and (
+                len(picks) != self.M or len(set(picks)) != self.M or any(i < 0 or i >= n for i in picks)
+                or set(picks) & set(discard))):
+            raise ValueError("picker: M distinct indices into the buffered uploads, none of them discarded")
+        picked = None if picks is None else [self.acc[i] for i in picks]
+        for i in reversed(discard):
+            pool.drop(self.acc.pop(i).slot)
+        if picked is None:  # not possible to update with the buffered uploads (:405-406)
+            return None
+        dampen = [self._dampen_of(q) for q in picked]  # tau from the epoch at pick time (:427)
+        try:
+            merged, grad = pool.update([q.slot for q in picked], dampen, want_f32=True)
+        except Exception as e:
+            bad = set(getattr(e, "slots", ()))  # Base64Error / LayoutError: the slots at fault leave, the model stays
+            for q in self.acc:
+                if q.slot in bad:
+                    pool.drop(q.slot)
+            self.acc = [q for q in self.acc if q.slot not in bad]
+            raise
+        window = [0] * len(self.global_labels)
+        for q in picked:
+            for j, v in enumerate(q.labels[: len(window)]):
+                window[j] += v
+        for j, v in enumerate(window):
+            self.global_labels[j] += v
+        if self.curr_epoch < len(self.lrates):
+            self.lr = np.float32(self.lrates[self.curr_epoch])
+        self.weights, self.fc_bias = self.codec.descent(self.weights, self.fc_bias, grad, self.layout, self.lr)
+        self.curr_epoch += 1
+        for q in picked:  # the picked uploads leave `acc` (:421), everything else stays buffered
+            pool.drop(q.slot)
+        gone = {q.slot for q in picked}
+        self.acc = [q for q in self.acc if q.slot not in gone]
+        self.last_merged = merged
+        return merged
 
     def _finish_batch(self, fused=None) -> bytes:
         """The M-th call's part after the arrival (:420-421, :463-464, :490-516): picks the

@@ -174,7 +174,7 @@ int fleet_last_ingress(fleet_ctx* ctx);
  * entries; fleet_layout_from_sizes / fleet_layout_parse produce it) holds
  * strictly ascending positions inside [0, fleet_b64_count(len)): the kernels
  * search the list. fleet_update_device, fleet_update_encode_device,
- * fleet_update_kardam_device and fleet_acc_create return FLEET_ERR_ARG for any
+ * fleet_update_kardam_device, fleet_acc_create and fleet_pool_create return FLEET_ERR_ARG for any
  * other list (unsorted, duplicate, negative, past the upload) and launch
  * nothing; the context's resident parameters stay those of the last accepted
  * call. The list is checked when it differs from the resident one, so a
@@ -263,8 +263,9 @@ int fleet_check(fleet_ctx* ctx, void* stream);
  * order; pruning thresholds 0), where getDampen's inputs (getCurrEpoch, the
  * global label vector) change only inside the M-th call (:502-504, descentNative),
  * so the factor known at arrival is the one the batch loop would compute. For
- * staleSize > 0, pruning thresholds above 0 or Kardam's side outputs keep the
- * batch entry points.
+ * staleSize > 0 keep the uploads in a fleet_pool (below), which aggregates any
+ * picked subset of them; for pruning thresholds above 0 or Kardam's side outputs
+ * keep the batch entry points.
  *
  * An accumulator belongs to its context (same mutex and device; destroy it
  * before fleet_destroy; errors through fleet_last_error(ctx)) and owns its memory
@@ -363,6 +364,76 @@ int fleet_acc_push_finish_device(fleet_acc* acc, const void* d_uploads, size_t p
                                  void* d_merged, void* d_merged_f32, void* stream);
 /* B: uploads folded per launch. */
 int fleet_acc_burst(void);
+
+/* Upload pool: arrivals kept in HBM, any picked subset aggregated ---------------
+ * With staleSize > 0 the reference's `acc` persists across updates
+ * (CppNNUpdater.java:383-411): at update time StalenessSimulator.stalenessSim
+ * (StalenessSimulator.java:38-176) picks M of the buffered uploads in an order of
+ * its own, leaves the rest buffered and discards those that are too old. A fold
+ * cannot be undone, so a fleet_acc does not cover that branch, and the batch calls
+ * pay the copy of all M picked rows after the last arrival. A fleet_pool is `acc`
+ * itself kept in HBM: an upload goes into a slot when it arrives (fleet_pool_put*),
+ * an update names any subset of occupied slots in any order with one getDampen
+ * factor each (CppNNUpdater.java:420-421, 463-464) and produces fleet_update's
+ * bytes for those uploads in that order (CppNNUpdater.java:490-508); after the last
+ * arrival what is left is one row's copy and one fold over resident rows. An update
+ * never frees a slot: the caller drops what it picked (fleet_pool_drop), unpicked
+ * slots stay for later updates.
+ *
+ * A pool belongs to its context like an accumulator (same mutex and device; destroy
+ * it before fleet_destroy; errors through fleet_last_error(ctx)). `len`, the header
+ * positions, the group window and `slots` >= 1 are fixed at creation, with
+ * fleet_acc_create's checks; a window behaves as the accumulator's: only the
+ * window's bytes are stored, read and written. Resident bytes over G groups:
+ * (slots + 1) rows of 16 G + 64 bytes (the extra row takes the host update's merged
+ * bytes), one fp32 state of 12 G bytes (it carries the running value between the
+ * launches of an update of more than fleet_acc_burst() picks; fewer picks move no
+ * state), the header block, the first pick's header codes, one status word per slot
+ * in HBM and pinned, and one pinned row. A failed allocation is FLEET_ERR_NOMEM and
+ * leaves nothing behind. */
+typedef struct fleet_pool fleet_pool;
+int fleet_pool_create(fleet_ctx* ctx, size_t len, const int32_t* header_pos, int n_headers, size_t group_begin,
+                      size_t group_end, int slots, fleet_pool** out);
+void fleet_pool_destroy(fleet_pool* pool);
+int fleet_pool_slots(const fleet_pool* pool);
+/* 1 / 0; FLEET_ERR_ARG for NULL or a slot outside [0, slots). */
+int fleet_pool_occupied(const fleet_pool* pool, int slot);
+/* One arrival (CppNNUpdater.java:383-411: the upload joins `acc`): fleet_acc_push's
+ * ingress without the fold. The window's bytes go through the pinned row to the
+ * slot, in pieces whose copy to the device overlaps the next piece's host copy;
+ * synchronous. A put into an occupied slot replaces the upload. FLEET_ERR_ARG: a NULL
+ * argument, a slot outside [0, slots), a length other than `len`. The text is checked
+ * when it is picked, not here. */
+int fleet_pool_put(fleet_pool* pool, int slot, const char* upload, size_t len);
+/* The same for an upload already in HBM (d_upload: the whole row, of which only the
+ * window's bytes are read): copied device-to-device on the caller's stream, no
+ * synchronisation. Host forms issued later wait for device puts in flight. */
+int fleet_pool_put_device(fleet_pool* pool, int slot, const void* d_upload, void* stream);
+/* Frees a slot (a picked upload after its update, or one StalenessSimulator.java:38-176
+ * discards as too old). */
+int fleet_pool_drop(fleet_pool* pool, int slot);
+/* Aggregates the uploads in slots picks[0..K) in that order with dampen[k]
+ * (CppNNUpdater.java:420-421, 463-464, 490-508): fleet_update's `merged` for those
+ * uploads in that order and optionally decodeFloat(merged) in merged_f32, header and
+ * unwalked slots from the last pick. fleet_acc_burst() picks per launch, the slots and
+ * factors in the kernel arguments. The host form writes this pool's window of `merged`
+ * (len chars) and of merged_f32; the device form uses fleet_acc_finish_device's
+ * addressing on `stream`. FLEET_ERR_ARG, before anything is launched and with the slot
+ * status untouched: K <= 0, a NULL array, a pick outside [0, slots), a pick of an
+ * unoccupied slot, a slot picked twice. A `cap` below len is FLEET_ERR_CAPACITY with
+ * *out_len = len. Both forms clear the slot status, fold, and synchronise once to read
+ * it. On FLEET_ERR_BASE64 (a picked upload is not Base64::encode output) or
+ * FLEET_ERR_LAYOUT (a picked upload's header slots differ from the first pick's) the
+ * outputs are not meaningful, the pool is exactly as before -- no slot changes, nothing
+ * is dropped -- and fleet_pool_slot_status names the offending slots; BASE64 comes
+ * before LAYOUT. An upload in an unpicked slot is not looked at. */
+int fleet_pool_update(fleet_pool* pool, const int32_t* picks, int K, const double* dampen, char* merged, size_t cap,
+                      size_t* out_len, float* merged_f32);
+int fleet_pool_update_device(fleet_pool* pool, const int32_t* picks, int K, const double* dampen, void* d_merged,
+                             void* d_merged_f32, void* stream);
+/* The error bits the last update saw in the slot's upload: 1 = Base64, 2 = layout
+ * header; 0 for a clean or unpicked slot. FLEET_ERR_ARG for NULL or a bad slot. */
+int fleet_pool_slot_status(const fleet_pool* pool, int slot);
 
 /* Self-test of the device codec arithmetic over whole input domains: an
  * order-independent 64-bit digest sum_i splitmix64(i<<32 | f(i)) of
