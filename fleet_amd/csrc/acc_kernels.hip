@@ -6,7 +6,7 @@
 // CppNNUpdater.update is entered once per upload and only buffers it until M have
 // arrived (CppNNUpdater.java:383-391); the chain it then runs over the picked uploads
 // (:420-421, :463-464, :490-508) is serial over clients and independent per element,
-// so one client's step can run when its upload arrives (DESIGN.md §4.6):
+// so one client's step can run when its upload arrives (DESIGN.md §4.3):
 //   y = Q(dec(code))   p = Q((float)((double)y * d))   A = first ? p : Q(A + p)
 // The state A is one fp32 per upload position of the accumulator's group window, read
 // from one buffer and written to the other, so a rejected upload leaves no trace.
@@ -15,6 +15,13 @@
 // leaves the table stages' domain (chain_general); a fold step no longer has the
 // earlier uploads, so here every stage falls back to the general codec within the step
 // (q_stage_d16x: wave-uniform behind a ballot, never taken by gradient-like data).
+//
+// One copy of each piece: the block prologue (acc_block_open), the per-group prologue
+// (acc_group_open), the per-upload step (acc_lane_step) and the finish epilogue
+// (acc_lane_finish); the kernels are loops around them, k_acc_push the step at K = 1.
+// One exception: k_pool_fold spells the per-group prologue out on locals of its own.
+// Calling acc_group_open there changed the kernel's schedule and cost 1-2 % per launch
+// (profiles/stream_shared/), so that piece of sharing stops at the other two kernels.
 //
 // This unit takes the stage helpers of kernels.hip and none of its kernels.
 #define FLEET_STREAM_TU
@@ -47,13 +54,23 @@ struct AccShared {
   int32_t hdr[kAccLdsHdr];
 };
 
-// tables and the header positions into LDS; returns the list the group search reads
-__device__ __forceinline__ void acc_init(AccShared& sh, const int32_t* __restrict__ hdr, int n_hdr) {
+// hdr_block = {0, count, walk_end, 0, positions} as a block reads it
+struct AccHdr {
+  int n_hdr;
+  int64_t walk_end;
+  const int32_t* hdr;
+};
+
+// Every kernel's block prologue: hdr_block unpacked, the tables and (when they fit) the
+// header positions copied into LDS.
+__device__ __forceinline__ AccHdr acc_block_open(AccShared& sh, const int32_t* __restrict__ hdr_block) {
+  const AccHdr H{hdr_block[1], hdr_block[2], hdr_block + 4};
   b64_tables_init<kAccNT>(&sh.tab);
   d16_table_init<kAccNT>(&sh.dtab);
-  if (n_hdr <= kAccLdsHdr)
-    for (int i = threadIdx.x; i < n_hdr; i += kAccNT) sh.hdr[i] = hdr[i];
+  if (H.n_hdr <= kAccLdsHdr)
+    for (int i = threadIdx.x; i < H.n_hdr; i += kAccNT) sh.hdr[i] = H.hdr[i];
   __syncthreads();
+  return H;
 }
 
 // bit e = slot p0 + e is a header slot; *first = the index of the group's first header
@@ -69,141 +86,57 @@ __device__ __forceinline__ uint32_t acc_header_bits(const AccShared& sh, const i
   return n_hdr <= kAccLdsHdr ? acc_bits_in(sh.hdr, n_hdr, p0, first) : acc_bits_in(hdr, n_hdr, p0, first);
 }
 
-}  // namespace
-
-// One upload's step over the groups [g_begin, g_end); `row`, `st_in` and `st_out` hold
-// the window alone (group g at byte 16 (g - g_begin), value 3 (g - g_begin)). Header
-// slots and slots at or past the walk's end carry no chain (their state stays Q(0) =
-// 0); header codes are recorded in hfirst[] by the first push and compared by the
-// later ones (FLEET_ERRBIT_LAYOUT, as the batch kernels do against client 0). A lane
-// owns a group: one 16-byte row load, one 12-byte state load and store.
-__global__ void __launch_bounds__(kAccNT) k_acc_push(const uint8_t* __restrict__ row, const float* __restrict__ st_in,
-                                                     float* __restrict__ st_out, int first, double dampen,
-                                                     int64_t n_up, int64_t g_begin, int64_t g_end,
-                                                     const int32_t* __restrict__ hdr_block,
-                                                     int32_t* __restrict__ hfirst, int* __restrict__ err) {
-  __shared__ AccShared sh;
-  const int n_hdr = hdr_block[1];
-  const int64_t walk_end = hdr_block[2];
-  const int32_t* hdr = hdr_block + 4;
-  acc_init(sh, hdr, n_hdr);
-  const int64_t ng = g_end - g_begin;
-  uint32_t bad = 0, layout_bad = 0;
-  for (int64_t base = (int64_t)blockIdx.x * kAccNT; base < ng; base += (int64_t)gridDim.x * kAccNT) {
-    const int64_t gl = base + threadIdx.x;
-    const bool live = gl < ng;
-    const int64_t gs = live ? gl : 0, g = g_begin + gs;  // dead lanes read group 0 of the window and store nothing
-    const uint4 w = *reinterpret_cast<const uint4*>(row + 16 * gs);
-    f3u a = f3u{0.f, 0.f, 0.f};
-    if (!first) a = *reinterpret_cast<const f3u*>(st_in + 3 * gs);
-    const uint32_t need = needed_chars_mask((int)min<int64_t>(3, max<int64_t>(0, n_up - 3 * g)));
-    int32_t codes[3];
-    if (need == 0xffffu) bad |= live ? b64_decode_group_full(w, &sh.tab, codes) : 0u;
-    else bad |= live ? (b64_decode_group(w, &sh.tab, codes) & need) : 0u;
-    int h0;
-    const uint32_t hbits = acc_header_bits(sh, hdr, n_hdr, 3 * g, &h0);
-    const uint32_t kbits = keep_bits<3>(hbits, true, 3 * g, walk_end);
-    if (__ballot(kbits != 0) != 0) {  // wave-uniform: few waves hold a header
-      int hi = h0;
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        if ((hbits >> i) & 1u) {
-          if (live) {
-            if (first) hfirst[hi] = codes[i];
-            else layout_bad |= (uint32_t)(codes[i] != hfirst[hi]);
-          }
-          ++hi;
-        }
-        if ((kbits >> i) & 1u) codes[i] = 0;
-      }
-    }
-    float y0[3], y[3], p[3];
-    dec_stage_d16<3>(y0, codes, &sh.dtab);
-    q_stage_d16x<3>(y, y0, &sh.dtab, sh.tab.var);
-    dampen_stage<3>(y, dampen);
-    q_stage_d16x<3>(p, y, &sh.dtab, sh.tab.var);
-    if (!first) {  // uniform
-      const float sm[3] = {a.x + p[0], a.y + p[1], a.z + p[2]};
-      q_stage_d16x<3>(p, sm, &sh.dtab, sh.tab.var);
-    }
-    if (live) *reinterpret_cast<f3u*>(st_out + 3 * gs) = f3u{p[0], p[1], p[2]};
-  }
-  if (bad) atomicOr(err, FLEET_ERRBIT_BASE64);
-  if (layout_bad) atomicOr(err, FLEET_ERRBIT_LAYOUT);
-}
-
-// merged_code over the window: Q(f32(f64(A) * inv)) encoded, header slots and slots at
-// or past the walk's end the last accepted upload's own codes (mergeFlatGradient,
-// CppNNUpdater.java:507-508), decoded from the accumulator's copy of that row (window
-// coordinates, like `st`). `merged` and `merged_f32` are addressed by the whole
-// upload's group index: Base64 at byte 16 g, fp32 at value 3 g.
-__global__ void __launch_bounds__(kAccNT) k_acc_finish(const uint8_t* __restrict__ last_row,
-                                                       const float* __restrict__ st, double inv, int64_t n_up,
-                                                       int64_t g_begin, int64_t g_end,
-                                                       const int32_t* __restrict__ hdr_block,
-                                                       uint8_t* __restrict__ merged, float* __restrict__ merged_f32) {
-  __shared__ AccShared sh;
-  const int n_hdr = hdr_block[1];
-  const int64_t walk_end = hdr_block[2];
-  const int32_t* hdr = hdr_block + 4;
-  acc_init(sh, hdr, n_hdr);
-  const int64_t ng = g_end - g_begin;
-  for (int64_t base = (int64_t)blockIdx.x * kAccNT; base < ng; base += (int64_t)gridDim.x * kAccNT) {
-    const int64_t gl = base + threadIdx.x;
-    if (gl >= ng) break;
-    const int64_t g = g_begin + gl;
-    const uint4 w = *reinterpret_cast<const uint4*>(last_row + 16 * gl);
-    const f3u a = *reinterpret_cast<const f3u*>(st + 3 * gl);
-    const float A[3] = {a.x, a.y, a.z};
-    int32_t codes[3], out[3];
-    (void)b64_decode_group(w, &sh.tab, codes);  // checked when the row was pushed
-    int h0;
-    const uint32_t kbits = keep_bits<3>(acc_header_bits(sh, hdr, n_hdr, 3 * g, &h0), true, 3 * g, walk_end);
-    const int r = (int)min<int64_t>(3, n_up - 3 * g);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) out[i] = i < r ? merged_code(A[i], inv, codes[i], (kbits >> i) & 1u, &sh.tab) : 0;
-    *reinterpret_cast<uint4*>(merged + 16 * g) = pad_group(b64_encode_group(out, &sh.tab), r);
-    if (merged_f32) {
-      float* mf = merged_f32 + 3 * g;
-      if (r == 3) {
-        *reinterpret_cast<f3u*>(mf) = f3u{dec_mt(out[0], sh.tab.mt), dec_mt(out[1], sh.tab.mt), dec_mt(out[2], sh.tab.mt)};
-      } else {
-        for (int e = 0; e < r; ++e) mf[e] = dec_mt(out[e], sh.tab.mt);
-      }
-    }
-  }
-}
-
-// A burst: the steps of K <= kAccBurst uploads over the window in one launch, the
-// running value in registers across the K clients, so the state is read and written
-// once per lane instead of once per upload. Each step is k_acc_push's (every Q is
-// q_stage_d16x: the per-step fallback holds inside a burst, no earlier row is re-read).
-// Rows 0..K-2 are rows + k * pitch, row K-1 is `last_row` (the accumulator's spare row
-// when the burst ends there, so the finish finds "the last accepted upload"; a chunk of
-// a longer burst passes rows + (K-1) * pitch); all in window coordinates. `first`: the
-// batch's first upload is row 0 -- st_in is not read, row 0's header codes are kept in
-// registers for the comparison and recorded in hfirst[]; otherwise the rows are compared
-// with hfirst[]. The factors travel by value: the index is wave-uniform, so
-// dampen_stage's test stays scalar. st_in and st_out may be the same buffer (the later
-// chunks of a long burst): a lane reads its 12 bytes before it writes them.
-//
-// FINISH: k_acc_finish's epilogue on the registers after the last client -- merged_code
-// with inv = 1 / (count + K), header and unwalked slots row K-1's own codes -- written to
-// merged / merged_f32 (whole-upload addressing); no state is stored. `merged` may be
-// `last_row` shifted back by the window's start and merged_f32 likewise `st_in` (the
-// host form borrows the spare buffers): a lane reads its group before it writes it, and
-// dead lanes load nothing.
-struct AccDampen {
-  double d[kAccBurst];
+// A lane's group for the kernels that step: what does not change from one upload to the
+// next, and the two values the steps carry (href, A).
+struct AccGroup {
+  bool live;              // inside the window; a dead lane loads nothing, runs the chain on code 0 and stores nothing
+  int64_t gs, g;          // the group's index in the window (dead lanes: 0) and in the whole upload
+  uint32_t need;          // the Base64 characters the group's values need
+  uint32_t hbits, kbits;  // bit i: slot 3 g + i is a header slot / carries no chain (header, or at or past the walk's end)
+  int h0;                 // index of the group's first header in hfirst[]
+  bool wave_keep;         // some lane of the wave has kbits: few waves hold a header, so the header work hides behind this
+  int32_t href[3];        // the batch's first upload's codes in the group's header slots
+  float A[3];             // the running value
 };
 
-// One upload's step on a lane's group of the pool's fold (k_pool_fold), the running value A in
-// registers: k_acc_push_many's step, which is k_acc_push's, every Q q_stage_d16x.
-// `src` is the lane's 16 bytes of the row; dead lanes load nothing and run the chain on
-// code 0. `is_first` (uniform): the batch's first upload -- its header codes go to href
-// and hfirst[], the later ones are compared with href. FINISH keeps the row's own codes
-// in keepc (the last row's are the ones left after the loop). bad / layout_bad collect
-// the Base64 check's and the header comparison's failures.
+// The per-group prologue. `first`: the launch's first upload is the batch's first, so
+// the state is not read and href comes from that upload (acc_lane_step); otherwise A is
+// the lane's 12 bytes of `st` and href is loaded from hfirst[].
+__device__ __forceinline__ AccGroup acc_group_open(const AccShared& sh, const AccHdr& H, int64_t gl, int64_t ng,
+                                                   int64_t g_begin, int64_t n_up, bool first, const float* st,
+                                                   const int32_t* hfirst) {
+  AccGroup G;
+  G.live = gl < ng;
+  G.gs = G.live ? gl : 0;
+  G.g = g_begin + G.gs;
+  G.A[0] = G.A[1] = G.A[2] = 0.f;
+  if (!first && G.live) {
+    const f3u a = *reinterpret_cast<const f3u*>(st + 3 * G.gs);
+    G.A[0] = a.x, G.A[1] = a.y, G.A[2] = a.z;
+  }
+  G.need = needed_chars_mask((int)min<int64_t>(3, max<int64_t>(0, n_up - 3 * G.g)));
+  G.hbits = acc_header_bits(sh, H.hdr, H.n_hdr, 3 * G.g, &G.h0);
+  G.kbits = keep_bits<3>(G.hbits, true, 3 * G.g, H.walk_end);
+  G.wave_keep = __ballot(G.kbits != 0) != 0;
+  G.href[0] = G.href[1] = G.href[2] = 0;
+  if (G.wave_keep && !first) {
+    int hi = G.h0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+      if ((G.hbits >> i) & 1u) G.href[i] = hfirst[hi++];
+  }
+  return G;
+}
+
+// One upload's step on a lane's group: A = is_first ? p : Q(A + p) with p the upload's
+// dampened value (the file's header), every Q q_stage_d16x. `src` is the lane's 16 bytes
+// of the upload's row. Slots with a kbit carry no chain: their code is taken as 0, so
+// their state stays Q(0) = 0. `is_first` (uniform): the batch's first upload -- its header
+// codes go to href and hfirst[]; a later upload's are compared with href, as the batch
+// kernels compare with client 0. FINISH keeps the upload's own codes in keepc for the
+// epilogue. bad / layout_bad collect the Base64 check's and the header comparison's
+// failures of live lanes. The group's values come one by one (AccGroup's fields, or
+// k_pool_fold's locals).
 template <bool FINISH>
 __device__ __forceinline__ void acc_lane_step(const AccShared& sh, const uint8_t* src, bool live, uint32_t need,
                                               bool wave_keep, uint32_t hbits, uint32_t kbits, int h0, bool is_first,
@@ -245,8 +178,10 @@ __device__ __forceinline__ void acc_lane_step(const AccShared& sh, const uint8_t
   }
 }
 
-// k_acc_finish's epilogue on a lane's registers: merged_code with `inv`, header and
-// unwalked slots the codes in keepc, stored to merged / merged_f32 (whole-upload addressing)
+// The finish epilogue on a live lane's group g: merged_code = Q(f32(f64(A) * inv))
+// encoded, slots with a kbit the last accepted upload's own codes (keepc; mergeFlatGradient,
+// CppNNUpdater.java:507-508). `merged` and `merged_f32` are addressed by the whole
+// upload's group index: Base64 at byte 16 g, fp32 at value 3 g.
 __device__ __forceinline__ void acc_lane_finish(const AccShared& sh, const float (&A)[3], const int32_t (&keepc)[3],
                                                 uint32_t kbits, double inv, int64_t n_up, int64_t g, uint8_t* merged,
                                                 float* merged_f32) {
@@ -265,6 +200,79 @@ __device__ __forceinline__ void acc_lane_finish(const AccShared& sh, const float
   }
 }
 
+}  // namespace
+
+// a launch's factors and the pool's picked slots, by value in the kernel arguments
+struct AccDampen {
+  double d[kAccBurst];
+};
+struct PoolPicks {
+  int32_t slot[kAccBurst];
+};
+
+// All four kernels work on the groups [g_begin, g_end), a lane per group: rows and state
+// hold that window alone (group g at byte 16 (g - g_begin), value 3 (g - g_begin)), one
+// 16-byte row load per upload and at most one 12-byte state load and store per lane.
+
+// One upload's step: state st_in -> st_out (st_in is not read when `first`).
+__global__ void __launch_bounds__(kAccNT) k_acc_push(const uint8_t* __restrict__ row, const float* __restrict__ st_in,
+                                                     float* __restrict__ st_out, int first, double dampen,
+                                                     int64_t n_up, int64_t g_begin, int64_t g_end,
+                                                     const int32_t* __restrict__ hdr_block,
+                                                     int32_t* __restrict__ hfirst, int* __restrict__ err) {
+  __shared__ AccShared sh;
+  const AccHdr H = acc_block_open(sh, hdr_block);
+  const int64_t ng = g_end - g_begin;
+  uint32_t bad = 0, layout_bad = 0;
+  for (int64_t base = (int64_t)blockIdx.x * kAccNT; base < ng; base += (int64_t)gridDim.x * kAccNT) {
+    AccGroup G = acc_group_open(sh, H, base + threadIdx.x, ng, g_begin, n_up, first, st_in, hfirst);
+    int32_t keepc[3];
+    acc_lane_step<false>(sh, row + 16 * G.gs, G.live, G.need, G.wave_keep, G.hbits, G.kbits, G.h0, first, dampen, hfirst,
+                         G.href, keepc, G.A, bad, layout_bad);
+    if (G.live) *reinterpret_cast<f3u*>(st_out + 3 * G.gs) = f3u{G.A[0], G.A[1], G.A[2]};
+  }
+  if (bad) atomicOr(err, FLEET_ERRBIT_BASE64);
+  if (layout_bad) atomicOr(err, FLEET_ERRBIT_LAYOUT);
+}
+
+// The merged gradient from the state `st` and the accumulator's copy of the last accepted
+// upload's row (both in window coordinates).
+__global__ void __launch_bounds__(kAccNT) k_acc_finish(const uint8_t* __restrict__ last_row,
+                                                       const float* __restrict__ st, double inv, int64_t n_up,
+                                                       int64_t g_begin, int64_t g_end,
+                                                       const int32_t* __restrict__ hdr_block,
+                                                       uint8_t* __restrict__ merged, float* __restrict__ merged_f32) {
+  __shared__ AccShared sh;
+  const AccHdr H = acc_block_open(sh, hdr_block);
+  const int64_t ng = g_end - g_begin;
+  for (int64_t base = (int64_t)blockIdx.x * kAccNT; base < ng; base += (int64_t)gridDim.x * kAccNT) {
+    const int64_t gl = base + threadIdx.x;
+    if (gl >= ng) break;
+    const int64_t g = g_begin + gl;
+    const uint4 w = *reinterpret_cast<const uint4*>(last_row + 16 * gl);
+    const f3u a = *reinterpret_cast<const f3u*>(st + 3 * gl);
+    const float A[3] = {a.x, a.y, a.z};
+    int32_t codes[3];
+    (void)b64_decode_group(w, &sh.tab, codes);  // checked when the row was pushed
+    int h0;
+    const uint32_t kbits = keep_bits<3>(acc_header_bits(sh, H.hdr, H.n_hdr, 3 * g, &h0), true, 3 * g, H.walk_end);
+    acc_lane_finish(sh, A, codes, kbits, inv, n_up, g, merged, merged_f32);
+  }
+}
+
+// A burst: the steps of K <= kAccBurst uploads in one launch, the running value in
+// registers across them, so the state is read and written once per lane instead of once
+// per upload. Rows 0..K-2 are rows + k * pitch, row K-1 is `last_row` (the accumulator's
+// spare row when the burst ends there, so the finish finds "the last accepted upload"; a
+// chunk of a longer burst passes rows + (K-1) * pitch). `first`: row 0 is the batch's
+// first upload. The factors travel by value: the index is wave-uniform, so dampen_stage's
+// test stays scalar. st_in and st_out may be the same buffer (the later chunks of a long
+// burst): a lane reads its 12 bytes before it writes them.
+//
+// FINISH: the epilogue after the last upload, inv = 1 / (count + K), in place of the
+// state store. `merged` may be `last_row` shifted back by the window's start and
+// merged_f32 likewise `st_in` (the host form borrows the spare buffers): a lane reads its
+// group before it writes it.
 template <bool FINISH>
 __global__ void __launch_bounds__(kAccNT) k_acc_push_many(const uint8_t* rows, size_t pitch, const uint8_t* last_row,
                                                           const float* st_in, float* st_out, int first, int K,
@@ -273,87 +281,21 @@ __global__ void __launch_bounds__(kAccNT) k_acc_push_many(const uint8_t* rows, s
                                                           int32_t* hfirst, int* __restrict__ err, uint8_t* merged,
                                                           float* merged_f32) {
   __shared__ AccShared sh;
-  const int n_hdr = hdr_block[1];
-  const int64_t walk_end = hdr_block[2];
-  const int32_t* hdr = hdr_block + 4;
-  acc_init(sh, hdr, n_hdr);
+  const AccHdr H = acc_block_open(sh, hdr_block);
   const int64_t ng = g_end - g_begin;
   uint32_t bad = 0, layout_bad = 0;
   for (int64_t base = (int64_t)blockIdx.x * kAccNT; base < ng; base += (int64_t)gridDim.x * kAccNT) {
-    const int64_t gl = base + threadIdx.x;
-    const bool live = gl < ng;
-    const int64_t gs = live ? gl : 0, g = g_begin + gs;  // dead lanes run the chain on zero bytes and store nothing
-    float A[3] = {0.f, 0.f, 0.f};
-    if (!first && live) {
-      const f3u a = *reinterpret_cast<const f3u*>(st_in + 3 * gs);
-      A[0] = a.x, A[1] = a.y, A[2] = a.z;
-    }
-    const uint32_t need = needed_chars_mask((int)min<int64_t>(3, max<int64_t>(0, n_up - 3 * g)));
-    int h0;
-    const uint32_t hbits = acc_header_bits(sh, hdr, n_hdr, 3 * g, &h0);
-    const uint32_t kbits = keep_bits<3>(hbits, true, 3 * g, walk_end);
-    const bool wave_keep = __ballot(kbits != 0) != 0;  // wave-uniform: few waves hold a header
-    int32_t href[3] = {0, 0, 0}, keepc[3] = {0, 0, 0};
-    if (wave_keep && !first) {
-      int hi = h0;
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-        if ((hbits >> i) & 1u) href[i] = hfirst[hi++];
-    }
+    AccGroup G = acc_group_open(sh, H, base + threadIdx.x, ng, g_begin, n_up, first, st_in, hfirst);
+    int32_t keepc[3] = {0, 0, 0};  // row K-1's are the ones left after the loop
     for (int k = 0; k < K; ++k) {
-      const uint8_t* src = (k == K - 1 ? last_row : rows + (size_t)k * pitch) + 16 * gs;
-      uint4 w = uint4{0u, 0u, 0u, 0u};
-      if (live) w = *reinterpret_cast<const uint4*>(src);
-      int32_t codes[3];
-      if (need == 0xffffu) bad |= live ? b64_decode_group_full(w, &sh.tab, codes) : 0u;
-      else bad |= live ? (b64_decode_group(w, &sh.tab, codes) & need) : 0u;
-      const bool is_first = first && k == 0;  // uniform
-      if (!live) codes[0] = codes[1] = codes[2] = 0;
-      if (wave_keep) {
-        int hi = h0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          if ((hbits >> i) & 1u) {
-            if (is_first) {
-              href[i] = codes[i];
-              if (live) hfirst[hi] = codes[i];
-            } else if (live) {
-              layout_bad |= (uint32_t)(codes[i] != href[i]);
-            }
-            ++hi;
-          }
-          if (FINISH) keepc[i] = codes[i];  // row K-1's are the ones left after the loop
-          if ((kbits >> i) & 1u) codes[i] = 0;
-        }
-      }
-      float y0[3], y[3], p[3];
-      dec_stage_d16<3>(y0, codes, &sh.dtab);
-      q_stage_d16x<3>(y, y0, &sh.dtab, sh.tab.var);
-      dampen_stage<3>(y, dampen.d[k]);
-      q_stage_d16x<3>(p, y, &sh.dtab, sh.tab.var);
-      if (is_first) {
-        A[0] = p[0], A[1] = p[1], A[2] = p[2];
-      } else {
-        const float sm[3] = {A[0] + p[0], A[1] + p[1], A[2] + p[2]};
-        q_stage_d16x<3>(A, sm, &sh.dtab, sh.tab.var);
-      }
+      const uint8_t* src = (k == K - 1 ? last_row : rows + (size_t)k * pitch) + 16 * G.gs;
+      acc_lane_step<FINISH>(sh, src, G.live, G.need, G.wave_keep, G.hbits, G.kbits, G.h0, first && k == 0, dampen.d[k],
+                            hfirst, G.href, keepc, G.A, bad, layout_bad);
     }
     if (!FINISH) {
-      if (live) *reinterpret_cast<f3u*>(st_out + 3 * gs) = f3u{A[0], A[1], A[2]};
-    } else if (live) {
-      const int r = (int)min<int64_t>(3, n_up - 3 * g);
-      int32_t out[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) out[i] = i < r ? merged_code(A[i], inv, keepc[i], (kbits >> i) & 1u, &sh.tab) : 0;
-      *reinterpret_cast<uint4*>(merged + 16 * g) = pad_group(b64_encode_group(out, &sh.tab), r);
-      if (merged_f32) {
-        float* mf = merged_f32 + 3 * g;
-        if (r == 3) {
-          *reinterpret_cast<f3u*>(mf) = f3u{dec_mt(out[0], sh.tab.mt), dec_mt(out[1], sh.tab.mt), dec_mt(out[2], sh.tab.mt)};
-        } else {
-          for (int e = 0; e < r; ++e) mf[e] = dec_mt(out[e], sh.tab.mt);
-        }
-      }
+      if (G.live) *reinterpret_cast<f3u*>(st_out + 3 * G.gs) = f3u{G.A[0], G.A[1], G.A[2]};
+    } else if (G.live) {
+      acc_lane_finish(sh, G.A, keepc, G.kbits, inv, n_up, G.g, merged, merged_f32);
     }
   }
   if (bad) atomicOr(err, FLEET_ERRBIT_BASE64);
@@ -363,24 +305,15 @@ __global__ void __launch_bounds__(kAccNT) k_acc_push_many(const uint8_t* rows, s
 // The upload pool's fold: the steps of K <= kAccBurst picked rows of a pool of resident
 // uploads in one launch (the reference's `acc` with staleSize > 0, CppNNUpdater.java:
 // 394-407: the server picks, at update time, which buffered uploads to aggregate). Pick
-// k's row is pool + slot[k] * pitch, in window coordinates; the slots travel by value
-// beside the factors, the pick index is wave-uniform, so the row address and
-// dampen_stage's test stay scalar. The step is k_acc_push_many's (acc_lane_step): no
-// chain_general, no re-read of an earlier row. A longer pick list runs as consecutive
-// launches over the one state buffer `st`: every launch but the first (`first`) reads the
-// lane's 12 bytes, every launch but the last (FINISH) writes them; K <= kAccBurst picks
-// move no state. The first launch keeps pick 0's header codes in registers and records
-// them in hfirst[], the later launches load hfirst[]. FINISH: the epilogue of
-// k_acc_push_many<true> with inv = 1 / picks of the whole update, header and unwalked
-// slots the last pick's own codes; merged_f32 may be `st` shifted back by the window's
-// start (a lane reads its 12 bytes before it writes them).
+// k's row is pool + slot[k] * pitch; the slots travel by value beside the factors, so the
+// row address stays scalar too. A longer pick list runs as consecutive launches over the
+// one state buffer `st`: every launch but the first (`first`) reads the lane's 12 bytes,
+// every launch but the last (FINISH) writes them; K <= kAccBurst picks move no state.
+// FINISH: inv = 1 / picks of the whole update; merged_f32 may be `st` shifted back by the
+// window's start (a lane reads its 12 bytes before it writes them).
 // Errors are attributed per pick: a lane remembers in two 64-bit masks which picks failed
 // the Base64 check or differed from the first pick's header codes and after all its
 // groups ORs FLEET_ERRBIT_* into status[slot[k]]; clean data pays no atomics.
-struct PoolPicks {
-  int32_t slot[kAccBurst];
-};
-
 template <bool FINISH>
 __global__ void __launch_bounds__(kAccNT) k_pool_fold(const uint8_t* pool, size_t pitch, PoolPicks picks, float* st,
                                                       int first, int K, AccDampen dampen, double inv, int64_t n_up,
@@ -388,16 +321,13 @@ __global__ void __launch_bounds__(kAccNT) k_pool_fold(const uint8_t* pool, size_
                                                       const int32_t* __restrict__ hdr_block, int32_t* hfirst,
                                                       int* __restrict__ status, uint8_t* merged, float* merged_f32) {
   __shared__ AccShared sh;
-  const int n_hdr = hdr_block[1];
-  const int64_t walk_end = hdr_block[2];
-  const int32_t* hdr = hdr_block + 4;
-  acc_init(sh, hdr, n_hdr);
+  const AccHdr H = acc_block_open(sh, hdr_block);
   const int64_t ng = g_end - g_begin;
   uint64_t bad_picks = 0, layout_picks = 0;
   for (int64_t base = (int64_t)blockIdx.x * kAccNT; base < ng; base += (int64_t)gridDim.x * kAccNT) {
     const int64_t gl = base + threadIdx.x;
     const bool live = gl < ng;
-    const int64_t gs = live ? gl : 0, g = g_begin + gs;  // dead lanes run the chain on zero bytes and store nothing
+    const int64_t gs = live ? gl : 0, g = g_begin + gs;  // acc_group_open, spelled out (the file's header)
     float A[3] = {0.f, 0.f, 0.f};
     if (!first && live) {
       const f3u a = *reinterpret_cast<const f3u*>(st + 3 * gs);
@@ -405,9 +335,9 @@ __global__ void __launch_bounds__(kAccNT) k_pool_fold(const uint8_t* pool, size_
     }
     const uint32_t need = needed_chars_mask((int)min<int64_t>(3, max<int64_t>(0, n_up - 3 * g)));
     int h0;
-    const uint32_t hbits = acc_header_bits(sh, hdr, n_hdr, 3 * g, &h0);
-    const uint32_t kbits = keep_bits<3>(hbits, true, 3 * g, walk_end);
-    const bool wave_keep = __ballot(kbits != 0) != 0;  // wave-uniform: few waves hold a header
+    const uint32_t hbits = acc_header_bits(sh, H.hdr, H.n_hdr, 3 * g, &h0);
+    const uint32_t kbits = keep_bits<3>(hbits, true, 3 * g, H.walk_end);
+    const bool wave_keep = __ballot(kbits != 0) != 0;
     int32_t href[3] = {0, 0, 0}, keepc[3] = {0, 0, 0};
     if (wave_keep && !first) {
       int hi = h0;
@@ -459,62 +389,51 @@ static unsigned acc_grid(int64_t groups) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, 8LL * cus));
 }
 
-hipError_t launch_acc_push(const uint8_t* row, const float* st_in, float* st_out, int first, double dampen,
-                           int64_t n_up, int64_t g_begin, int64_t g_end, const int32_t* d_hdr_block,
-                           int32_t* d_hfirst, int* d_err, hipStream_t s) {
-  if (g_end <= g_begin) return hipSuccess;
-  hipLaunchKernelGGL(k_acc_push, dim3(acc_grid(g_end - g_begin)), dim3(kAccNT), 0, s, row, st_in, st_out, first, dampen,
-                     n_up, g_begin, g_end, d_hdr_block, d_hfirst, d_err);
+// One launch over the window's groups; an empty window launches nothing.
+template <typename... P, typename... A>
+static hipError_t acc_launch(void (*kern)(P...), const AccWindow& w, hipStream_t s, A... args) {
+  if (w.g_end <= w.g_begin) return hipSuccess;
+  kern<<<dim3(acc_grid(w.g_end - w.g_begin)), dim3(kAccNT), 0, s>>>(args...);
   return hipGetLastError();
 }
 
-hipError_t launch_acc_finish(const uint8_t* last_row, const float* st, double inv, int64_t n_up, int64_t g_begin,
-                             int64_t g_end, const int32_t* d_hdr_block, uint8_t* merged, float* merged_f32,
-                             hipStream_t s) {
-  if (g_end <= g_begin) return hipSuccess;
-  hipLaunchKernelGGL(k_acc_finish, dim3(acc_grid(g_end - g_begin)), dim3(kAccNT), 0, s, last_row, st, inv, n_up,
-                     g_begin, g_end, d_hdr_block, merged, merged_f32);
-  return hipGetLastError();
+// the K factors of a launch by value
+static AccDampen acc_dampen(const double* dampen, int K) {
+  AccDampen d;
+  for (int k = 0; k < kAccBurst; ++k) d.d[k] = k < K ? dampen[k] : 1.0;
+  return d;
+}
+
+hipError_t launch_acc_push(const uint8_t* row, const float* st_in, float* st_out, int first, double dampen,
+                           const AccWindow& w, int* d_err, hipStream_t s) {
+  return acc_launch(k_acc_push, w, s, row, st_in, st_out, first, dampen, w.n_up, w.g_begin, w.g_end, w.d_hdr_block,
+                    w.d_hfirst, d_err);
+}
+
+hipError_t launch_acc_finish(const uint8_t* last_row, const float* st, double inv, const AccWindow& w, uint8_t* merged,
+                             float* merged_f32, hipStream_t s) {
+  return acc_launch(k_acc_finish, w, s, last_row, st, inv, w.n_up, w.g_begin, w.g_end, w.d_hdr_block, merged,
+                    merged_f32);
 }
 
 hipError_t launch_acc_push_many(const uint8_t* rows, size_t pitch, const uint8_t* last_row, const float* st_in,
                                 float* st_out, int first, int K, const double* dampen, bool finish, double inv,
-                                int64_t n_up, int64_t g_begin, int64_t g_end, const int32_t* d_hdr_block,
-                                int32_t* d_hfirst, int* d_err, uint8_t* merged, float* merged_f32, hipStream_t s) {
+                                const AccWindow& w, int* d_err, uint8_t* merged, float* merged_f32, hipStream_t s) {
   if (K <= 0 || K > kAccBurst) return hipErrorInvalidValue;
-  if (g_end <= g_begin) return hipSuccess;
-  AccDampen d;
-  for (int k = 0; k < kAccBurst; ++k) d.d[k] = k < K ? dampen[k] : 1.0;
-  const dim3 grid(acc_grid(g_end - g_begin)), block(kAccNT);
-  if (finish)
-    hipLaunchKernelGGL(k_acc_push_many<true>, grid, block, 0, s, rows, pitch, last_row, st_in, st_out, first, K, d, inv,
-                       n_up, g_begin, g_end, d_hdr_block, d_hfirst, d_err, merged, merged_f32);
-  else
-    hipLaunchKernelGGL(k_acc_push_many<false>, grid, block, 0, s, rows, pitch, last_row, st_in, st_out, first, K, d, inv,
-                       n_up, g_begin, g_end, d_hdr_block, d_hfirst, d_err, merged, merged_f32);
-  return hipGetLastError();
+  return acc_launch(finish ? k_acc_push_many<true> : k_acc_push_many<false>, w, s, rows, pitch, last_row, st_in, st_out,
+                    first, K, acc_dampen(dampen, K), inv, w.n_up, w.g_begin, w.g_end, w.d_hdr_block, w.d_hfirst, d_err,
+                    merged, merged_f32);
 }
 
 hipError_t launch_pool_fold(const uint8_t* pool, size_t pitch, const int32_t* slots, float* st, int first, int K,
-                            const double* dampen, bool finish, double inv, int64_t n_up, int64_t g_begin, int64_t g_end,
-                            const int32_t* d_hdr_block, int32_t* d_hfirst, int* d_status, uint8_t* merged,
-                            float* merged_f32, hipStream_t s) {
+                            const double* dampen, bool finish, double inv, const AccWindow& w, int* d_status,
+                            uint8_t* merged, float* merged_f32, hipStream_t s) {
   if (K <= 0 || K > kAccBurst) return hipErrorInvalidValue;
-  if (g_end <= g_begin) return hipSuccess;
-  AccDampen d;
   PoolPicks p;
-  for (int k = 0; k < kAccBurst; ++k) {
-    d.d[k] = k < K ? dampen[k] : 1.0;
-    p.slot[k] = k < K ? slots[k] : 0;
-  }
-  const dim3 grid(acc_grid(g_end - g_begin)), block(kAccNT);
-  if (finish)
-    hipLaunchKernelGGL(k_pool_fold<true>, grid, block, 0, s, pool, pitch, p, st, first, K, d, inv, n_up, g_begin, g_end,
-                       d_hdr_block, d_hfirst, d_status, merged, merged_f32);
-  else
-    hipLaunchKernelGGL(k_pool_fold<false>, grid, block, 0, s, pool, pitch, p, st, first, K, d, inv, n_up, g_begin, g_end,
-                       d_hdr_block, d_hfirst, d_status, merged, merged_f32);
-  return hipGetLastError();
+  for (int k = 0; k < kAccBurst; ++k) p.slot[k] = k < K ? slots[k] : 0;
+  return acc_launch(finish ? k_pool_fold<true> : k_pool_fold<false>, w, s, pool, pitch, p, st, first, K,
+                    acc_dampen(dampen, K), inv, w.n_up, w.g_begin, w.g_end, w.d_hdr_block, w.d_hfirst, d_status, merged,
+                    merged_f32);
 }
 
 }  // namespace fleet

@@ -1785,6 +1785,113 @@ int fleet_model_version(fleet_ctx* c, const float* weights, const int32_t* dims,
 
 // ------------------------------------------------------ streaming aggregation
 
+// (static: a helper in an unnamed namespace inside this file's extern "C" block still gets
+// an unmangled dynamic symbol, and a name such as OpenACC's acc_free, which the OpenMP
+// runtime torch loads exports, would then be called in its place)
+namespace {
+
+constexpr size_t kAccPiece = 1 << 20;  // host rows: copy and DMA overlap in pieces
+
+// The part of an upload that an accumulator or a pool keeps: the groups [gb, ge) of
+// uploads of `len` characters (n values), bytes [col0, col0 + width) of the text. Rows
+// and state on the device hold the window alone; merged outputs are addressed by the
+// whole upload (kernels.h).
+struct Window {
+  size_t len = 0, n = 0, gb = 0, ge = 0, ng = 0, col0 = 0, width = 0;
+  int n_hdr = 0;
+  int32_t* d_hdr = nullptr;     // {0, count, walk_end, 0, positions}
+  int32_t* d_hfirst = nullptr;  // the batch's first upload's header codes
+  size_t row_bytes() const { return 16 * ng + 64; }
+  size_t state_bytes() const { return sizeof(float) * 3 * ng + 64; }
+  fleet::AccWindow launch() const { return {(int64_t)n, (int64_t)gb, (int64_t)ge, d_hdr, d_hfirst}; }
+};
+
+static void window_release(Window* w) {
+  if (w->d_hdr) (void)hipFree(w->d_hdr);
+  if (w->d_hfirst) (void)hipFree(w->d_hfirst);
+  w->d_hdr = w->d_hfirst = nullptr;
+}
+
+// Checks the arguments that describe the window (the entry points made the bare
+// FLEET_ERR_ARG checks), fills the geometry, allocates d_hfirst and uploads the header
+// block. A failed allocation returns FLEET_ERR_NOMEM with the geometry filled and no
+// message: the caller's names what it was creating.
+static int window_open(fleet_ctx* c, size_t len, const int32_t* header_pos, int n_headers, size_t group_begin,
+                       size_t group_end, Window* w) {
+  int rc = check_text_len(c, len);
+  if (rc) return rc;
+  const size_t n = fleet_b64_count(len), groups = groups_of(n);
+  if (16 * groups + 16 >= ((size_t)1 << 31)) return fail(c, FLEET_ERR_ARG, "upload of %zu bytes: 2 GiB or more", len);
+  if (group_end > groups) group_end = groups;
+  if (group_begin > group_end) return fail(c, FLEET_ERR_ARG, "group window [%zu, %zu) is empty or reversed", group_begin, group_end);
+  if ((rc = check_header_positions(c, header_pos, n_headers, n))) return rc;
+  w->len = len, w->n = n, w->n_hdr = n_headers;
+  w->gb = group_begin, w->ge = group_end, w->ng = group_end - group_begin;
+  w->col0 = 16 * w->gb;
+  w->width = w->ng ? std::min(len, 16 * w->ge) - w->col0 : 0;
+  // walk_end = n: the caller's layout covers the whole upload (as fleet_update_device)
+  std::vector<int32_t> hw{0, n_headers, (int32_t)n, 0};
+  if (n_headers) hw.insert(hw.end(), header_pos, header_pos + n_headers);
+  const size_t hdr_bytes = sizeof(int32_t) * hw.size();
+  if (hipMalloc((void**)&w->d_hdr, hdr_bytes) != hipSuccess ||
+      hipMalloc((void**)&w->d_hfirst, sizeof(int32_t) * ((size_t)n_headers + 16)) != hipSuccess ||
+      hipMemcpy(w->d_hdr, hw.data(), hdr_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    window_release(w);
+    return FLEET_ERR_NOMEM;
+  }
+  return FLEET_OK;
+}
+
+// `whose`: "the accumulator's", "the pool's"
+static int window_len_arg(fleet_ctx* c, const Window& w, size_t len, const char* whose) {
+  if (len != w.len) return fail(c, FLEET_ERR_ARG, "upload has length %zu, %s is %zu", len, whose, w.len);
+  return FLEET_OK;
+}
+
+// An upload's window from host memory to the device row `d` through the pinned row `h`,
+// in pieces on `s`. Bytes past `len` in a row's last group stay zero: the copy stops at len.
+static int window_copy_in(fleet_ctx* c, const Window& w, const char* upload, uint8_t* h, uint8_t* d, hipStream_t s) {
+  for (size_t o = 0; o < w.width; o += kAccPiece) {
+    const size_t m = std::min(kAccPiece, w.width - o);
+    std::memcpy(h + o, upload + w.col0 + o, m);
+    HIP_TRY(c, hipMemcpyAsync(d + o, h + o, m, hipMemcpyHostToDevice, s));
+  }
+  return FLEET_OK;
+}
+
+// A host finish's outputs from the spare device buffers that hold them, d_out and d_f32,
+// to the caller's buffers on `s`. The two hold the window alone: the kernel, which
+// addresses its outputs by the whole upload's group index, was given them shifted back
+// by the window's start.
+static int window_read_back(fleet_ctx* c, const Window& w, const uint8_t* d_out, const float* d_f32, char* merged,
+                            float* merged_f32, hipStream_t s) {
+  const size_t v0 = 3 * w.gb, v1 = std::max(v0, std::min(w.n, 3 * w.ge));
+  if (w.width) HIP_TRY(c, hipMemcpyAsync(merged + w.col0, d_out, w.width, hipMemcpyDeviceToHost, s));
+  if (merged_f32 && v1 > v0)
+    HIP_TRY(c, hipMemcpyAsync(merged_f32 + v0, d_f32, sizeof(float) * (v1 - v0), hipMemcpyDeviceToHost, s));
+  return FLEET_OK;
+}
+
+// Device-side calls still in flight on the caller's stream.
+struct InFlight {
+  bool pending = false;
+  hipStream_t stream = nullptr;
+  void on(hipStream_t s) { pending = true, stream = s; }
+  void done() { pending = false; }  // the caller synchronised `stream` itself
+};
+
+// Waits for them, unless they run on `same`, which orders the caller's next work itself.
+static int settle(fleet_ctx* c, InFlight* f, hipStream_t same, bool wait) {
+  if (f->pending && (wait || f->stream != same)) {
+    HIP_TRY(c, hipStreamSynchronize(f->stream));
+    f->done();
+  }
+  return FLEET_OK;
+}
+
+}  // namespace
+
 // One upload folded into a resident sum per call (acc_kernels.hip). The buffers come
 // in pairs: state[cur] holds the sum and the step writes state[cur ^ 1]; row[last]
 // holds the last accepted upload's window (the merge keeps its header codes) and the
@@ -1793,19 +1900,15 @@ int fleet_model_version(fleet_ctx* c, const float* weights, const int32_t* dims,
 // outputs (the next push overwrites both), so the accumulator holds nothing else.
 struct fleet_acc {
   fleet_ctx* c = nullptr;
-  size_t len = 0, n = 0, gb = 0, ge = 0, ng = 0, col0 = 0, width = 0;
-  int n_hdr = 0;
+  Window w;
   float* d_state[2] = {nullptr, nullptr};
   uint8_t* d_row[2] = {nullptr, nullptr};
   uint8_t* h_row[2] = {nullptr, nullptr};  // pinned
-  int32_t* d_hdr = nullptr;                // {0, count, walk_end, 0, positions}
-  int32_t* d_hfirst = nullptr;             // the batch's first upload's header codes
   int* d_err = nullptr;
   volatile int* h_err = nullptr;           // pinned: [0] synchronous reads, [1] written back after device pushes
   int cur = 0, last = 0, count = 0;
   int sticky = 0;                          // a device push's error, until fleet_acc_reset
-  bool pending = false;                    // device pushes in flight on pending_stream
-  hipStream_t pending_stream = nullptr;
+  InFlight fly;                            // device pushes
   // host bursts: rows 0..K-2 of a launch, window bytes at stage_pitch apart; grown on
   // demand to at most kAccBurst rows and kept until fleet_acc_destroy
   uint8_t* d_stage = nullptr;
@@ -1813,12 +1916,7 @@ struct fleet_acc {
   size_t stage_rows = 0, stage_pitch = 0;
 };
 
-// (static: a helper in an unnamed namespace inside this file's extern "C" block still gets
-// an unmangled dynamic symbol, and a name such as OpenACC's acc_free, which the OpenMP
-// runtime torch loads exports, would then be called in its place)
 namespace {
-
-constexpr size_t kAccPiece = 1 << 20;  // host push: copy and DMA overlap in pieces
 
 static int acc_code(fleet_ctx* c, int e) {
   if (e & FLEET_ERRBIT_BASE64) return fail(c, FLEET_ERR_BASE64, "input is not Base64::encode output (alphabet/padding)");
@@ -1832,14 +1930,10 @@ static int acc_sticky(fleet_acc* a) {
   return acc_code(a->c, FLEET_ERRBIT_LAYOUT);
 }
 
-// Waits for the device pushes in flight (unless they run on `same`, which orders the
-// caller's next work itself) and turns an error they wrote back into the sticky one.
+// Settles the device pushes in flight and turns an error they wrote back into the sticky one.
 static int acc_settle(fleet_acc* a, hipStream_t same, bool wait) {
-  fleet_ctx* c = a->c;
-  if (a->pending && (wait || a->pending_stream != same)) {
-    HIP_TRY(c, hipStreamSynchronize(a->pending_stream));
-    a->pending = false;
-  }
+  const int rc = settle(a->c, &a->fly, same, wait);
+  if (rc) return rc;
   const int e = a->h_err[1];
   if (e && !a->sticky) a->sticky = (e & FLEET_ERRBIT_BASE64) ? FLEET_ERR_BASE64 : FLEET_ERR_LAYOUT;
   return a->sticky ? acc_sticky(a) : FLEET_OK;
@@ -1853,12 +1947,27 @@ static int acc_clear_err(fleet_acc* a, hipStream_t s) {
   return FLEET_OK;
 }
 
+// the error word of the steps just enqueued on `s`, read synchronously; an error
+// leaves nothing committed
+static int acc_verdict(fleet_acc* a, hipStream_t s) {
+  fleet_ctx* c = a->c;
+  HIP_TRY(c, hipMemcpyAsync((void*)a->h_err, a->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  const int e = a->h_err[0];
+  if (e) {
+    const int rc = acc_clear_err(a, s);
+    return rc ? rc : acc_code(c, e);
+  }
+  return FLEET_OK;
+}
+
 static void release_accumulator(fleet_acc* a) {
-  for (void* p : {(void*)a->d_state[0], (void*)a->d_state[1], (void*)a->d_row[0], (void*)a->d_row[1], (void*)a->d_hdr,
-                  (void*)a->d_hfirst, (void*)a->d_err, (void*)a->d_stage})
+  for (void* p : {(void*)a->d_state[0], (void*)a->d_state[1], (void*)a->d_row[0], (void*)a->d_row[1], (void*)a->d_err,
+                  (void*)a->d_stage})
     if (p) (void)hipFree(p);
   for (void* p : {(void*)a->h_row[0], (void*)a->h_row[1], (void*)a->h_err, (void*)a->h_stage})
     if (p) (void)hipHostFree(p);
+  window_release(&a->w);
   delete a;
 }
 
@@ -1871,25 +1980,15 @@ int fleet_acc_create(fleet_ctx* c, size_t len, const int32_t* header_pos, int n_
   if (len == 0 || n_headers < 0 || n_headers > FLEET_MAX_HEADERS || (n_headers && !header_pos)) return FLEET_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DEVICE_SCOPE(c);
-  int rc = check_text_len(c, len);
+  Window w;
+  const int rc = window_open(c, len, header_pos, n_headers, group_begin, group_end, &w);
+  if (rc == FLEET_ERR_NOMEM)
+    return fail(c, FLEET_ERR_NOMEM, "fleet_acc_create: allocating the accumulator of %zu groups failed", w.ng);
   if (rc) return rc;
-  const size_t n = fleet_b64_count(len), groups = groups_of(n);
-  if (16 * groups + 16 >= ((size_t)1 << 31)) return fail(c, FLEET_ERR_ARG, "upload of %zu bytes: 2 GiB or more", len);
-  if (group_end > groups) group_end = groups;
-  if (group_begin > group_end) return fail(c, FLEET_ERR_ARG, "group window [%zu, %zu) is empty or reversed", group_begin, group_end);
-  if ((rc = check_header_positions(c, header_pos, n_headers, n))) return rc;
   fleet_acc* a = new fleet_acc();
   a->c = c;
-  a->len = len;
-  a->n = n;
-  a->gb = group_begin;
-  a->ge = group_end;
-  a->ng = group_end - group_begin;
-  a->col0 = 16 * a->gb;
-  a->width = a->ng ? std::min(len, 16 * a->ge) - a->col0 : 0;
-  a->n_hdr = n_headers;
-  const size_t row_bytes = 16 * a->ng + 64, st_bytes = sizeof(float) * 3 * a->ng + 64;
-  const size_t hdr_bytes = sizeof(int32_t) * ((size_t)n_headers + 4);
+  a->w = w;
+  const size_t row_bytes = a->w.row_bytes(), st_bytes = a->w.state_bytes();
   bool ok = true;
   for (int i = 0; i < 2 && ok; ++i) {
     ok = hipMalloc((void**)&a->d_state[i], st_bytes) == hipSuccess && hipMalloc((void**)&a->d_row[i], row_bytes) == hipSuccess &&
@@ -1898,26 +1997,15 @@ int fleet_acc_create(fleet_ctx* c, size_t len, const int32_t* header_pos, int n_
     if (ok) std::memset(a->h_row[i], 0, row_bytes);
     ok = ok && hipMemset(a->d_row[i], 0, row_bytes) == hipSuccess && hipMemset(a->d_state[i], 0, st_bytes) == hipSuccess;
   }
-  ok = ok && hipMalloc((void**)&a->d_hdr, hdr_bytes) == hipSuccess &&
-       hipMalloc((void**)&a->d_hfirst, sizeof(int32_t) * ((size_t)n_headers + 16)) == hipSuccess &&
-       hipMalloc((void**)&a->d_err, 64) == hipSuccess && hipMemset(a->d_err, 0, 64) == hipSuccess &&
+  ok = ok && hipMalloc((void**)&a->d_err, 64) == hipSuccess && hipMemset(a->d_err, 0, 64) == hipSuccess &&
        hipHostMalloc((void**)&a->h_err, 64, hipHostMallocDefault) == hipSuccess;
-  if (ok) {
-    a->h_err[0] = 0;
-    a->h_err[1] = 0;
-    std::vector<int32_t> hw((size_t)n_headers + 4);
-    hw[0] = 0;
-    hw[1] = n_headers;
-    hw[2] = (int32_t)n;  // the caller's layout covers the whole upload (as fleet_update_device)
-    hw[3] = 0;
-    if (n_headers) std::memcpy(hw.data() + 4, header_pos, sizeof(int32_t) * (size_t)n_headers);
-    ok = hipMemcpy(a->d_hdr, hw.data(), hdr_bytes, hipMemcpyHostToDevice) == hipSuccess;
-  }
   if (!ok) {
     (void)hipGetLastError();
     release_accumulator(a);
-    return fail(c, FLEET_ERR_NOMEM, "fleet_acc_create: allocating the accumulator of %zu groups failed", group_end - group_begin);
+    return fail(c, FLEET_ERR_NOMEM, "fleet_acc_create: allocating the accumulator of %zu groups failed", w.ng);
   }
+  a->h_err[0] = 0;
+  a->h_err[1] = 0;
   *out = a;
   return FLEET_OK;
 }
@@ -1927,7 +2015,7 @@ void fleet_acc_destroy(fleet_acc* a) {
   fleet_ctx* c = a->c;
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard dg(c->device);
-  if (a->pending) (void)hipStreamSynchronize(a->pending_stream);
+  (void)settle(c, &a->fly, nullptr, true);
   (void)hipStreamSynchronize(c->stream);
   release_accumulator(a);
 }
@@ -1939,25 +2027,14 @@ int fleet_acc_push(fleet_acc* a, const char* upload, size_t len, double dampen) 
   fleet_ctx* c = a->c;
   std::lock_guard<std::mutex> lk(c->mu);
   DEVICE_SCOPE(c);
-  if (len != a->len) return fail(c, FLEET_ERR_ARG, "upload has length %zu, the accumulator's is %zu", len, a->len);
-  int rc = acc_settle(a, c->stream, true);
+  int rc = window_len_arg(c, a->w, len, "the accumulator's");
   if (rc) return rc;
+  if ((rc = acc_settle(a, c->stream, true))) return rc;
   const int spare = a->last ^ 1;
-  for (size_t o = 0; o < a->width; o += kAccPiece) {
-    const size_t m = std::min(kAccPiece, a->width - o);
-    std::memcpy(a->h_row[spare] + o, upload + a->col0 + o, m);
-    HIP_TRY(c, hipMemcpyAsync(a->d_row[spare] + o, a->h_row[spare] + o, m, hipMemcpyHostToDevice, c->stream));
-  }
+  if ((rc = window_copy_in(c, a->w, upload, a->h_row[spare], a->d_row[spare], c->stream))) return rc;
   HIP_TRY(c, fleet::launch_acc_push(a->d_row[spare], a->d_state[a->cur], a->d_state[a->cur ^ 1], a->count == 0, dampen,
-                                    (int64_t)a->n, (int64_t)a->gb, (int64_t)a->ge, a->d_hdr, a->d_hfirst, a->d_err,
-                                    c->stream));
-  HIP_TRY(c, hipMemcpyAsync((void*)a->h_err, a->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const int e = a->h_err[0];
-  if (e) {  // rejected: state[cur], row[last] and the count are as before the call
-    if ((rc = acc_clear_err(a, c->stream))) return rc;
-    return acc_code(c, e);
-  }
+                                    a->w.launch(), a->d_err, c->stream));
+  if ((rc = acc_verdict(a, c->stream))) return rc;  // rejected: state[cur], row[last] and the count are as before
   a->cur ^= 1;
   a->last = spare;
   ++a->count;
@@ -1973,16 +2050,15 @@ int fleet_acc_push_device(fleet_acc* a, const void* d_upload, double dampen, voi
   int rc = acc_settle(a, s, false);
   if (rc) return rc;
   const int spare = a->last ^ 1;
-  if (a->width)
-    HIP_TRY(c, hipMemcpyAsync(a->d_row[spare], (const uint8_t*)d_upload + a->col0, a->width, hipMemcpyDeviceToDevice, s));
+  if (a->w.width)
+    HIP_TRY(c, hipMemcpyAsync(a->d_row[spare], (const uint8_t*)d_upload + a->w.col0, a->w.width, hipMemcpyDeviceToDevice, s));
   HIP_TRY(c, fleet::launch_acc_push(a->d_row[spare], a->d_state[a->cur], a->d_state[a->cur ^ 1], a->count == 0, dampen,
-                                    (int64_t)a->n, (int64_t)a->gb, (int64_t)a->ge, a->d_hdr, a->d_hfirst, a->d_err, s));
+                                    a->w.launch(), a->d_err, s));
   HIP_TRY(c, hipMemcpyAsync((void*)(a->h_err + 1), a->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
   a->cur ^= 1;
   a->last = spare;
   ++a->count;
-  a->pending = true;
-  a->pending_stream = s;
+  a->fly.on(s);
   return FLEET_OK;
 }
 
@@ -1994,19 +2070,13 @@ int fleet_acc_finish(fleet_acc* a, char* merged, size_t cap, size_t* out_len, fl
   int rc = acc_settle(a, c->stream, true);
   if (rc) return rc;
   if (a->count == 0) return fail(c, FLEET_ERR_ARG, "fleet_acc_finish: nothing was pushed");
-  if (out_len) *out_len = a->len;
-  if (cap < a->len) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu", cap, a->len);
-  // outputs in the spare row and the spare state (window coordinates: shifted back by
-  // the window's start, as the kernel addresses them by the whole upload's group index)
-  uint8_t* d_out = a->d_row[a->last ^ 1];
+  if (out_len) *out_len = a->w.len;
+  if (cap < a->w.len) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu", cap, a->w.len);
+  uint8_t* d_out = a->d_row[a->last ^ 1];  // the spare row and the spare state
   float* d_f32 = a->d_state[a->cur ^ 1];
-  HIP_TRY(c, fleet::launch_acc_finish(a->d_row[a->last], a->d_state[a->cur], (double)1 / a->count, (int64_t)a->n,
-                                      (int64_t)a->gb, (int64_t)a->ge, a->d_hdr, d_out - a->col0,
-                                      merged_f32 ? d_f32 - 3 * a->gb : nullptr, c->stream));
-  const size_t v0 = 3 * a->gb, v1 = std::max(v0, std::min(a->n, 3 * a->ge));
-  if (a->width) HIP_TRY(c, hipMemcpyAsync(merged + a->col0, d_out, a->width, hipMemcpyDeviceToHost, c->stream));
-  if (merged_f32 && v1 > v0)
-    HIP_TRY(c, hipMemcpyAsync(merged_f32 + v0, d_f32, sizeof(float) * (v1 - v0), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, fleet::launch_acc_finish(a->d_row[a->last], a->d_state[a->cur], (double)1 / a->count, a->w.launch(),
+                                      d_out - a->w.col0, merged_f32 ? d_f32 - 3 * a->w.gb : nullptr, c->stream));
+  if ((rc = window_read_back(c, a->w, d_out, d_f32, merged, merged_f32, c->stream))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   a->count = 0;
   return FLEET_OK;
@@ -2021,12 +2091,11 @@ int fleet_acc_finish_device(fleet_acc* a, void* d_merged, void* d_merged_f32, vo
   int rc = acc_settle(a, s, false);
   if (rc) return rc;
   if (a->count == 0) return fail(c, FLEET_ERR_ARG, "fleet_acc_finish_device: nothing was pushed");
-  HIP_TRY(c, fleet::launch_acc_finish(a->d_row[a->last], a->d_state[a->cur], (double)1 / a->count, (int64_t)a->n,
-                                      (int64_t)a->gb, (int64_t)a->ge, a->d_hdr, (uint8_t*)d_merged,
-                                      (float*)d_merged_f32, s));
+  HIP_TRY(c, fleet::launch_acc_finish(a->d_row[a->last], a->d_state[a->cur], (double)1 / a->count, a->w.launch(),
+                                      (uint8_t*)d_merged, (float*)d_merged_f32, s));
   HIP_TRY(c, hipMemcpyAsync((void*)(a->h_err + 1), a->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
-  a->pending = false;
+  a->fly.done();
   if ((rc = acc_settle(a, s, false))) return rc;  // a device push of this batch was malformed
   a->count = 0;
   return FLEET_OK;
@@ -2038,13 +2107,13 @@ namespace {
 
 static int acc_stage_reserve(fleet_acc* a, size_t rows) {
   fleet_ctx* c = a->c;
-  if (rows <= a->stage_rows || a->ng == 0) return FLEET_OK;
+  if (rows <= a->stage_rows || a->w.ng == 0) return FLEET_OK;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (a->d_stage) (void)hipFree(a->d_stage);
   if (a->h_stage) (void)hipHostFree(a->h_stage);
   a->d_stage = a->h_stage = nullptr;
   a->stage_rows = 0;
-  a->stage_pitch = 16 * a->ng + 64;
+  a->stage_pitch = a->w.row_bytes();
   const size_t bytes = rows * a->stage_pitch;
   if (hipMalloc((void**)&a->d_stage, bytes) != hipSuccess ||
       hipHostMalloc((void**)&a->h_stage, bytes, hipHostMallocDefault) != hipSuccess ||
@@ -2055,8 +2124,7 @@ static int acc_stage_reserve(fleet_acc* a, size_t rows) {
     a->d_stage = a->h_stage = nullptr;
     return fail(c, FLEET_ERR_NOMEM, "burst staging of %zu rows of %zu bytes failed", rows, a->stage_pitch);
   }
-  // bytes past `len` in a row's last group stay zero: the uploads' copies stop at len
-  std::memset(a->h_stage, 0, bytes);
+  std::memset(a->h_stage, 0, bytes);  // as the rows of fleet_acc_create
   a->stage_rows = rows;
   return FLEET_OK;
 }
@@ -2070,14 +2138,12 @@ static int acc_stage_reserve(fleet_acc* a, size_t rows) {
 static int acc_fold(fleet_acc* a, const char* const* uploads, const uint8_t* d_rows, size_t pitch, int K,
                     const double* dampen, hipStream_t s, bool finish, uint8_t* d_merged, float* d_f32) {
   fleet_ctx* c = a->c;
-  if (a->ng == 0) return FLEET_OK;
+  if (a->w.ng == 0) return FLEET_OK;
   constexpr int B = fleet::kAccBurst;
   const int spare = a->last ^ 1;
-  if (uploads) {
-    // a launch's rows but the burst's last one, which goes to the spare row
-    const int rc = acc_stage_reserve(a, (size_t)(K > B ? B : K - 1));
-    if (rc) return rc;
-  }
+  int rc;
+  // a launch's rows but the burst's last one, which goes to the spare row
+  if (uploads && (rc = acc_stage_reserve(a, (size_t)(K > B ? B : K - 1)))) return rc;
   const double inv = (double)1 / (a->count + K);
   for (int k0 = 0; k0 < K; k0 += B) {
     const int kc = std::min(B, K - k0);
@@ -2090,11 +2156,7 @@ static int acc_fold(fleet_acc* a, const char* const* uploads, const uint8_t* d_r
         const bool to_spare = last_chunk && k == kc - 1;
         uint8_t* h = to_spare ? a->h_row[spare] : a->h_stage + (size_t)k * a->stage_pitch;
         uint8_t* d = to_spare ? a->d_row[spare] : a->d_stage + (size_t)k * a->stage_pitch;
-        for (size_t o = 0; o < a->width; o += kAccPiece) {  // copy and DMA overlap in pieces, as fleet_acc_push
-          const size_t m = std::min(kAccPiece, a->width - o);
-          std::memcpy(h + o, uploads[k0 + k] + a->col0 + o, m);
-          HIP_TRY(c, hipMemcpyAsync(d + o, h + o, m, hipMemcpyHostToDevice, s));
-        }
+        if ((rc = window_copy_in(c, a->w, uploads[k0 + k], h, d, s))) return rc;
       }
       rows = a->d_stage;
       rp = a->stage_pitch;
@@ -2102,13 +2164,12 @@ static int acc_fold(fleet_acc* a, const char* const* uploads, const uint8_t* d_r
       rows = d_rows + (size_t)k0 * pitch;
       rp = pitch;
       if (last_chunk)
-        HIP_TRY(c, hipMemcpyAsync(a->d_row[spare], rows + (size_t)(kc - 1) * pitch, a->width, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(a->d_row[spare], rows + (size_t)(kc - 1) * pitch, a->w.width, hipMemcpyDeviceToDevice, s));
     }
     last_row = last_chunk ? a->d_row[spare] : rows + (size_t)(kc - 1) * rp;
     const bool fin = finish && last_chunk;
     HIP_TRY(c, fleet::launch_acc_push_many(rows, rp, last_row, a->d_state[k0 ? a->cur ^ 1 : a->cur], a->d_state[a->cur ^ 1],
-                                           k0 == 0 && a->count == 0, kc, dampen + k0, fin, inv, (int64_t)a->n,
-                                           (int64_t)a->gb, (int64_t)a->ge, a->d_hdr, a->d_hfirst, a->d_err,
+                                           k0 == 0 && a->count == 0, kc, dampen + k0, fin, inv, a->w.launch(), a->d_err,
                                            fin ? d_merged : nullptr, fin ? d_f32 : nullptr, s));
   }
   return FLEET_OK;
@@ -2117,30 +2178,16 @@ static int acc_fold(fleet_acc* a, const char* const* uploads, const uint8_t* d_r
 static int acc_host_args(fleet_acc* a, const char* const* uploads, const size_t* lens, int K, const char* what) {
   for (int k = 0; k < K; ++k) {
     if (!uploads[k]) return fail(a->c, FLEET_ERR_ARG, "%s: upload %d is NULL", what, k);
-    if (lens[k] != a->len)
-      return fail(a->c, FLEET_ERR_ARG, "%s: upload %d has length %zu, the accumulator's is %zu", what, k, lens[k], a->len);
+    if (lens[k] != a->w.len)
+      return fail(a->c, FLEET_ERR_ARG, "%s: upload %d has length %zu, the accumulator's is %zu", what, k, lens[k], a->w.len);
   }
   return FLEET_OK;
 }
 
 // rows 0..K-2 are read in place with 16-byte loads
 static int acc_device_args(fleet_acc* a, const void* d_uploads, size_t pitch, int K, const char* what) {
-  if (K > 1 && (pitch % 16 != 0 || pitch < 16 * groups_of(a->n) || (uintptr_t)d_uploads % 16 != 0))
+  if (K > 1 && (pitch % 16 != 0 || pitch < 16 * groups_of(a->w.n) || (uintptr_t)d_uploads % 16 != 0))
     return fail(a->c, FLEET_ERR_ARG, "%s: rows must be 16-byte aligned, the pitch a multiple of 16 covering the upload's groups", what);
-  return FLEET_OK;
-}
-
-// the error word of the burst just enqueued on `s`, read synchronously; an error
-// leaves nothing committed
-static int acc_burst_verdict(fleet_acc* a, hipStream_t s) {
-  fleet_ctx* c = a->c;
-  HIP_TRY(c, hipMemcpyAsync((void*)a->h_err, a->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  const int e = a->h_err[0];
-  if (e) {
-    const int rc = acc_clear_err(a, s);
-    return rc ? rc : acc_code(c, e);
-  }
   return FLEET_OK;
 }
 
@@ -2157,7 +2204,7 @@ int fleet_acc_push_many(fleet_acc* a, const char* const* uploads, const size_t* 
   if (rc) return rc;
   if ((rc = acc_settle(a, c->stream, true))) return rc;
   if ((rc = acc_fold(a, uploads, nullptr, 0, K, dampen, c->stream, false, nullptr, nullptr))) return rc;
-  if ((rc = acc_burst_verdict(a, c->stream))) return rc;  // rejected: state[cur], row[last] and the count are as before
+  if ((rc = acc_verdict(a, c->stream))) return rc;  // rejected: state[cur], row[last] and the count are as before
   a->cur ^= 1;
   a->last ^= 1;
   a->count += K;
@@ -2174,14 +2221,13 @@ int fleet_acc_push_many_device(fleet_acc* a, const void* d_uploads, size_t pitch
   if (rc) return rc;
   hipStream_t s = pick(c, stream);
   if ((rc = acc_settle(a, s, false))) return rc;
-  if ((rc = acc_fold(a, nullptr, (const uint8_t*)d_uploads + a->col0, pitch, K, dampen, s, false, nullptr, nullptr)))
+  if ((rc = acc_fold(a, nullptr, (const uint8_t*)d_uploads + a->w.col0, pitch, K, dampen, s, false, nullptr, nullptr)))
     return rc;
   HIP_TRY(c, hipMemcpyAsync((void*)(a->h_err + 1), a->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
   a->cur ^= 1;
   a->last ^= 1;
   a->count += K;
-  a->pending = true;
-  a->pending_stream = s;
+  a->fly.on(s);
   return FLEET_OK;
 }
 
@@ -2194,20 +2240,15 @@ int fleet_acc_push_finish(fleet_acc* a, const char* const* uploads, const size_t
   int rc = acc_host_args(a, uploads, lens, K, "fleet_acc_push_finish");
   if (rc) return rc;
   if ((rc = acc_settle(a, c->stream, true))) return rc;
-  if (out_len) *out_len = a->len;
-  if (cap < a->len) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu", cap, a->len);
-  // outputs in the spare row (over row K-1, which the lane has read by then) and the
-  // spare state, as fleet_acc_finish
-  uint8_t* d_out = a->d_row[a->last ^ 1];
+  if (out_len) *out_len = a->w.len;
+  if (cap < a->w.len) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu", cap, a->w.len);
+  uint8_t* d_out = a->d_row[a->last ^ 1];  // over row K-1, which the lane has read by then
   float* d_f32 = a->d_state[a->cur ^ 1];
-  if ((rc = acc_fold(a, uploads, nullptr, 0, K, dampen, c->stream, true, d_out - a->col0,
-                     merged_f32 ? d_f32 - 3 * a->gb : nullptr)))
+  if ((rc = acc_fold(a, uploads, nullptr, 0, K, dampen, c->stream, true, d_out - a->w.col0,
+                     merged_f32 ? d_f32 - 3 * a->w.gb : nullptr)))
     return rc;
-  const size_t v0 = 3 * a->gb, v1 = std::max(v0, std::min(a->n, 3 * a->ge));
-  if (a->width) HIP_TRY(c, hipMemcpyAsync(merged + a->col0, d_out, a->width, hipMemcpyDeviceToHost, c->stream));
-  if (merged_f32 && v1 > v0)
-    HIP_TRY(c, hipMemcpyAsync(merged_f32 + v0, d_f32, sizeof(float) * (v1 - v0), hipMemcpyDeviceToHost, c->stream));
-  if ((rc = acc_burst_verdict(a, c->stream))) return rc;  // rejected: nothing committed (the outputs are not meaningful)
+  if ((rc = window_read_back(c, a->w, d_out, d_f32, merged, merged_f32, c->stream))) return rc;
+  if ((rc = acc_verdict(a, c->stream))) return rc;  // rejected: nothing committed (the outputs are not meaningful)
   a->count = 0;
   return FLEET_OK;
 }
@@ -2222,14 +2263,14 @@ int fleet_acc_push_finish_device(fleet_acc* a, const void* d_uploads, size_t pit
   if (rc) return rc;
   hipStream_t s = pick(c, stream);
   if ((rc = acc_settle(a, s, false))) return rc;
-  if ((rc = acc_fold(a, nullptr, (const uint8_t*)d_uploads + a->col0, pitch, K, dampen, s, true, (uint8_t*)d_merged,
+  if ((rc = acc_fold(a, nullptr, (const uint8_t*)d_uploads + a->w.col0, pitch, K, dampen, s, true, (uint8_t*)d_merged,
                      (float*)d_merged_f32)))
     return rc;
   // device pushes of this batch still in flight are on `s` and wrote their error word
   // back before this burst ran: theirs is sticky and comes first, the burst's own is not
   HIP_TRY(c, hipMemcpyAsync((void*)a->h_err, a->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
-  a->pending = false;
+  a->fly.done();
   if ((rc = acc_settle(a, s, false))) return rc;
   const int e = a->h_err[0];
   if (e) {
@@ -2245,12 +2286,8 @@ int fleet_acc_reset(fleet_acc* a) {
   fleet_ctx* c = a->c;
   std::lock_guard<std::mutex> lk(c->mu);
   DEVICE_SCOPE(c);
-  if (a->pending) {
-    HIP_TRY(c, hipStreamSynchronize(a->pending_stream));
-    a->pending = false;
-  }
-  int rc = acc_clear_err(a, c->stream);
-  if (rc) return rc;
+  int rc = settle(c, &a->fly, nullptr, true);
+  if (rc || (rc = acc_clear_err(a, c->stream))) return rc;
   a->sticky = 0;
   a->count = 0;
   return FLEET_OK;
@@ -2265,38 +2302,28 @@ int fleet_acc_reset(fleet_acc* a) {
 // the state (the finish launch reads a lane's 12 bytes before it writes them).
 struct fleet_pool {
   fleet_ctx* c = nullptr;
-  size_t len = 0, n = 0, gb = 0, ge = 0, ng = 0, col0 = 0, width = 0, pitch = 0;
-  int n_hdr = 0, slots = 0;
+  Window w;
+  size_t pitch = 0;
+  int slots = 0;
   uint8_t* d_rows = nullptr;
-  float* d_state = nullptr;     // the running value between the launches of an update of more than kAccBurst picks
-  int32_t* d_hdr = nullptr;     // {0, count, walk_end, 0, positions}
-  int32_t* d_hfirst = nullptr;  // the update's first pick's header codes
-  int* d_status = nullptr;      // one error word per slot, cleared by every update
-  int* h_status = nullptr;      // pinned: what the last update left in d_status
-  uint8_t* h_row = nullptr;     // pinned: a host put's way in
+  float* d_state = nullptr;  // the running value between the launches of an update of more than kAccBurst picks
+  int* d_status = nullptr;   // one error word per slot, cleared by every update
+  int* h_status = nullptr;   // pinned: what the last update left in d_status
+  uint8_t* h_row = nullptr;  // pinned: a host put's way in
   std::vector<uint8_t> occupied;
-  std::vector<uint8_t> seen;    // update: the picks so far
-  bool pending = false;         // device puts in flight on pending_stream
-  hipStream_t pending_stream = nullptr;
+  std::vector<uint8_t> seen;  // update: the picks so far
+  InFlight fly;               // device puts
 };
 
 namespace {
 
 static void release_pool(fleet_pool* p) {
-  for (void* d : {(void*)p->d_rows, (void*)p->d_state, (void*)p->d_hdr, (void*)p->d_hfirst, (void*)p->d_status})
+  for (void* d : {(void*)p->d_rows, (void*)p->d_state, (void*)p->d_status})
     if (d) (void)hipFree(d);
   for (void* h : {(void*)p->h_status, (void*)p->h_row})
     if (h) (void)hipHostFree(h);
+  window_release(&p->w);
   delete p;
-}
-
-// waits for the device puts in flight unless they run on `same`, which orders the caller's next work itself
-static int pool_settle(fleet_pool* p, hipStream_t same, bool wait) {
-  if (p->pending && (wait || p->pending_stream != same)) {
-    HIP_TRY(p->c, hipStreamSynchronize(p->pending_stream));
-    p->pending = false;
-  }
-  return FLEET_OK;
 }
 
 static int pool_slot_arg(fleet_pool* p, int slot, const char* what) {
@@ -2328,8 +2355,7 @@ static int pool_fold(fleet_pool* p, const int32_t* picks, int K, const double* d
   for (int k0 = 0; k0 < K; k0 += B) {
     const int kc = std::min(B, K - k0);
     HIP_TRY(c, fleet::launch_pool_fold(p->d_rows, p->pitch, picks + k0, p->d_state, k0 == 0, kc, dampen + k0, k0 + kc == K,
-                                       (double)1 / K, (int64_t)p->n, (int64_t)p->gb, (int64_t)p->ge, p->d_hdr,
-                                       p->d_hfirst, p->d_status, d_merged, d_f32, s));
+                                       (double)1 / K, p->w.launch(), p->d_status, d_merged, d_f32, s));
   }
   HIP_TRY(c, hipMemcpyAsync(p->h_status, p->d_status, sizeof(int) * (size_t)p->slots, hipMemcpyDeviceToHost, s));
   return FLEET_OK;
@@ -2361,53 +2387,34 @@ int fleet_pool_create(fleet_ctx* c, size_t len, const int32_t* header_pos, int n
     return FLEET_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DEVICE_SCOPE(c);
-  int rc = check_text_len(c, len);
+  Window w;
+  const int rc = window_open(c, len, header_pos, n_headers, group_begin, group_end, &w);
+  if (rc == FLEET_ERR_NOMEM)
+    return fail(c, FLEET_ERR_NOMEM, "fleet_pool_create: allocating %d slots of %zu groups failed", slots, w.ng);
   if (rc) return rc;
-  const size_t n = fleet_b64_count(len), groups = groups_of(n);
-  if (16 * groups + 16 >= ((size_t)1 << 31)) return fail(c, FLEET_ERR_ARG, "upload of %zu bytes: 2 GiB or more", len);
-  if (group_end > groups) group_end = groups;
-  if (group_begin > group_end) return fail(c, FLEET_ERR_ARG, "group window [%zu, %zu) is empty or reversed", group_begin, group_end);
-  if ((rc = check_header_positions(c, header_pos, n_headers, n))) return rc;
   fleet_pool* p = new fleet_pool();
   p->c = c;
-  p->len = len;
-  p->n = n;
-  p->gb = group_begin;
-  p->ge = group_end;
-  p->ng = group_end - group_begin;
-  p->col0 = 16 * p->gb;
-  p->width = p->ng ? std::min(len, 16 * p->ge) - p->col0 : 0;
-  p->pitch = 16 * p->ng + 64;
-  p->n_hdr = n_headers;
+  p->w = w;
+  p->pitch = p->w.row_bytes();
   p->slots = slots;
   p->occupied.assign((size_t)slots, 0);
   p->seen.assign((size_t)slots, 0);
-  const size_t rows_bytes = ((size_t)slots + 1) * p->pitch, st_bytes = sizeof(float) * 3 * p->ng + 64;
-  const size_t hdr_bytes = sizeof(int32_t) * ((size_t)n_headers + 4), status_bytes = sizeof(int) * (size_t)slots;
-  // the rows are zeroed once: bytes past `len` in a row's last group stay zero, the puts' copies stop at len
-  bool ok = hipMalloc((void**)&p->d_rows, rows_bytes) == hipSuccess && hipMemset(p->d_rows, 0, rows_bytes) == hipSuccess &&
-            hipMalloc((void**)&p->d_state, st_bytes) == hipSuccess && hipMemset(p->d_state, 0, st_bytes) == hipSuccess &&
-            hipMalloc((void**)&p->d_hdr, hdr_bytes) == hipSuccess &&
-            hipMalloc((void**)&p->d_hfirst, sizeof(int32_t) * ((size_t)n_headers + 16)) == hipSuccess &&
-            hipMalloc((void**)&p->d_status, status_bytes) == hipSuccess &&
-            hipMemset(p->d_status, 0, status_bytes) == hipSuccess &&
-            hipHostMalloc((void**)&p->h_status, status_bytes, hipHostMallocDefault) == hipSuccess &&
-            hipHostMalloc((void**)&p->h_row, p->pitch, hipHostMallocDefault) == hipSuccess;
-  if (ok) {
-    std::memset(p->h_status, 0, status_bytes);
-    std::vector<int32_t> hw((size_t)n_headers + 4);
-    hw[0] = 0;
-    hw[1] = n_headers;
-    hw[2] = (int32_t)n;  // the caller's layout covers the whole upload (as fleet_acc_create)
-    hw[3] = 0;
-    if (n_headers) std::memcpy(hw.data() + 4, header_pos, sizeof(int32_t) * (size_t)n_headers);
-    ok = hipMemcpy(p->d_hdr, hw.data(), hdr_bytes, hipMemcpyHostToDevice) == hipSuccess;
-  }
+  const size_t rows_bytes = ((size_t)slots + 1) * p->pitch, st_bytes = p->w.state_bytes();
+  const size_t status_bytes = sizeof(int) * (size_t)slots;
+  // the rows are zeroed once: the puts' copies stop at len
+  const bool ok = hipMalloc((void**)&p->d_rows, rows_bytes) == hipSuccess &&
+                  hipMemset(p->d_rows, 0, rows_bytes) == hipSuccess && hipMalloc((void**)&p->d_state, st_bytes) == hipSuccess &&
+                  hipMemset(p->d_state, 0, st_bytes) == hipSuccess &&
+                  hipMalloc((void**)&p->d_status, status_bytes) == hipSuccess &&
+                  hipMemset(p->d_status, 0, status_bytes) == hipSuccess &&
+                  hipHostMalloc((void**)&p->h_status, status_bytes, hipHostMallocDefault) == hipSuccess &&
+                  hipHostMalloc((void**)&p->h_row, p->pitch, hipHostMallocDefault) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
     release_pool(p);
-    return fail(c, FLEET_ERR_NOMEM, "fleet_pool_create: allocating %d slots of %zu groups failed", slots, group_end - group_begin);
+    return fail(c, FLEET_ERR_NOMEM, "fleet_pool_create: allocating %d slots of %zu groups failed", slots, w.ng);
   }
+  std::memset(p->h_status, 0, status_bytes);
   *out = p;
   return FLEET_OK;
 }
@@ -2417,7 +2424,7 @@ void fleet_pool_destroy(fleet_pool* p) {
   fleet_ctx* c = p->c;
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard dg(c->device);
-  if (p->pending) (void)hipStreamSynchronize(p->pending_stream);
+  (void)settle(c, &p->fly, nullptr, true);
   (void)hipStreamSynchronize(c->stream);
   release_pool(p);
 }
@@ -2443,14 +2450,9 @@ int fleet_pool_put(fleet_pool* p, int slot, const char* upload, size_t len) {
   DEVICE_SCOPE(c);
   int rc = pool_slot_arg(p, slot, "fleet_pool_put");
   if (rc) return rc;
-  if (len != p->len) return fail(c, FLEET_ERR_ARG, "upload has length %zu, the pool's is %zu", len, p->len);
-  if ((rc = pool_settle(p, c->stream, true))) return rc;
-  uint8_t* d = p->d_rows + (size_t)slot * p->pitch;
-  for (size_t o = 0; o < p->width; o += kAccPiece) {  // copy and DMA overlap in pieces, as fleet_acc_push
-    const size_t m = std::min(kAccPiece, p->width - o);
-    std::memcpy(p->h_row + o, upload + p->col0 + o, m);
-    HIP_TRY(c, hipMemcpyAsync(d + o, p->h_row + o, m, hipMemcpyHostToDevice, c->stream));
-  }
+  if ((rc = window_len_arg(c, p->w, len, "the pool's"))) return rc;
+  if ((rc = settle(c, &p->fly, c->stream, true))) return rc;
+  if ((rc = window_copy_in(c, p->w, upload, p->h_row, p->d_rows + (size_t)slot * p->pitch, c->stream))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   p->occupied[slot] = 1;
   return FLEET_OK;
@@ -2464,13 +2466,12 @@ int fleet_pool_put_device(fleet_pool* p, int slot, const void* d_upload, void* s
   int rc = pool_slot_arg(p, slot, "fleet_pool_put_device");
   if (rc) return rc;
   hipStream_t s = pick(c, stream);
-  if ((rc = pool_settle(p, s, false))) return rc;
-  if (p->width)
-    HIP_TRY(c, hipMemcpyAsync(p->d_rows + (size_t)slot * p->pitch, (const uint8_t*)d_upload + p->col0, p->width,
+  if ((rc = settle(c, &p->fly, s, false))) return rc;
+  if (p->w.width)
+    HIP_TRY(c, hipMemcpyAsync(p->d_rows + (size_t)slot * p->pitch, (const uint8_t*)d_upload + p->w.col0, p->w.width,
                               hipMemcpyDeviceToDevice, s));
   p->occupied[slot] = 1;
-  p->pending = true;
-  p->pending_stream = s;
+  p->fly.on(s);
   return FLEET_OK;
 }
 
@@ -2492,18 +2493,14 @@ int fleet_pool_update(fleet_pool* p, const int32_t* picks, int K, const double* 
   DEVICE_SCOPE(c);
   int rc = pool_update_args(p, picks, K, "fleet_pool_update");
   if (rc) return rc;
-  if (out_len) *out_len = p->len;
-  if (cap < p->len) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu", cap, p->len);
-  if ((rc = pool_settle(p, c->stream, true))) return rc;
-  // outputs in the pool's spare row and over the state (window coordinates: shifted back by
-  // the window's start, as the kernel addresses them by the whole upload's group index)
-  uint8_t* d_out = p->d_rows + (size_t)p->slots * p->pitch;
-  if ((rc = pool_fold(p, picks, K, dampen, c->stream, d_out - p->col0, merged_f32 ? p->d_state - 3 * p->gb : nullptr)))
+  if (out_len) *out_len = p->w.len;
+  if (cap < p->w.len) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu", cap, p->w.len);
+  if ((rc = settle(c, &p->fly, c->stream, true))) return rc;
+  uint8_t* d_out = p->d_rows + (size_t)p->slots * p->pitch;  // the pool's spare row; the fp32 go over the state
+  if ((rc = pool_fold(p, picks, K, dampen, c->stream, d_out - p->w.col0,
+                      merged_f32 ? p->d_state - 3 * p->w.gb : nullptr)))
     return rc;
-  const size_t v0 = 3 * p->gb, v1 = std::max(v0, std::min(p->n, 3 * p->ge));
-  if (p->width) HIP_TRY(c, hipMemcpyAsync(merged + p->col0, d_out, p->width, hipMemcpyDeviceToHost, c->stream));
-  if (merged_f32 && v1 > v0)
-    HIP_TRY(c, hipMemcpyAsync(merged_f32 + v0, p->d_state, sizeof(float) * (v1 - v0), hipMemcpyDeviceToHost, c->stream));
+  if ((rc = window_read_back(c, p->w, d_out, p->d_state, merged, merged_f32, c->stream))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return pool_verdict(p, picks, K);  // on an error the outputs are not meaningful; the pool is as before
 }
@@ -2517,10 +2514,10 @@ int fleet_pool_update_device(fleet_pool* p, const int32_t* picks, int K, const d
   int rc = pool_update_args(p, picks, K, "fleet_pool_update_device");
   if (rc) return rc;
   hipStream_t s = pick(c, stream);
-  if ((rc = pool_settle(p, s, false))) return rc;
+  if ((rc = settle(c, &p->fly, s, false))) return rc;
   if ((rc = pool_fold(p, picks, K, dampen, s, (uint8_t*)d_merged, (float*)d_merged_f32))) return rc;
   HIP_TRY(c, hipStreamSynchronize(s));
-  p->pending = false;
+  p->fly.done();
   return pool_verdict(p, picks, K);
 }
 

@@ -88,40 +88,40 @@ hipError_t launch_update_encode(const uint8_t* uploads, size_t pitch, int M, con
                                 int* d_err, const float* values, size_t vpitch, uint8_t* enc_out, hipStream_t s);
 hipError_t launch_encode_f32(const float* values, int64_t n, size_t vpitch, int rows, uint8_t* out, size_t pitch,
                              hipStream_t s);
-// Streaming aggregation (acc_kernels.hip): one upload's step of the chain over the
-// groups [g_begin, g_end) -- row, st_in, st_out hold that window alone (group g at byte
-// 16 (g - g_begin), value 3 (g - g_begin)); st_in is not read when `first`; d_hfirst
-// (n_headers codes) is written by the first step and compared by the later ones -- and
-// the merged gradient from the state and the last accepted row (merged / merged_f32
-// addressed by the whole upload's group index, as launch_update's).
+// Streaming aggregation (acc_kernels.hip). Every launcher works on a window of an
+// upload's groups: rows and state hold the groups [g_begin, g_end) alone (group g at byte
+// 16 (g - g_begin), value 3 (g - g_begin)), while merged / merged_f32 are addressed by
+// the whole upload's group index, as launch_update's. d_hfirst (n_headers codes) is
+// written by a batch's first step and compared by the later ones.
+struct AccWindow {
+  int64_t n_up, g_begin, g_end;
+  const int32_t* d_hdr_block;
+  int32_t* d_hfirst;
+};
+// One upload's step of the chain (st_in is not read when `first`), and the merged
+// gradient from the state and the last accepted row.
 hipError_t launch_acc_push(const uint8_t* row, const float* st_in, float* st_out, int first, double dampen,
-                           int64_t n_up, int64_t g_begin, int64_t g_end, const int32_t* d_hdr_block,
-                           int32_t* d_hfirst, int* d_err, hipStream_t s);
-hipError_t launch_acc_finish(const uint8_t* last_row, const float* st, double inv, int64_t n_up, int64_t g_begin,
-                             int64_t g_end, const int32_t* d_hdr_block, uint8_t* merged, float* merged_f32,
-                             hipStream_t s);
+                           const AccWindow& w, int* d_err, hipStream_t s);
+hipError_t launch_acc_finish(const uint8_t* last_row, const float* st, double inv, const AccWindow& w, uint8_t* merged,
+                             float* merged_f32, hipStream_t s);
 // A burst of K <= kAccBurst uploads folded by one launch (k_acc_push_many): rows 0..K-2
-// at rows + k * pitch, row K-1 at last_row, all in window coordinates; dampen holds K
-// factors (host memory: they travel in the kernel arguments). `first`: row 0 is the
-// batch's first upload (st_in unread, hfirst[] written). st_in may equal st_out. With
-// `finish` the launch ends in k_acc_finish's epilogue (inv = 1 / uploads of the batch;
-// merged / merged_f32 in whole-upload addressing) and stores no state.
+// at rows + k * pitch, row K-1 at last_row; dampen holds K factors (host memory: they
+// travel in the kernel arguments). `first`: row 0 is the batch's first upload (st_in
+// unread, hfirst[] written). st_in may equal st_out. With `finish` the launch ends in
+// the finish epilogue (inv = 1 / uploads of the batch) and stores no state.
 constexpr int kAccBurst = 64;
 hipError_t launch_acc_push_many(const uint8_t* rows, size_t pitch, const uint8_t* last_row, const float* st_in,
                                 float* st_out, int first, int K, const double* dampen, bool finish, double inv,
-                                int64_t n_up, int64_t g_begin, int64_t g_end, const int32_t* d_hdr_block,
-                                int32_t* d_hfirst, int* d_err, uint8_t* merged, float* merged_f32, hipStream_t s);
+                                const AccWindow& w, int* d_err, uint8_t* merged, float* merged_f32, hipStream_t s);
 // The upload pool's fold (k_pool_fold): K <= kAccBurst picked rows of a pool of resident
-// uploads, pick k at pool + slots[k] * pitch (window coordinates, pitch a multiple of 16);
-// slots and dampen are host arrays of K entries (they travel in the kernel arguments).
-// `first`: pick 0 is the update's first (st unread, hfirst[] written); without `finish`
-// the launch stores the running value in st, with it the launch ends in the finish
-// epilogue (inv = 1 / picks of the whole update; merged / merged_f32 in whole-upload
-// addressing) and stores no state. d_status: one error word per slot of the pool.
+// uploads, pick k at pool + slots[k] * pitch (pitch a multiple of 16); slots and dampen
+// are host arrays of K entries. `first`: pick 0 is the update's first (st unread,
+// hfirst[] written); without `finish` the launch stores the running value in st, with it
+// the launch ends in the finish epilogue (inv = 1 / picks of the whole update) and
+// stores no state. d_status: one error word per slot of the pool.
 hipError_t launch_pool_fold(const uint8_t* pool, size_t pitch, const int32_t* slots, float* st, int first, int K,
-                            const double* dampen, bool finish, double inv, int64_t n_up, int64_t g_begin, int64_t g_end,
-                            const int32_t* d_hdr_block, int32_t* d_hfirst, int* d_status, uint8_t* merged,
-                            float* merged_f32, hipStream_t s);
+                            const double* dampen, bool finish, double inv, const AccWindow& w, int* d_status,
+                            uint8_t* merged, float* merged_f32, hipStream_t s);
 hipError_t launch_encode_minibatch(const float* images, int64_t n_images, int F, const int32_t* labels,
                                    const int32_t* idx, int B, const float* teacher, int NL, const float header[7],
                                    uint8_t* out, int* err, hipStream_t s);
