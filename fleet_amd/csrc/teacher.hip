@@ -14,7 +14,8 @@
 // network::forward (commonLib/cppNN/network.h:523-585) zeroes every node, copies
 // the sample into I1 and, layer by layer, activates the layer (bias + activation)
 // and accumulates it into the next one. Every sum below runs in the reference's
-// order, one binary32 rounding per multiply and per add (no contraction):
+// order, one binary32 rounding per multiply and per add (no contraction); mojo_sum,
+// mojo_add, mojo_div ... of teacher_math.h also give a NaN the reference's x86 bits:
 //   convolution k x k (layer.h:805-872, core_math.h dotsum_unwrapped_NxN): per
 //     output, input channel k outer and kernel tap i = row*5 + col inner, one
 //     running sum from 0;
@@ -73,9 +74,12 @@ __global__ void __launch_bounds__(256) k_teacher_forward(const float* __restrict
   for (int o = t; o < kMaps1 * kC1 * kC1; o += 256) {
     const int map = o / (kC1 * kC1), p = o % (kC1 * kC1), y = p / kC1, x = p % kC1;
     const float* wm = w + kW1 + map * 25;
-    float acc = 0.0f;
+    const float acc = mojo_sum([&](auto mac) {
+      float a = 0.0f;
 #pragma unroll
-    for (int i = 0; i < 25; ++i) acc = acc + s_in[(y + i / 5) * kIn + x + i % 5] * wm[i];
+      for (int i = 0; i < 25; ++i) a = mac(a, s_in[(y + i / 5) * kIn + x + i % 5], wm[i]);
+      return a;
+    });
     s_c1[o] = mojo_elu(acc, b[kB1 + map]);
   }
   __syncthreads();
@@ -93,9 +97,12 @@ __global__ void __launch_bounds__(256) k_teacher_forward(const float* __restrict
   // C2i: 1x1 over 8 input channels, then bias + elu
   for (int o = t; o < kMaps2i * kP1 * kP1; o += 256) {
     const int map = o / (kP1 * kP1), p = o % (kP1 * kP1);
-    float acc = 0.0f;
+    const float acc = mojo_sum([&](auto mac) {
+      float a = 0.0f;
 #pragma unroll
-    for (int k = 0; k < kMaps1; ++k) acc = acc + s_p1[k * kP1 * kP1 + p] * w[kW2i + map + k * kMaps2i];
+      for (int k = 0; k < kMaps1; ++k) a = mac(a, s_p1[k * kP1 * kP1 + p], w[kW2i + map + k * kMaps2i]);
+      return a;
+    });
     s_c2i[o] = mojo_elu(acc, b[kB2i + map]);
   }
   __syncthreads();
@@ -103,13 +110,16 @@ __global__ void __launch_bounds__(256) k_teacher_forward(const float* __restrict
   // C2: 5x5 over 16 input channels (channel outer, tap inner), then bias + elu
   for (int o = t; o < kMaps2 * kC2 * kC2; o += 256) {
     const int map = o / (kC2 * kC2), p = o % (kC2 * kC2), y = p / kC2, x = p % kC2;
-    float acc = 0.0f;
-    for (int k = 0; k < kMaps2i; ++k) {
-      const float* wm = w + kW2 + (int64_t)(k * kMaps2 + map) * 25;
-      const float* src = s_c2i + k * kP1 * kP1;
+    const float acc = mojo_sum([&](auto mac) {
+      float a = 0.0f;
+      for (int k = 0; k < kMaps2i; ++k) {
+        const float* wm = w + kW2 + (int64_t)(k * kMaps2 + map) * 25;
+        const float* src = s_c2i + k * kP1 * kP1;
 #pragma unroll
-      for (int i = 0; i < 25; ++i) acc = acc + src[(y + i / 5) * kP1 + x + i % 5] * wm[i];
-    }
+        for (int i = 0; i < 25; ++i) a = mac(a, src[(y + i / 5) * kP1 + x + i % 5], wm[i]);
+      }
+      return a;
+    });
     s_c2[o] = mojo_elu(acc, b[kB2 + map]);
   }
   __syncthreads();
@@ -127,9 +137,12 @@ __global__ void __launch_bounds__(256) k_teacher_forward(const float* __restrict
   // FC2: node[j] = 0 + dot(P2, W row j)
   if (t < kClasses) {
     const float* wr = w + kWfc + (int64_t)t * kFcIn;
-    float v = 0.0f;
-    for (int i = 0; i < kFcIn; ++i) v = v + s_p2[i] * wr[i];
-    s_fc[t] = 0.0f + v;
+    const float v = mojo_sum([&](auto mac) {
+      float a = 0.0f;
+      for (int i = 0; i < kFcIn; ++i) a = mac(a, s_p2[i], wr[i]);
+      return a;
+    });
+    s_fc[t] = mojo_add(0.0f, v);
   }
   __syncthreads();
 
@@ -141,12 +154,13 @@ __global__ void __launch_bounds__(256) k_teacher_forward(const float* __restrict
     float mx = in[0];
 #pragma unroll
     for (int j = 1; j < kClasses; ++j)
-      if (in[j] > mx) mx = in[j] / temperature;
+      if (in[j] > mx) mx = mojo_div(in[j], temperature);
     float denom = 0.0f;
 #pragma unroll
-    for (int j = 0; j < kClasses; ++j) denom = denom + glibc_expf(in[j] / temperature - mx);
+    for (int j = 0; j < kClasses; ++j) denom = mojo_add(denom, mojo_expf(mojo_sub(mojo_div(in[j], temperature), mx)));
 #pragma unroll
-    for (int j = 0; j < kClasses; ++j) probs[(int64_t)blockIdx.x * kClasses + j] = glibc_expf(in[j] / temperature - mx) / denom;
+    for (int j = 0; j < kClasses; ++j)
+      probs[(int64_t)blockIdx.x * kClasses + j] = mojo_div(mojo_expf(mojo_sub(mojo_div(in[j], temperature), mx)), denom);
   }
 }
 

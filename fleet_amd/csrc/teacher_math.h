@@ -18,8 +18,10 @@
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #define FLEET_TM __host__ __device__ __forceinline__
+#define FLEET_TM_MEMBER __host__ __device__ __forceinline__
 #else
 #define FLEET_TM static inline __attribute__((always_inline))
+#define FLEET_TM_MEMBER inline __attribute__((always_inline))
 #endif
 
 namespace fleet {
@@ -64,10 +66,54 @@ FLEET_TM float glibc_expf(float x) {
   return (float)(y * s);
 }
 
+// NaN results as the reference's x86 SSE build produces them: r = a OP b, where a
+// NaN operand propagates quieted (the first one winning) and an invalid operation
+// on non-NaN operands (0*inf, inf-inf, inf/inf, 0/0) gives the default NaN
+// 0xFFC00000. The GPU's own default NaN is 0x7FC00000, so the device applies the
+// rule explicitly, as k_descent's x86_nan does; on the host (x86) the hardware has
+// already done it and this is the identity, so tests/native/check_teacher.cpp
+// checks the same code against the reference's recorded bits. Without NaN among
+// weights, biases and pixels every NaN of the forward is then 0xFFC00000, as in the
+// reference; with NaN inputs the reference's result depends on its compiler's
+// operand order per instruction, which is not restated.
+FLEET_TM float teacher_x86_nan(float a, float b, float r) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (r == r) return r;
+  if (a != a) return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, a) | 0x00400000u);
+  if (b != b) return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, b) | 0x00400000u);
+  return __builtin_bit_cast(float, 0xFFC00000u);
+#else
+  (void)a, (void)b;
+  return r;
+#endif
+}
+FLEET_TM float mojo_add(float a, float b) { return teacher_x86_nan(a, b, a + b); }
+FLEET_TM float mojo_sub(float a, float b) { return teacher_x86_nan(a, b, a - b); }
+FLEET_TM float mojo_mul(float a, float b) { return teacher_x86_nan(a, b, a * b); }
+FLEET_TM float mojo_div(float a, float b) { return teacher_x86_nan(a, b, a / b); }
+// std::exp(float) of a value that may be NaN or +-inf (expf's own x + x)
+FLEET_TM float mojo_expf(float x) { return teacher_x86_nan(x, x, glibc_expf(x)); }
+
+// One running sum of the forward, acc = acc + a*b per term. NaN is absorbing in + and *,
+// so a sum that comes out no NaN met none on the way and the plain operations gave the
+// reference's bits; only a sum that comes out NaN is repeated with the x86 rule per
+// operation (mojo_sum: `sum(mac)` runs the layer's loop nest with the given step).
+struct MacPlain {
+  FLEET_TM_MEMBER float operator()(float acc, float a, float b) const { return acc + a * b; }
+};
+struct MacX86 {
+  FLEET_TM_MEMBER float operator()(float acc, float a, float b) const { return mojo_add(acc, mojo_mul(a, b)); }
+};
+template <class Sum>
+FLEET_TM float mojo_sum(Sum sum) {
+  const float acc = sum(MacPlain{});
+  return acc == acc ? acc : sum(MacX86{});
+}
+
 // activation.h:161-176 elu::fc on one value: the bias added, then
-// 0.1f*(exp(v) - 1) for v < 0
+// 0.1f*(exp(v) - 1) for v < 0 (v is then no NaN, and exp(v) - 1 is finite)
 FLEET_TM float mojo_elu(float x, float bias) {
-  const float v = x + bias;
+  const float v = mojo_add(x, bias);
   return v < 0.0f ? 0.1f * (glibc_expf(v) - 1.0f) : v;
 }
 
