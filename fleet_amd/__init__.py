@@ -128,6 +128,15 @@ def lib() -> C.CDLL:
         "fleet_pool_update": (i32, [vp, vp, i32, vp, vp, sz, szp, vp]),
         "fleet_pool_update_device": (i32, [vp, vp, i32, vp, vp, vp, vp]),
         "fleet_pool_slot_status": (i32, [vp, i32]),
+        "fleet_kledger_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
+        "fleet_kledger_destroy": (None, [vp]),
+        "fleet_kledger_workers": (i32, [vp]),
+        "fleet_kledger_has": (i32, [vp, i32]),
+        "fleet_kledger_epoch": (i32, [vp, i32, C.POINTER(i32)]),
+        "fleet_kledger_forget": (i32, [vp, i32]),
+        "fleet_kledger_read": (i32, [vp, i32, vp, sz]),
+        "fleet_kledger_update": (i32, [vp, vp, i32, vp, vp, vp, C.c_double, vp, sz, szp, vp, vp, vp, vp]),
+        "fleet_kledger_update_device": (i32, [vp, vp, i32, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp]),
         "fleet_update_kernel": (C.c_char_p, [sz]),
         "fleet_update_plan_grid": (i32, [sz, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -1077,6 +1086,112 @@ class Pool:
                                                      merged_u8.data_ptr(),
                                                      merged_f32.data_ptr() if merged_f32 is not None else None,
                                                      _stream(stream)), pk)
+
+    def ledger(self, workers: int, max_store: Optional[int] = None) -> "Ledger":
+        """A Kardam ledger (fleet_kledger) over this pool: ``workers`` worker ids, at most
+        ``max_store`` (default: the pool's slots) picks of one update that store a row."""
+        return Ledger(self, workers, self.slots if max_store is None else max_store)
+
+
+class Ledger:
+    """Kardam's ``grads`` map kept in HBM beside an upload pool (fleet_kledger,
+    include/fleet_codec.h; Kardam.java:56-71): ``update`` / ``update_device`` are the pool's
+    plus ``setGrad`` for every pick, in pick order -- the gradient norm, the norm of the
+    difference to the worker's previous gradient and the ``setGrad`` result per pick -- from
+    the one pass over the picked rows that produces the merged bytes. When an update raises
+    ``Base64Error`` or ``LayoutError`` the ledger and the pool are as before and the
+    exception's ``slots`` lists the slots at fault. Close it before its pool."""
+
+    def __init__(self, pool: Pool, workers: int, max_store: int):
+        self.pool = pool
+        self._L = pool._L
+        self._h = None
+        h = C.c_void_p()
+        pool.codec._check(self._L.fleet_kledger_create(pool._h, int(workers), int(max_store), C.byref(h)))
+        self._h = h
+        self.workers = int(self._L.fleet_kledger_workers(h))
+        self.max_store = int(max_store)
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.pool, "_h", None) and getattr(self.pool.codec, "_h", None):
+            self._L.fleet_kledger_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _live(self):
+        """The handle, while the ledger and its pool are open."""
+        if not getattr(self, "_h", None) or not getattr(self.pool, "_h", None):
+            raise ValueError("the ledger or its pool is closed")
+        return self._h
+
+    def has(self, worker: int) -> bool:
+        v = self._L.fleet_kledger_has(self._live(), int(worker))
+        if v < 0:
+            raise FleetError(v, f"worker {worker} outside [0, {self.workers})")
+        return bool(v)
+
+    def epoch(self, worker: int) -> int:
+        """The epoch recorded with the worker's gradient (the worker must be in the ledger)."""
+        e = C.c_int(0)
+        self.pool.codec._check(self._L.fleet_kledger_epoch(self._live(), int(worker), C.byref(e)))
+        return int(e.value)
+
+    def forget(self, worker: int) -> None:
+        self.pool.codec._check(self._L.fleet_kledger_forget(self._live(), int(worker)))
+
+    def read(self, worker: int):
+        """The worker's gradient: float32 in upload coordinates, header slots 0."""
+        g = np.zeros(b64_count(self.pool.length), np.float32)
+        self.pool.codec._check(self._L.fleet_kledger_read(self._live(), int(worker), g.ctypes.data, len(g)))
+        return g
+
+    def _args(self, picks, dampens, workers, epochs):
+        pk, d = Pool._pick_args(picks, dampens)
+        w = np.ascontiguousarray(workers, dtype=np.int32)
+        e = np.ascontiguousarray(epochs, dtype=np.int32)
+        if len(w) != len(pk) or len(e) != len(pk):
+            raise ValueError("one worker and one epoch per pick")
+        K = len(pk)
+        return pk, d, w, e, np.full(K, np.nan), np.full(K, np.nan), np.zeros(K, np.uint8)
+
+    def update(self, picks, dampens, workers, epochs, lr: float, want_f32: bool = False):
+        """``Pool.update`` over ``picks`` plus ``setGrad(workers[k], g_k * lr, epochs[k])`` for
+        each pick (``workers[k] < 0``: none for that pick). Returns ``(merged, f32 or None,
+        norm_g, norm_diff, set)``; a norm that ``setGrad`` does not compute is NaN."""
+        pk, d, w, e, ng, nd, st = self._args(picks, dampens, workers, epochs)
+        length = self.pool.length
+        out = np.zeros(length + 16, np.uint8)
+        n = C.c_size_t(0)
+        f32 = np.zeros(b64_count(length) + 1, np.float32) if want_f32 else None
+        self.pool._check(self._L.fleet_kledger_update(
+            self._live(), pk.ctypes.data, len(pk), d.ctypes.data, w.ctypes.data, e.ctypes.data, float(lr), out.ctypes.data,
+            len(out), C.byref(n), f32.ctypes.data if want_f32 else None, ng.ctypes.data, nd.ctypes.data,
+            st.ctypes.data), pk)
+        return (out[: n.value].tobytes(), f32[: b64_count(length)].copy() if want_f32 else None, ng, nd,
+                st.astype(bool))
+
+    def update_device(self, picks, dampens, workers, epochs, lr: float, merged_u8, merged_f32=None, stream=None):
+        """The device form (``Pool.update_device``'s tensors). Returns ``(norm_g, norm_diff, set)``."""
+        pk, d, w, e, ng, nd, st = self._args(picks, dampens, workers, epochs)
+        if merged_u8.numel() < 16 * self.pool.groups or (
+                merged_f32 is not None and merged_f32.numel() < b64_count(self.pool.length)):
+            raise ValueError("merged tensors smaller than the upload's groups")
+        self.pool._check(self._L.fleet_kledger_update_device(
+            self._live(), pk.ctypes.data, len(pk), d.ctypes.data, w.ctypes.data, e.ctypes.data, float(lr),
+            merged_u8.data_ptr(), merged_f32.data_ptr() if merged_f32 is not None else None, ng.ctypes.data,
+            nd.ctypes.data, st.ctypes.data, _stream(stream)), pk)
+        return ng, nd, st.astype(bool)
 
 
 def update_multi(codecs: Sequence["Codec"], uploads: Sequence, dampen: Sequence[float], want_f32: bool = False):

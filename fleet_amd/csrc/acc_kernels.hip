@@ -1,7 +1,8 @@
 // fleet_amd/csrc/acc_kernels.hip -- streaming aggregation: one upload folded into a
 // resident sum per launch (k_acc_push), the merged gradient from the sum (k_acc_finish),
-// a burst of uploads per launch (k_acc_push_many), and the upload pool's fold over picked
-// resident rows (k_pool_fold).
+// a burst of uploads per launch (k_acc_push_many), the upload pool's fold over picked
+// resident rows (k_pool_fold), and that fold with Kardam's side outputs of the picks
+// (k_pool_fold_kd, k_pool_kd_reduce: the Kardam ledger).
 //
 // CppNNUpdater.update is entered once per upload and only buffers it until M have
 // arrived (CppNNUpdater.java:383-391); the chain it then runs over the picked uploads
@@ -170,6 +171,55 @@ __device__ __forceinline__ void acc_lane_step(const AccShared& sh, const uint8_t
   q_stage_d16x<3>(y, y0, &sh.dtab, sh.tab.var);
   dampen_stage<3>(y, d);
   q_stage_d16x<3>(p, y, &sh.dtab, sh.tab.var);
+  if (is_first) {
+    A[0] = p[0], A[1] = p[1], A[2] = p[2];
+  } else {
+    const float sm[3] = {A[0] + p[0], A[1] + p[1], A[2] + p[2]};
+    q_stage_d16x<3>(A, sm, &sh.dtab, sh.tab.var);
+  }
+}
+
+// The step in two pieces for k_pool_fold_kd, which takes p between them: the upload's
+// dampened value p (acc_lane_value: acc_lane_step up to its last stage, line for line) and
+// its add into the running value (acc_lane_add). A copy, not a split of acc_lane_step:
+// building that from the two pieces changed k_pool_fold's register allocation and added
+// 29 instructions to it, and the sharing there already stops where it costs (the file's
+// header).
+template <bool FINISH>
+__device__ __forceinline__ void acc_lane_value(const AccShared& sh, const uint8_t* src, bool live, uint32_t need,
+                                               bool wave_keep, uint32_t hbits, uint32_t kbits, int h0, bool is_first,
+                                               double d, int32_t* hfirst, int32_t (&href)[3], int32_t (&keepc)[3],
+                                               float (&p)[3], uint32_t& bad, uint32_t& layout_bad) {
+  uint4 w = uint4{0u, 0u, 0u, 0u};
+  if (live) w = *reinterpret_cast<const uint4*>(src);
+  int32_t codes[3];
+  if (need == 0xffffu) bad |= live ? b64_decode_group_full(w, &sh.tab, codes) : 0u;
+  else bad |= live ? (b64_decode_group(w, &sh.tab, codes) & need) : 0u;
+  if (!live) codes[0] = codes[1] = codes[2] = 0;
+  if (wave_keep) {
+    int hi = h0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      if ((hbits >> i) & 1u) {
+        if (is_first) {
+          href[i] = codes[i];
+          if (live) hfirst[hi] = codes[i];
+        } else if (live) {
+          layout_bad |= (uint32_t)(codes[i] != href[i]);
+        }
+        ++hi;
+      }
+      if (FINISH) keepc[i] = codes[i];
+      if ((kbits >> i) & 1u) codes[i] = 0;
+    }
+  }
+  float y0[3], y[3];
+  dec_stage_d16<3>(y0, codes, &sh.dtab);
+  q_stage_d16x<3>(y, y0, &sh.dtab, sh.tab.var);
+  dampen_stage<3>(y, d);
+  q_stage_d16x<3>(p, y, &sh.dtab, sh.tab.var);
+}
+__device__ __forceinline__ void acc_lane_add(const AccShared& sh, bool is_first, const float (&p)[3], float (&A)[3]) {
   if (is_first) {
     A[0] = p[0], A[1] = p[1], A[2] = p[2];
   } else {
@@ -367,6 +417,175 @@ __global__ void __launch_bounds__(kAccNT) k_pool_fold(const uint8_t* pool, size_
   }
 }
 
+// Kardam's side outputs of the pool's fold (the ledger, fleet_kledger_update*): pick k's
+// previous row and output row in the slab of fp32 rows (-1: none) and its mode, by value
+// beside the slots and the factors, so every test on them stays scalar.
+constexpr int kKdNorm = 1, kKdDiff = 2, kKdStore = 4;
+struct PoolKdRows {
+  int32_t prev[kAccBurst];
+  int32_t out[kAccBurst];
+};
+struct PoolKdModes {
+  uint8_t m[kAccBurst];
+};
+
+// k_pool_fold with, per pick k, what kardam_lane_step does in the batch stream kernel
+// (CppNNUpdater.java:478, Kardam.java:56-71), on the pick's p between the dampen stage
+// and the add: G = Q(f32(f64(p) * lr)), sg = sum (double)(G * G) over the flat slots
+// (neither header slots nor at or past the walk's end, where G is 0), with a previous row
+// D = Q(G - prev) and sd = sum (double)(D * D), and for a storing pick G as the lane's 12
+// bytes of its output row (upload coordinates; a row holds whole groups, so a ragged last
+// group is stored whole, its tail 0). A pick's previous row may be the output row of an
+// earlier pick of the launch (a worker picked twice): the same lane stored those 12 bytes,
+// and the load follows the store in program order, so `slab` is not __restrict__ and the
+// previous row is loaded inside its own pick's step, not a pick ahead.
+// The norms: per pick the wave's sg / sd are reduced over the wave two picks at a time
+// (quad_sum_f64, a last even pick by pair_sum_f64<64>) and added into the wave's own LDS
+// slots kdp[wave][pick][2] across the grid-stride iterations; after them the wave stores
+// its 2 K sums once, partials[(k * waves + w) * 2 + {0, 1}], w = 4 blockIdx.x + wave, and
+// k_pool_kd_reduce adds the waves in a fixed order. No floating-point atomics: the same
+// bits for the same inputs and grid. The ledger's pool covers the whole upload (g_begin =
+// 0), so the lane's slots are 3 g .. 3 g + 2 in the row.
+// merged, merged_f32, the state and status[] are k_pool_fold's: the loop below is that
+// kernel's with the step in its two pieces.
+template <bool FINISH>
+__global__ void __launch_bounds__(kAccNT) k_pool_fold_kd(const uint8_t* pool, size_t pitch, PoolPicks picks, float* st,
+                                                         int first, int K, AccDampen dampen, double inv, int64_t n_up,
+                                                         int64_t g_begin, int64_t g_end,
+                                                         const int32_t* __restrict__ hdr_block, int32_t* hfirst,
+                                                         int* __restrict__ status, uint8_t* merged, float* merged_f32,
+                                                         PoolKdRows rows, PoolKdModes modes, double lr, float* slab,
+                                                         size_t vpitch, double* __restrict__ partials) {
+  __shared__ AccShared sh;
+  __shared__ double kdp[kAccNT / 64][kAccBurst][2];
+  for (int i = threadIdx.x; i < (kAccNT / 64) * kAccBurst * 2; i += kAccNT) (&kdp[0][0][0])[i] = 0.0;
+  const AccHdr H = acc_block_open(sh, hdr_block);  // (its barrier covers the zeroes)
+  const int64_t ng = g_end - g_begin;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint64_t bad_picks = 0, layout_picks = 0;
+  for (int64_t base = (int64_t)blockIdx.x * kAccNT; base < ng; base += (int64_t)gridDim.x * kAccNT) {
+    const int64_t gl = base + threadIdx.x;
+    const bool live = gl < ng;
+    const int64_t gs = live ? gl : 0, g = g_begin + gs;
+    float A[3] = {0.f, 0.f, 0.f};
+    if (!first && live) {
+      const f3u a = *reinterpret_cast<const f3u*>(st + 3 * gs);
+      A[0] = a.x, A[1] = a.y, A[2] = a.z;
+    }
+    const uint32_t need = needed_chars_mask((int)min<int64_t>(3, max<int64_t>(0, n_up - 3 * g)));
+    int h0;
+    const uint32_t hbits = acc_header_bits(sh, H.hdr, H.n_hdr, 3 * g, &h0);
+    const uint32_t kbits = keep_bits<3>(hbits, true, 3 * g, H.walk_end);
+    const bool wave_keep = __ballot(kbits != 0) != 0;
+    const uint32_t flat = live ? ~kbits & 7u : 0u;
+    int32_t href[3] = {0, 0, 0}, keepc[3] = {0, 0, 0};
+    if (wave_keep && !first) {
+      int hi = h0;
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        if ((hbits >> i) & 1u) href[i] = hfirst[hi++];
+    }
+    double sg0 = 0.0, sd0 = 0.0;  // an even pick's sums, held for the pair
+    int mode0 = 0;
+    for (int k = 0; k < K; ++k) {
+      const int mode = modes.m[k];
+      float pv[3] = {0.f, 0.f, 0.f};
+      if ((mode & kKdDiff) && live) {
+        const f3u t = *reinterpret_cast<const f3u*>(slab + (size_t)rows.prev[k] * vpitch + 3 * gs);
+        pv[0] = t.x, pv[1] = t.y, pv[2] = t.z;
+      }
+      const uint8_t* src = pool + (size_t)picks.slot[k] * pitch + 16 * gs;
+      uint32_t bad = 0, layout_bad = 0;
+      float p[3];
+      acc_lane_value<FINISH>(sh, src, live, need, wave_keep, hbits, kbits, h0, first && k == 0, dampen.d[k], hfirst, href,
+                             keepc, p, bad, layout_bad);
+      bad_picks |= (uint64_t)(bad != 0) << k;
+      layout_picks |= (uint64_t)(layout_bad != 0) << k;
+      double sg = 0.0, sd = 0.0;
+      if (mode & kKdNorm) {
+        float rg[3] = {p[0], p[1], p[2]}, G[3];
+        dampen_stage<3>(rg, lr);
+        q_stage_d16x<3>(G, rg, &sh.dtab, sh.tab.var);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          G[i] = ((flat >> i) & 1u) ? G[i] : 0.0f;
+          sg += (double)(G[i] * G[i]);
+        }
+        if (mode & kKdDiff) {
+          float dv[3], D[3];
+#pragma unroll
+          for (int i = 0; i < 3; ++i) dv[i] = ((flat >> i) & 1u) ? G[i] - pv[i] : 0.0f;
+          q_stage_d16x<3>(D, dv, &sh.dtab, sh.tab.var);
+#pragma unroll
+          for (int i = 0; i < 3; ++i) sd += (double)(D[i] * D[i]);
+        }
+        if ((mode & kKdStore) && live)
+          *reinterpret_cast<f3u*>(slab + (size_t)rows.out[k] * vpitch + 3 * gs) = f3u{G[0], G[1], G[2]};
+      }
+      acc_lane_add(sh, first && k == 0, p, A);
+      if (k & 1) {
+        if ((mode | mode0) & kKdNorm) {
+          const double s = quad_sum_f64(sg0, sd0, sg, sd);
+          if ((lane & 15) == 15)  // rows 0..3: (k - 1, g), (k, g), (k - 1, d), (k, d)
+            kdp[wave][k - 1 + ((lane >> 4) & 1)][lane >> 5] += s;
+        }
+      } else if (k + 1 == K) {
+        if (mode & kKdNorm) {
+          const double s = pair_sum_f64<64>(sg, sd);
+          if ((lane & 31) == 31) kdp[wave][k][lane >> 5] += s;
+        }
+      } else {
+        sg0 = sg, sd0 = sd, mode0 = mode;
+      }
+    }
+    if (!FINISH) {
+      if (live) *reinterpret_cast<f3u*>(st + 3 * gs) = f3u{A[0], A[1], A[2]};
+    } else if (live) {
+      acc_lane_finish(sh, A, keepc, kbits, inv, n_up, g, merged, merged_f32);
+    }
+  }
+  if (bad_picks | layout_picks) {
+    for (int k = 0; k < K; ++k) {
+      const int e = (((bad_picks >> k) & 1) ? FLEET_ERRBIT_BASE64 : 0) | (((layout_picks >> k) & 1) ? FLEET_ERRBIT_LAYOUT : 0);
+      if (e) atomicOr(status + picks.slot[k], e);
+    }
+  }
+  __syncthreads();  // the wave's slots were written by four (or two) of its lanes
+  if (lane < K) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    const size_t w = (size_t)blockIdx.x * (kAccNT / 64) + wave, waves = (size_t)gridDim.x * (kAccNT / 64);
+    reinterpret_cast<d2*>(partials)[(size_t)lane * waves + w] = d2{kdp[wave][lane][0], kdp[wave][lane][1]};
+  }
+}
+
+// Pick k's 2 sums from the waves' partials of one k_pool_fold_kd launch, in a fixed
+// order: a lane adds every 256th wave's pair in turn, the wave folds by DPP lane moves
+// (group_sum_f64), lane 0 adds the block's four waves in order. sums[2 k + {0, 1}].
+__global__ void __launch_bounds__(kAccNT) k_pool_kd_reduce(const double* __restrict__ partials, int64_t waves,
+                                                           double* __restrict__ sums) {
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  __shared__ double red[2][kAccNT / 64];
+  const int k = blockIdx.x;
+  const d2* p = reinterpret_cast<const d2*>(partials) + (size_t)k * waves;
+  d2 v = d2{0.0, 0.0};
+  for (int64_t w = threadIdx.x; w < waves; w += kAccNT) v += p[w];
+  const double a = group_sum_f64<64>(v.x), b = group_sum_f64<64>(v.y);  // valid in lane 63
+  if ((threadIdx.x & 63) == 63) {
+    red[0][threadIdx.x / 64] = a;
+    red[1][threadIdx.x / 64] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double sa = 0.0, sb = 0.0;
+    for (int i = 0; i < kAccNT / 64; ++i) {
+      sa += red[0][i];
+      sb += red[1][i];
+    }
+    sums[2 * k] = sa;
+    sums[2 * k + 1] = sb;
+  }
+}
+
 // Element-wise kernels: a grid of whole blocks per CU (8 x 256 lanes fill a CU's wave
 // slots), striding over the groups, so the tables are copied into LDS once per block.
 static unsigned acc_grid(int64_t groups) {
@@ -434,6 +653,37 @@ hipError_t launch_pool_fold(const uint8_t* pool, size_t pitch, const int32_t* sl
   return acc_launch(finish ? k_pool_fold<true> : k_pool_fold<false>, w, s, pool, pitch, p, st, first, K,
                     acc_dampen(dampen, K), inv, w.n_up, w.g_begin, w.g_end, w.d_hdr_block, w.d_hfirst, d_status, merged,
                     merged_f32);
+}
+
+int64_t pool_kd_partial_doubles(const AccWindow& w) {
+  return (int64_t)acc_grid(std::max<int64_t>(1, w.g_end - w.g_begin)) * (kAccNT / 64) * kAccBurst * 2;
+}
+
+hipError_t launch_pool_fold_kd(const uint8_t* pool, size_t pitch, const int32_t* slots, float* st, int first, int K,
+                               const double* dampen, bool finish, double inv, const AccWindow& w, int* d_status,
+                               uint8_t* merged, float* merged_f32, const PoolKd& kd, hipStream_t s) {
+  if (K <= 0 || K > kAccBurst || w.g_begin != 0 || w.g_end <= 0) return hipErrorInvalidValue;
+  if (!kd.slab || !kd.partials || !kd.sums || kd.vpitch < (size_t)(3 * w.g_end)) return hipErrorInvalidValue;
+  PoolPicks p;
+  PoolKdRows r;
+  PoolKdModes m;
+  for (int k = 0; k < kAccBurst; ++k) {
+    p.slot[k] = k < K ? slots[k] : 0;
+    m.m[k] = k < K ? kd.mode[k] : 0;
+    r.prev[k] = k < K && (m.m[k] & kKdDiff) ? kd.prev[k] : -1;
+    r.out[k] = k < K && (m.m[k] & kKdStore) ? kd.out[k] : -1;
+    // a mode that names no row, or a row outside the slab, never reaches the kernel
+    if ((m.m[k] & (kKdDiff | kKdStore)) && !(m.m[k] & kKdNorm)) return hipErrorInvalidValue;
+    if ((m.m[k] & kKdDiff) && (r.prev[k] < 0 || r.prev[k] >= kd.rows)) return hipErrorInvalidValue;
+    if ((m.m[k] & kKdStore) && (r.out[k] < 0 || r.out[k] >= kd.rows)) return hipErrorInvalidValue;
+  }
+  const unsigned grid = acc_grid(w.g_end - w.g_begin);
+  hipError_t e = acc_launch(finish ? k_pool_fold_kd<true> : k_pool_fold_kd<false>, w, s, pool, pitch, p, st, first, K,
+                            acc_dampen(dampen, K), inv, w.n_up, w.g_begin, w.g_end, w.d_hdr_block, w.d_hfirst,
+                            d_status, merged, merged_f32, r, m, kd.lr, kd.slab, kd.vpitch, kd.partials);
+  if (e != hipSuccess) return e;
+  k_pool_kd_reduce<<<dim3((unsigned)K), dim3(kAccNT), 0, s>>>(kd.partials, (int64_t)grid * (kAccNT / 64), kd.sums);
+  return hipGetLastError();
 }
 
 }  // namespace fleet

@@ -2521,6 +2521,242 @@ int fleet_pool_update_device(fleet_pool* p, const int32_t* picks, int K, const d
   return pool_verdict(p, picks, K);
 }
 
+// --------------------------------------------------------------- Kardam ledger
+
+// Kardam.java's `grads` map (worker -> (g, epoch), Kardam.java:40, 56-71) with every g
+// one fp32 row of a slab in HBM (upload coordinates, header slots 0). An update's picks
+// are resolved against the tables on the host, in pick order, into (mode, prev row, out
+// row) per pick; G always goes to a free row, and the tables change after the slot
+// status came back clean, so a rejected update leaves no trace.
+struct fleet_kledger {
+  fleet_pool* p = nullptr;
+  int workers = 0, max_store = 0, rows = 0;
+  size_t vpitch = 0;           // floats per row: 12 G bytes rounded up to 16
+  float* d_slab = nullptr;
+  double* d_part = nullptr;    // one launch's per-wave partials
+  double* d_sums = nullptr;    // 2 sums per pick of an update (picks are distinct slots)
+  double* h_sums = nullptr;    // pinned
+  std::vector<int32_t> row_of, epoch_of, free_rows;
+  // one update's resolution
+  std::vector<int32_t> t_row, t_epoch, t_free, t_release, k_prev, k_out;
+  std::vector<uint8_t> k_mode, k_set;
+};
+
+namespace {
+
+static void release_kledger(fleet_kledger* l) {
+  for (void* d : {(void*)l->d_slab, (void*)l->d_part, (void*)l->d_sums})
+    if (d) (void)hipFree(d);
+  if (l->h_sums) (void)hipHostFree(l->h_sums);
+  delete l;
+}
+
+static int kledger_worker_arg(const fleet_kledger* l, int worker, const char* what) {
+  if (worker < 0 || worker >= l->workers)
+    return fail(l->p->c, FLEET_ERR_ARG, "%s: worker %d outside [0, %d)", what, worker, l->workers);
+  if (l->row_of[worker] < 0) return fail(l->p->c, FLEET_ERR_ARG, "%s: worker %d is not in the ledger", what, worker);
+  return FLEET_OK;
+}
+
+// Kardam.setGrad's decisions (Kardam.java:56-71) for the picks in order, on copies of the
+// tables; FLEET_ERR_ARG before anything is launched.
+static int kledger_resolve(fleet_kledger* l, int K, const int32_t* worker, const int32_t* epoch, const char* what) {
+  fleet_ctx* c = l->p->c;
+  for (int k = 0; k < K; ++k)
+    if (worker[k] >= l->workers) return fail(c, FLEET_ERR_ARG, "%s: pick %d names worker %d of %d", what, k, worker[k], l->workers);
+  l->t_row = l->row_of, l->t_epoch = l->epoch_of, l->t_free = l->free_rows;
+  l->t_release.clear();
+  l->k_mode.assign((size_t)K, 0), l->k_set.assign((size_t)K, 0);
+  l->k_prev.assign((size_t)K, -1), l->k_out.assign((size_t)K, -1);
+  int stores = 0;
+  for (int k = 0; k < K; ++k) {
+    const int w = worker[k];
+    if (w < 0) continue;  // Kardam does not run for this pick (CppNNUpdater.java:472-474)
+    const int32_t cur = l->t_row[w];
+    if (cur >= 0 && l->t_epoch[w] == epoch[k]) {  // the push is ignored (Kardam.java:59-62)
+      l->k_mode[k] = 1;
+      continue;
+    }
+    if (++stores > l->max_store || l->t_free.empty())
+      return fail(c, FLEET_ERR_ARG, "%s: more than %d picks store a row", what, l->max_store);
+    const int32_t out = l->t_free.back();
+    l->t_free.pop_back();
+    l->k_out[k] = out;
+    l->k_mode[k] = 1 | 4;
+    if (cur >= 0) {  // Kardam.java:63-65
+      l->k_mode[k] |= 2;
+      l->k_prev[k] = cur;
+      l->k_set[k] = 1;
+      l->t_release.push_back(cur);
+    }
+    l->t_row[w] = out, l->t_epoch[w] = epoch[k];
+  }
+  return FLEET_OK;
+}
+
+// pool_fold with the side outputs: every launch's sums land in d_sums[2 k0 ..)
+static int kledger_fold(fleet_kledger* l, const int32_t* picks, int K, const double* dampen, double lr, hipStream_t s,
+                        uint8_t* d_merged, float* d_f32) {
+  fleet_pool* p = l->p;
+  fleet_ctx* c = p->c;
+  constexpr int B = fleet::kAccBurst;
+  HIP_TRY(c, hipMemsetAsync(p->d_status, 0, sizeof(int) * (size_t)p->slots, s));
+  for (int k0 = 0; k0 < K; k0 += B) {
+    const int kc = std::min(B, K - k0);
+    const fleet::PoolKd kd{lr, l->k_mode.data() + k0, l->k_prev.data() + k0, l->k_out.data() + k0, l->d_slab, l->vpitch,
+                           l->rows, l->d_part, l->d_sums + 2 * (size_t)k0};
+    HIP_TRY(c, fleet::launch_pool_fold_kd(p->d_rows, p->pitch, picks + k0, p->d_state, k0 == 0, kc, dampen + k0,
+                                          k0 + kc == K, (double)1 / K, p->w.launch(), p->d_status, d_merged, d_f32, kd, s));
+  }
+  HIP_TRY(c, hipMemcpyAsync(p->h_status, p->d_status, sizeof(int) * (size_t)p->slots, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(l->h_sums, l->d_sums, sizeof(double) * 2 * (size_t)K, hipMemcpyDeviceToHost, s));
+  return FLEET_OK;
+}
+
+// after the stream was synchronised: the verdict, and on a clean one the commit and the outputs
+static int kledger_commit(fleet_kledger* l, const int32_t* picks, int K, double* norm_g, double* norm_diff, uint8_t* set) {
+  const int rc = pool_verdict(l->p, picks, K);
+  if (rc) return rc;  // the tables, the free list and every row a worker names are as before
+  l->row_of.swap(l->t_row), l->epoch_of.swap(l->t_epoch), l->free_rows.swap(l->t_free);
+  l->free_rows.insert(l->free_rows.end(), l->t_release.begin(), l->t_release.end());
+  for (int k = 0; k < K; ++k) {
+    norm_g[k] = (l->k_mode[k] & 1) ? std::sqrt(l->h_sums[2 * k]) : std::nan("");
+    norm_diff[k] = (l->k_mode[k] & 2) ? std::sqrt(l->h_sums[2 * k + 1]) : std::nan("");
+    set[k] = l->k_set[k];
+  }
+  return FLEET_OK;
+}
+
+}  // namespace
+
+int fleet_kledger_create(fleet_pool* p, int workers, int max_store, fleet_kledger** out) {
+  if (!p || !out) return FLEET_ERR_ARG;
+  *out = nullptr;
+  if (workers < 1 || max_store < 1) return FLEET_ERR_ARG;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  if (p->w.gb != 0 || p->w.ng != groups_of(p->w.n) || p->w.ng == 0)
+    return fail(c, FLEET_ERR_ARG, "fleet_kledger_create: the pool holds the groups [%zu, %zu) of %zu (the norms are sums over the whole upload)",
+                p->w.gb, p->w.ge, groups_of(p->w.n));
+  if ((size_t)workers + (size_t)max_store > (size_t)1 << 24)
+    return fail(c, FLEET_ERR_ARG, "fleet_kledger_create: %d workers + %d rows", workers, max_store);
+  fleet_kledger* l = new fleet_kledger();
+  l->p = p;
+  l->workers = workers, l->max_store = max_store, l->rows = workers + max_store;
+  l->vpitch = (12 * p->w.ng + 15) / 16 * 4;
+  l->row_of.assign((size_t)workers, -1);
+  l->epoch_of.assign((size_t)workers, 0);
+  for (int r = l->rows - 1; r >= 0; --r) l->free_rows.push_back(r);
+  const size_t slab_bytes = sizeof(float) * l->vpitch * (size_t)l->rows;
+  const size_t part_bytes = sizeof(double) * (size_t)fleet::pool_kd_partial_doubles(p->w.launch());
+  const size_t sums_bytes = sizeof(double) * 2 * (size_t)p->slots;
+  const bool ok = hipMalloc((void**)&l->d_slab, slab_bytes) == hipSuccess && hipMemset(l->d_slab, 0, slab_bytes) == hipSuccess &&
+                  hipMalloc((void**)&l->d_part, part_bytes) == hipSuccess &&
+                  hipMalloc((void**)&l->d_sums, sums_bytes) == hipSuccess &&
+                  hipHostMalloc((void**)&l->h_sums, sums_bytes, hipHostMallocDefault) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    release_kledger(l);
+    return fail(c, FLEET_ERR_NOMEM, "fleet_kledger_create: allocating %d rows of %zu groups failed", workers + max_store, p->w.ng);
+  }
+  *out = l;
+  return FLEET_OK;
+}
+
+void fleet_kledger_destroy(fleet_kledger* l) {
+  if (!l) return;
+  fleet_ctx* c = l->p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard dg(c->device);
+  (void)hipStreamSynchronize(c->stream);
+  release_kledger(l);
+}
+
+int fleet_kledger_workers(const fleet_kledger* l) { return l ? l->workers : FLEET_ERR_ARG; }
+
+int fleet_kledger_has(const fleet_kledger* l, int worker) {
+  if (!l || worker < 0 || worker >= l->workers) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(l->p->c->mu);
+  return l->row_of[worker] >= 0 ? 1 : 0;
+}
+
+int fleet_kledger_epoch(const fleet_kledger* l, int worker, int* epoch) {
+  if (!l || !epoch) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(l->p->c->mu);
+  const int rc = kledger_worker_arg(l, worker, "fleet_kledger_epoch");
+  if (rc) return rc;
+  *epoch = l->epoch_of[worker];
+  return FLEET_OK;
+}
+
+int fleet_kledger_forget(fleet_kledger* l, int worker) {
+  if (!l) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(l->p->c->mu);
+  const int rc = kledger_worker_arg(l, worker, "fleet_kledger_forget");
+  if (rc) return rc;
+  l->free_rows.push_back(l->row_of[worker]);  // every update synchronised: nothing in flight reads the row
+  l->row_of[worker] = -1;
+  return FLEET_OK;
+}
+
+int fleet_kledger_read(fleet_kledger* l, int worker, float* g, size_t cap) {
+  if (!l || !g) return FLEET_ERR_ARG;
+  fleet_ctx* c = l->p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  const int rc = kledger_worker_arg(l, worker, "fleet_kledger_read");
+  if (rc) return rc;
+  const size_t n = l->p->w.n;
+  if (cap < n) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu values", cap, n);
+  HIP_TRY(c, hipMemcpyAsync(g, l->d_slab + (size_t)l->row_of[worker] * l->vpitch, sizeof(float) * n, hipMemcpyDeviceToHost,
+                            c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return FLEET_OK;
+}
+
+int fleet_kledger_update(fleet_kledger* l, const int32_t* picks, int K, const double* dampen, const int32_t* worker,
+                         const int32_t* epoch, double lr, char* merged, size_t cap, size_t* out_len, float* merged_f32,
+                         double* norm_g, double* norm_diff, uint8_t* set) {
+  if (!l || !picks || !dampen || !merged || K <= 0 || !worker || !epoch || !norm_g || !norm_diff || !set)
+    return FLEET_ERR_ARG;
+  fleet_pool* p = l->p;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  if (!std::isfinite(lr)) return fail(c, FLEET_ERR_ARG, "fleet_kledger_update: the learning rate is not finite");
+  int rc = pool_update_args(p, picks, K, "fleet_kledger_update");
+  if (rc || (rc = kledger_resolve(l, K, worker, epoch, "fleet_kledger_update"))) return rc;
+  if (out_len) *out_len = p->w.len;
+  if (cap < p->w.len) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu", cap, p->w.len);
+  if ((rc = settle(c, &p->fly, c->stream, true))) return rc;
+  uint8_t* d_out = p->d_rows + (size_t)p->slots * p->pitch;  // as fleet_pool_update
+  if ((rc = kledger_fold(l, picks, K, dampen, lr, c->stream, d_out, merged_f32 ? p->d_state : nullptr))) return rc;
+  if ((rc = window_read_back(c, p->w, d_out, p->d_state, merged, merged_f32, c->stream))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return kledger_commit(l, picks, K, norm_g, norm_diff, set);
+}
+
+int fleet_kledger_update_device(fleet_kledger* l, const int32_t* picks, int K, const double* dampen,
+                                const int32_t* worker, const int32_t* epoch, double lr, void* d_merged,
+                                void* d_merged_f32, double* norm_g, double* norm_diff, uint8_t* set, void* stream) {
+  if (!l || !picks || !dampen || !d_merged || K <= 0 || !worker || !epoch || !norm_g || !norm_diff || !set)
+    return FLEET_ERR_ARG;
+  fleet_pool* p = l->p;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  if (!std::isfinite(lr)) return fail(c, FLEET_ERR_ARG, "fleet_kledger_update_device: the learning rate is not finite");
+  int rc = pool_update_args(p, picks, K, "fleet_kledger_update_device");
+  if (rc || (rc = kledger_resolve(l, K, worker, epoch, "fleet_kledger_update_device"))) return rc;
+  hipStream_t s = pick(c, stream);
+  if ((rc = settle(c, &p->fly, s, false))) return rc;
+  if ((rc = kledger_fold(l, picks, K, dampen, lr, s, (uint8_t*)d_merged, (float*)d_merged_f32))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(s));
+  p->fly.done();
+  return kledger_commit(l, picks, K, norm_g, norm_diff, set);
+}
+
 const char* fleet_update_kernel(size_t len) {
   static thread_local std::string name;
   name = fleet::update_kernel_name((int64_t)groups_of(fleet_b64_count(len)));

@@ -122,6 +122,29 @@ hipError_t launch_acc_push_many(const uint8_t* rows, size_t pitch, const uint8_t
 hipError_t launch_pool_fold(const uint8_t* pool, size_t pitch, const int32_t* slots, float* st, int first, int K,
                             const double* dampen, bool finish, double inv, const AccWindow& w, int* d_status,
                             uint8_t* merged, float* merged_f32, hipStream_t s);
+// launch_pool_fold with Kardam's side outputs of the picks (k_pool_fold_kd, then
+// k_pool_kd_reduce on the same stream): mode[k] = 1 (G and its squared norm) | 2 (prev[k]:
+// D = Q(G - prev) and its squared norm) | 4 (G stored in row out[k]), 0 = the plain step;
+// prev / out are rows of `slab` (`rows` rows of vpitch >= 3 groups floats, 16-byte
+// aligned), prev[k] possibly the out[j] of an earlier pick. sums[2 k + {0, 1}] receive
+// pick k's two sums (0 where the mode computes none); partials holds
+// pool_kd_partial_doubles(w) doubles. The window must begin at group 0 (hipErrorInvalidValue
+// otherwise, as for a mode or a row that does not fit). All arrays are host arrays of K.
+struct PoolKd {
+  double lr;
+  const uint8_t* mode;
+  const int32_t* prev;
+  const int32_t* out;
+  float* slab;
+  size_t vpitch;
+  int rows;
+  double* partials;
+  double* sums;
+};
+int64_t pool_kd_partial_doubles(const AccWindow& w);
+hipError_t launch_pool_fold_kd(const uint8_t* pool, size_t pitch, const int32_t* slots, float* st, int first, int K,
+                               const double* dampen, bool finish, double inv, const AccWindow& w, int* d_status,
+                               uint8_t* merged, float* merged_f32, const PoolKd& kd, hipStream_t s);
 hipError_t launch_encode_minibatch(const float* images, int64_t n_images, int F, const int32_t* labels,
                                    const int32_t* idx, int B, const float* teacher, int NL, const float header[7],
                                    uint8_t* out, int* err, hipStream_t s);

@@ -18,9 +18,11 @@ pruning thresholds at 0 (their defaults in the quick start), and the
 StalenessSimulator.stalenessSim: the buffered uploads then live in an upload pool
 in HBM (``Codec.pool``), the picker names which of them an update aggregates and
 in which order, and the rest stay buffered. Staleness simulation itself
-(StalenessSimulator), percentile pruning and Kardam's bookkeeping are the
-reference's host-side experiment controls and are not rebuilt (SURVEY.md §2 rows
-11-13); their O(N) natives (getNorm, subtract) are on :class:`Codec`.
+(StalenessSimulator) and percentile pruning are the reference's host-side experiment
+controls and are not rebuilt; their O(N) natives (getNorm,
+subtract) are on :class:`Codec`. Kardam's bookkeeping of the picked uploads (:470-484)
+is opt-in in the picker mode (``kardam=``): its gradients live in a ledger beside the
+pool, and the pool's fold computes their norms as side outputs.
 """
 from __future__ import annotations
 
@@ -81,9 +83,13 @@ class Kardam:
     the model-difference norm from ``subtractNative`` + ``getNorm``. ``checkByz``
     is not rebuilt: CppNNUpdater bypasses it (``if (true || ...)``, :488)."""
 
-    def __init__(self, codec, workers: int = 10):
+    def __init__(self, codec, workers: int = 10, ledger=None):
         self.codec = codec
         self.workers = workers
+        # ledger-backed mode: `grads` lives in HBM (fleet_amd.Ledger, which an update through
+        # the upload pool keeps current); setGrad's results arrive through apply(), and
+        # set_grads, which computes texts, is not used
+        self.ledger = ledger
         self.grads = {}           # worker -> (g text, epoch)
         self.models = {}          # worker -> model text
         self.model_diff_norm = {}
@@ -114,6 +120,14 @@ class Kardam:
                 self.grads[w] = (g, ep)
                 out.append(False)
         return out
+
+    def apply(self, worker: int, set_flag: bool, norm_diff: float) -> bool:
+        """One pick's setGrad result as the ledger computed it (``Ledger.update``'s ``set`` and
+        ``norm_diff``): gradDiffNorm is recorded when setGrad returned true (Kardam.java:63-65).
+        Returns ``set_flag``."""
+        if set_flag:
+            self.grad_diff_norm[worker] = float(norm_diff)
+        return bool(set_flag)
 
     def set_model(self, worker: int, model_text: bytes) -> None:
         if worker in self.models:
@@ -151,7 +165,11 @@ class FleetUpdater:
 
     def __init__(self, codec, layout, M: int, lrates: Sequence[float], weights, fc_bias, policy: int = 0,
                  alpha: float = 0.0, stale_size: int = 0, num_labels: int = 10, has_outlier: bool = False,
-                 streaming: bool = False, picker=None, pool_slots: Optional[int] = None):
+                 streaming: bool = False, picker=None, pool_slots: Optional[int] = None, kardam=None,
+                 kardam_model=None):
+        if kardam is not None and (picker is None or kardam_model is None):
+            raise ValueError("Kardam's bookkeeping runs in the staleSize > 0 branch: kardam needs a picker and a "
+                             "kardam_model")
         if stale_size != 0 and picker is None:
             raise NotImplementedError("staleness simulation (StalenessSimulator) is not rebuilt: staleSize != 0 needs a "
                                       "picker")
@@ -190,6 +208,16 @@ class FleetUpdater:
         self.picker = picker
         self.pool_slots = 4 * M if pool_slots is None else int(pool_slots)
         self._pool = None
+        # kardam: Kardam's bookkeeping of the picked uploads (:470-484), opt-in. ``kardam`` is a
+        # :class:`Kardam`; its `grads` then live in a ledger beside the pool (``Pool.ledger``),
+        # and one ``Ledger.update`` gives the merged bytes and every pick's setGrad result.
+        # ``kardam_model(tau)`` stands where getModelParametersNative(modelsSize()-1-tau) and
+        # the modelsSize() == staleSize gate stand (:472-474): the picked model's text, or
+        # None when Kardam does not run for that pick (:483-484). The caller holds the
+        # fleet_amd.Model with the versions.
+        self.kardam = kardam
+        self.kardam_model = kardam_model
+        self._ledger = None
 
     def _dampen_of(self, p: "Pending") -> float:
         """getDampen for one pick (:463-464) from the current epoch and label vector."""
@@ -248,8 +276,19 @@ class FleetUpdater:
         if picked is None:  # not possible to update with the buffered uploads (:405-406)
             return None
         dampen = [self._dampen_of(q) for q in picked]  # tau from the epoch at pick time (:427)
+        kd = None
         try:
-            merged, grad = pool.update([q.slot for q in picked], dampen, want_f32=True)
+            if self.kardam is None:
+                merged, grad = pool.update([q.slot for q in picked], dampen, want_f32=True)
+            else:
+                if self._ledger is None:
+                    self._ledger = self.kardam.ledger = pool.ledger(self.kardam.workers)
+                models = [self.kardam_model(self.curr_epoch - q.epoch) for q in picked]
+                workers = [-1 if m is None else q.client_id for q, m in zip(picked, models)]
+                # getLrate() before descentNative (:478): the rate of the previous step
+                merged, grad, _, diff, was_set = self._ledger.update(
+                    [q.slot for q in picked], dampen, workers, [q.epoch for q in picked], float(self.lr), want_f32=True)
+                kd = (models, diff, was_set)
         except Exception as e:
             bad = set(getattr(e, "slots", ()))  # Base64Error / LayoutError: the slots at fault leave, the model stays
             for q in self.acc:
@@ -257,6 +296,13 @@ class FleetUpdater:
                     pool.drop(q.slot)
             self.acc = [q for q in self.acc if q.slot not in bad]
             raise
+        if kd is not None:  # the loop's order (:476-480): a worker picked twice gets the reference's lips
+            for q, m, dn, st in zip(picked, *kd):
+                if m is None:
+                    continue
+                self.kardam.set_model(q.client_id, m)
+                if self.kardam.apply(q.client_id, bool(st), float(dn)):
+                    self.kardam.update_lip(q.client_id)
         window = [0] * len(self.global_labels)
         for q in picked:
             for j, v in enumerate(q.labels[: len(window)]):

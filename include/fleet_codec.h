@@ -264,8 +264,9 @@ int fleet_check(fleet_ctx* ctx, void* stream);
  * global label vector) change only inside the M-th call (:502-504, descentNative),
  * so the factor known at arrival is the one the batch loop would compute. For
  * staleSize > 0 keep the uploads in a fleet_pool (below), which aggregates any
- * picked subset of them; for pruning thresholds above 0 or Kardam's side outputs
- * keep the batch entry points.
+ * picked subset of them, with Kardam's side outputs from the pooled rows through a
+ * fleet_kledger (further below); for pruning thresholds above 0 keep the batch entry
+ * points.
  *
  * An accumulator belongs to its context (same mutex and device; destroy it
  * before fleet_destroy; errors through fleet_last_error(ctx)) and owns its memory
@@ -434,6 +435,79 @@ int fleet_pool_update_device(fleet_pool* pool, const int32_t* picks, int K, cons
 /* The error bits the last update saw in the slot's upload: 1 = Base64, 2 = layout
  * header; 0 for a clean or unpicked slot. FLEET_ERR_ARG for NULL or a bad slot. */
 int fleet_pool_slot_status(const fleet_pool* pool, int slot);
+
+/* Kardam ledger: Kardam's `grads` map kept in HBM beside an upload pool --------
+ * Kardam's bookkeeping runs in the staleSize > 0 branch alone (kardam.setModel /
+ * setGrad / updateLip under modelsSize() == staleSize, CppNNUpdater.java:472-481),
+ * the branch the pool covers. A fleet_kledger is Kardam.java's `grads` (worker ->
+ * (g, epoch), Kardam.java:40, 56-71) with every g as one fp32 row in HBM, in upload
+ * coordinates with header slots 0 (fleet_update_kardam_device's g_out rows). An
+ * update through the ledger is fleet_pool_update plus setGrad for its picks, in pick
+ * order: the fold kernel (k_pool_fold_kd) takes each pick's dampened value p on its
+ * way into the sum and computes G = Q(f32(f64(p) * lr)) -- pickedGrad.scalarMultiply(
+ * getLrate()), CppNNUpdater.java:478 --, its squared norm, the squared norm of
+ * Q(G - prev) (g.subtract(prev).getNorm(), Kardam.java:63) and stores G, so the
+ * picked rows are read once for the merged bytes and the side outputs together.
+ *
+ * A ledger belongs to one pool (same context, mutex and device; destroy it before
+ * fleet_pool_destroy) whose window must cover the whole upload (a windowed pool is
+ * FLEET_ERR_ARG: the norms are sums over all elements). It owns a slab of
+ * workers + max_store fp32 rows of 12 G bytes rounded up to 16 (G groups), the
+ * worker -> row and worker -> epoch tables and a free list of rows on the host, one
+ * launch's per-wave norm partials (grid x 4 waves x fleet_acc_burst() picks x 2
+ * doubles) and the pool's slots x 2 sums in HBM and pinned. `max_store` >= 1 bounds
+ * the picks of one update that store a row. */
+typedef struct fleet_kledger fleet_kledger;
+int fleet_kledger_create(fleet_pool* pool, int workers, int max_store, fleet_kledger** out);
+void fleet_kledger_destroy(fleet_kledger* ledger);
+int fleet_kledger_workers(const fleet_kledger* ledger);
+/* grads.containsKey(worker) (Kardam.java:57): 1 / 0; FLEET_ERR_ARG for NULL or a worker
+ * outside [0, workers). */
+int fleet_kledger_has(const fleet_kledger* ledger, int worker);
+/* grads.get(worker).y (Kardam.java:59): the epoch recorded with the worker's row;
+ * FLEET_ERR_ARG for NULL arguments, a worker outside [0, workers) or one not in the
+ * ledger (*epoch untouched). */
+int fleet_kledger_epoch(const fleet_kledger* ledger, int worker, int* epoch);
+/* grads.remove(worker): the worker's row returns to the free list. FLEET_ERR_ARG as
+ * fleet_kledger_epoch. */
+int fleet_kledger_forget(fleet_kledger* ledger, int worker);
+/* grads.get(worker).x decoded (Kardam.java:89-91): the worker's row, n = fleet_b64_count(
+ * len) floats in upload coordinates, header slots 0. Synchronous. FLEET_ERR_ARG as
+ * fleet_kledger_epoch; cap < n is FLEET_ERR_CAPACITY. */
+int fleet_kledger_read(fleet_kledger* ledger, int worker, float* g, size_t cap);
+/* fleet_pool_update* (CppNNUpdater.java:420-421, 463-464, 490-508) plus, for pick k of
+ * worker[k] at model epoch epoch[k], kardam.setGrad(worker[k], pickedGrad.scalarMultiply(
+ * lr), epoch[k]) (CppNNUpdater.java:478, Kardam.java:56-71), resolved on the host in pick
+ * order before the launch:
+ *   worker[k] < 0 (modelsSize()-1-tau < 0 or the modelsSize() == staleSize gate closed,
+ *     CppNNUpdater.java:472-474, 483-484): set 0, norm_g and norm_diff NaN, nothing stored;
+ *   not in the ledger (Kardam.java:67-70): set 0, norm_diff NaN, G stored;
+ *   in the ledger with epoch[k] (Kardam.java:59-62, the push is ignored): set 0,
+ *     norm_diff NaN, nothing stored;
+ *   in the ledger with another epoch (Kardam.java:63-65): set 1, norm_diff =
+ *     getNorm(g.subtract(prev)), G stored.
+ * norm_g[k] = sqrt(sum (double)(G*G)) is g.getNorm() (Kardam.java:58), norm_diff
+ * likewise over D = Q(G - prev): getNorm's float products summed in double in another
+ * order (per wave, then the waves in a fixed order: no floating-point atomics, the same
+ * bits for the same inputs on the same device). A worker that appears again later in the
+ * same update sees what the earlier pick left: its prev is that pick's G, its epoch that
+ * pick's. merged, merged_f32 and the slot status are fleet_pool_update's, bit for bit.
+ *
+ * Transactional: G goes to a free row, and worker -> row, the epoch and the free list
+ * change only after the slot status was read back clean. On FLEET_ERR_BASE64 /
+ * FLEET_ERR_LAYOUT the ledger (has, epoch, every row fleet_kledger_read returns) and the
+ * pool are exactly as before, fleet_pool_slot_status names the slots, and the outputs
+ * are not meaningful. FLEET_ERR_ARG, before anything is launched and with every output
+ * untouched: everything fleet_pool_update rejects, a NULL worker, epoch, norm_g,
+ * norm_diff or set, a worker >= workers, more storing picks than max_store, a
+ * non-finite lr. Both forms synchronise once (the norms are host outputs); neither is
+ * for graph capture. The device form uses fleet_pool_update_device's addressing. */
+int fleet_kledger_update(fleet_kledger* ledger, const int32_t* picks, int K, const double* dampen,
+                         const int32_t* worker, const int32_t* epoch, double lr, char* merged, size_t cap,
+                         size_t* out_len, float* merged_f32, double* norm_g, double* norm_diff, uint8_t* set);
+int fleet_kledger_update_device(fleet_kledger* ledger, const int32_t* picks, int K, const double* dampen,
+                                const int32_t* worker, const int32_t* epoch, double lr, void* d_merged,
+                                void* d_merged_f32, double* norm_g, double* norm_diff, uint8_t* set, void* stream);
 
 /* Self-test of the device codec arithmetic over whole input domains: an
  * order-independent 64-bit digest sum_i splitmix64(i<<32 | f(i)) of
