@@ -1,9 +1,13 @@
-// fleet_amd/csrc/kernels.h -- internal launchers (fleet_codec.cpp <-> kernels.hip).
+// fleet_amd/csrc/kernels.h -- internal launchers (fleet_codec.cpp <-> kernels.hip). What an
+// update launcher launches is decided in launch_plan.h / launch_plan.cpp (host code only:
+// the plan's overrides, plan_update and its two siblings, the kernel names).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <string>
+
+#include "launch_plan.h"
 
 // device error bits (atomicOr into the context's error word, read back by fleet_check)
 #define FLEET_ERRBIT_BASE64 1
@@ -42,7 +46,6 @@ hipError_t launch_update(const uint8_t* uploads, size_t pitch, int M, const doub
 // allocation, kd_epoch: a value new to them, per launch). The plan
 // overrides are the caller's one snapshot, passed to the sizing call and the launch
 // alike, so a concurrent fleet_set_plan cannot change the grid between the two.
-struct PlanOverrides;
 struct KardamOut {
   double lr;
   const float* prev;
@@ -57,28 +60,6 @@ hipError_t launch_update_kardam(const uint8_t* uploads, size_t pitch, int M, con
                                 double* norms, int* norm_parts, int* flag_slots, uint32_t* kd_flags,
                                 uint32_t kd_epoch, const PlanOverrides& o, hipStream_t s,
                                 uint32_t kd_wait_skew = 0);
-// Launch-plan overrides: experiments, and the tests that run every launch variant on
-// small inputs. Process-wide; set by fleet_set_plan (spec "key=value,..." -- update=
-// auto|stream|tiled|pipe, grid=auto|plain|lanes|balanced, fused=on|off,
-// stage_threads=N, stage_pieces=N, tile=auto|classic|flat|weave6|8, flat_w2=auto|N,
-// tile_enc_prio=auto|0..3,
-// tile_enc_rows=N) or, once at first
-// use, from FLEET_EXPERIMENTS (the
-// same spec). The default (empty spec) is the measured plan.
-struct PlanOverrides {
-  int update = 0;         // 0 auto, 1 stream grid, 2 64-group tiles, 3 16-group pipelined tiles
-  int grid = 0;           // stream grid: 0 auto, 1 a group per lane everywhere, 2 a value per lane everywhere
-  int tile = 0;           // tiles: 0 auto (flat alone, classic fused), 1 classic, 2 flat, 6/8 woven
-  int flat_w2 = 0;        // flat tiles: width of the tiles after the whole 64-group rounds (0 auto)
-  int tile_enc_prio = -1; // tiled / flat fused step: the encode blocks' issue priority (-1 auto)
-  int tile_enc_rows = 0;  // fused steps (tiles and stream): rows per encode block (0 auto: 24)
-  int fused = 1;          // 0: the pipelined step as two launches (update, then encode)
-  int stage_threads = 0;  // host staging copy threads (0 auto)
-  int stage_pieces = 0;   // host staging H2D parts (0 auto)
-};
-PlanOverrides plan_overrides();
-int set_plan_overrides(const char* spec, std::string* err);  // 0, or -1 (nothing changed)
-std::string plan_spec();                                     // normalised active spec, "" = default
 // names of the kernels launch_update / launch_update_encode pick for `groups` groups
 std::string update_kernel_name(int64_t groups);
 void update_plan_grid(int64_t groups, int* kind, int64_t* blocks, int64_t* n_a, int64_t* n_w, int64_t* n_n);

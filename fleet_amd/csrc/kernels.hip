@@ -12,7 +12,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <type_traits>
 
@@ -1397,13 +1396,7 @@ __device__ __forceinline__ int64_t xcd_tile(int64_t b, int64_t nb) {
 // LDS): 7 blocks per CU. A tile's (client, group) items are client-major over its W
 // groups, 512 per pass (two per thread): floor(512 / W) whole clients per pass, so
 // phase 2 is k_update_tiled's.
-// The widest flat tile: E = 192 values, one per phase-2 thread. 85-group tiles (six
-// whole clients per pass, a fourth phase-2 wave, 23.4 KB of LDS: 6 blocks per CU) were
-// slower everywhere: cifar10_256 update 275.5 against 268.4 us, the N = 4 window 250.3
-// against 230.6 (r05, profiles/r05/ab_flat_width85.txt).
-constexpr int kFlatTG = 64;
-constexpr int kFlatPass = 512;  // items per pass
-constexpr int kFlatSlots = 7;   // blocks per CU (LDS 22.6 KB, 92 SGPRs; r05 residency traces)
+constexpr int kFlatPass = 512;  // items per pass (kFlatTG, kFlatSlots: launch_plan.h)
 
 // scalarMultiply(getDampen) for a lane's own client (dampen_stage with a per-lane d: a
 // narrow tile's wave spans 64 / W clients): the binary32 multiply when every lane's d is
@@ -1569,11 +1562,6 @@ __device__ __forceinline__ void update_flat_block(TileShared<kFlatTG, 4, true>& 
                 reinterpret_cast<int32_t*>(pbuf + 3 * kFlatTG));
 }
 
-// The grid of k_update_flat: blocks [0, nW) are tiles of w1 groups, [nW, nU) tiles of
-// w2 groups (the last one ragged), each run in XCD-aware order (xcd_tile).
-struct FlatGrid {
-  int nW, nU, w1, w2;
-};
 __device__ __forceinline__ void flat_tile_range(int64_t b, const FlatGrid& fg, int64_t g_begin, int64_t g_end,
                                                 int64_t* g0, int* ng, int* w) {
   if (b < fg.nW) {
@@ -1601,7 +1589,7 @@ __device__ __forceinline__ void flat_tile_range(int64_t b, const FlatGrid& fg, i
 // next chunk's group is loaded one chunk ahead. NW = 4: the block's fourth wave
 // only produces, and which wave that is rotates with the tile (every SIMD of a CU
 // carries the same share of serial work).
-constexpr int kWeaveTG = 64, kWeaveE = 3 * kWeaveTG;
+constexpr int kWeaveE = 3 * kWeaveTG;
 
 template <int NW>
 struct WeaveShared {
@@ -2803,140 +2791,12 @@ hipError_t launch_descent(float* weights, float* fc_bias, const float* grad, con
 
 // ---------------------------------------------------------------- launch plan
 
-// Launch-plan overrides (kernels.h): process-wide, set by fleet_set_plan or, once at
-// first use, from FLEET_EXPERIMENTS (the same spec) -- the only environment read of
-// the launch path. Validated: an unknown key or value rejects the whole spec.
-namespace {
-std::mutex g_plan_mu;
-PlanOverrides g_plan;
-std::string g_plan_spec;  // normalised, "" = the measured default plan
-std::once_flag g_plan_env_once;
-
-bool parse_int(const std::string& v, int lo, int hi, int* out) {
-  if (v.empty() || v.size() > 6 || v.find_first_not_of("0123456789") != std::string::npos) return false;
-  const int x = atoi(v.c_str());
-  if (x < lo || x > hi) return false;
-  *out = x;
-  return true;
-}
-
-int parse_plan(const char* spec, PlanOverrides* o, std::string* norm, std::string* err) {
-  *o = PlanOverrides{};
-  norm->clear();
-  std::string s = spec ? spec : "";
-  for (char& ch : s)
-    if (ch == ';' || ch == ' ') ch = ',';
-  size_t p = 0;
-  while (p <= s.size()) {
-    size_t q = s.find(',', p);
-    if (q == std::string::npos) q = s.size();
-    const std::string item = s.substr(p, q - p);
-    p = q + 1;
-    if (item.empty()) continue;
-    const size_t eq = item.find('=');
-    if (eq == std::string::npos) {
-      *err = "plan item '" + item + "' is not key=value";
-      return -1;
-    }
-    const std::string k = item.substr(0, eq), v = item.substr(eq + 1);
-    bool ok = true;
-    if (k == "update") {
-      if (v == "auto") o->update = 0;
-      else if (v == "stream") o->update = 1;
-      else if (v == "tiled") o->update = 2;
-      else if (v == "pipe") o->update = 3;
-      else ok = false;
-    } else if (k == "grid") {
-      if (v == "auto") o->grid = 0;
-      else if (v == "plain") o->grid = 1;
-      else if (v == "lanes") o->grid = 2;
-      else if (v == "balanced") o->grid = 3;
-      else ok = false;
-    } else if (k == "tile") {
-      if (v == "auto") o->tile = 0;
-      else if (v == "classic") o->tile = 1;
-      else if (v == "flat") o->tile = 2;
-      else if (v == "weave6") o->tile = 6;
-      else if (v == "weave8") o->tile = 8;
-      else ok = false;
-    } else if (k == "tile_enc_prio") {
-      if (v == "auto") o->tile_enc_prio = -1;
-      else ok = parse_int(v, 0, 3, &o->tile_enc_prio);
-    } else if (k == "flat_w2") {
-      if (v == "auto") o->flat_w2 = 0;
-      else ok = parse_int(v, 1, kFlatTG, &o->flat_w2);
-    } else if (k == "tile_enc_rows") {
-      ok = parse_int(v, 1, 4096, &o->tile_enc_rows);
-    } else if (k == "fused") {
-      if (v == "on") o->fused = 1;
-      else if (v == "off") o->fused = 0;
-      else ok = false;
-    } else if (k == "stage_threads") {
-      ok = parse_int(v, 1, 64, &o->stage_threads);
-    } else if (k == "stage_pieces") {
-      ok = parse_int(v, 1, 64, &o->stage_pieces);
-    } else {
-      *err = "unknown plan key '" + k + "' (update, grid, tile, flat_w2, tile_enc_prio, tile_enc_rows, fused, "
-             "stage_threads, "
-             "stage_pieces)";
-      return -1;
-    }
-    if (!ok) {
-      *err = "bad value '" + v + "' for plan key '" + k + "'";
-      return -1;
-    }
-    if (!norm->empty()) *norm += ",";
-    *norm += k + "=" + v;
-  }
-  return 0;
-}
-
-void plan_env_init() {
-  std::call_once(g_plan_env_once, [] {
-    const char* e = getenv("FLEET_EXPERIMENTS");
-    if (!e || !*e) return;
-    PlanOverrides o;
-    std::string norm, err;
-    if (parse_plan(e, &o, &norm, &err) != 0) {
-      fprintf(stderr, "[fleet] FLEET_EXPERIMENTS rejected (%s): the default launch plan is used\n", err.c_str());
-      return;
-    }
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    g_plan = o;
-    g_plan_spec = norm;
-  });
-}
-}  // namespace
-
 #ifdef FLEET_TRACE
 hipError_t set_trace_buffer(void* p) {
   unsigned long long* q = static_cast<unsigned long long*>(p);
   return hipMemcpyToSymbol(HIP_SYMBOL(g_fleet_trace), &q, sizeof(q));
 }
 #endif
-
-PlanOverrides plan_overrides() {
-  plan_env_init();
-  std::lock_guard<std::mutex> lk(g_plan_mu);
-  return g_plan;
-}
-
-int set_plan_overrides(const char* spec, std::string* err) {
-  plan_env_init();
-  PlanOverrides o;
-  std::string norm;
-  if (parse_plan(spec, &o, &norm, err) != 0) return -1;
-  std::lock_guard<std::mutex> lk(g_plan_mu);
-  g_plan = o;
-  g_plan_spec = norm;
-  return 0;
-}
-
-std::string plan_spec() {
-  plan_env_init();
-  std::lock_guard<std::mutex> lk(g_plan_mu);
-  return g_plan_spec;
-}
 
 static inline unsigned blocks_for(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
 
@@ -2969,183 +2829,56 @@ static int device_simds() {
   return v;
 }
 
-// k_update_flat's grid for `groups` groups: r whole rounds of kFlatTG-group tiles over the
-// CUs, the rest in tiles of w2 = kFlatTG, 1/2 or 1/4 of it dealt round robin after them.
-// Picks the w2 that leaves the most loaded CU the fewest groups (r * kFlatTG +
-// ceil(n2 / CUs) * w2) with every tile resident at once (r + ceil(n2 / CUs) <= kFlatSlots),
-// the wider on a tie; more than one round of the widest tiles when the groups do not fit
-// one. (On the N = 8 window, 2.7 tiles per CU, the 16-group tiles' extra serial chains
-// also hide latency: the update 156-159 us on one width, 143 us with them; r05.)
-static FlatGrid flat_grid(int64_t groups, const PlanOverrides& o, bool fused) {
-  const int64_t cus = device_simds() / 4, w1 = kFlatTG;
-  const int64_t r = groups / (w1 * cus);
-  const int64_t rest = groups - r * w1 * cus;
-  int best = -1;
-  int64_t best_load = INT64_MAX;
-  // the fused step: no quarter-width tiles (their extra blocks take the slots the encode's
-  // blocks would start in) and half-width ones on a tie (the N = 8 window, 192 groups per
-  // CU either way: 175.4 us with quarter-width, 173.1 / 176.6 with half-width against
-  // 182.3 with full-width narrow tiles; r05 same-process A/Bs)
-  for (int k = 0; k < (fused ? 2 : 3); ++k) {
-    const int w2 = o.flat_w2 ? o.flat_w2 : kFlatTG >> k;  // a forced width: that one, even past a round
-    const int64_t n2 = (rest + w2 - 1) / w2, per_cu = (n2 + cus - 1) / cus;
-    if (r + per_cu > kFlatSlots && !o.flat_w2) continue;
-    const int64_t load = r * w1 + per_cu * w2;
-    if (load < best_load || (fused && load == best_load)) {  // the fused step: the narrower on a tie
-      best_load = load;
-      best = w2;
-    }
-  }
-  if (best < 0) best = kFlatTG;  // more than a round: the widest tiles throughout
-  const int64_t n2 = (rest + best - 1) / best;
-  return FlatGrid{(int)(r * cus), (int)(r * cus + n2), kFlatTG, best};
-}
-
-// The aggregation's launch plan for a bucket (or window) of `groups` 3-value groups.
-//   stream -- k_update_mixed<256> (fused: k_update_encode<256>): a lane walks its group
-//             down all M rows, whole rounds group-per-lane and the rest a value per lane;
-//   tiled  -- the one-width 64-group tiles of k_update_tiled_encode<64> (the fused step);
-//   flat   -- k_update_flat: two-phase tiles of a runtime width, one balanced round;
-//   woven  -- k_update_weave<8> / k_update_weave_encode<8 | 6>: both phases in one barrier
-//             interval (small windows, latency-bound);
-//   pipe   -- k_update_pipe<16, 1, 5, 0>: 16-group tiles, 4 producer waves + one consumer
-//             wave (MNIST-size buckets: the serial chain is the critical path).
-// Default ranges (DESIGN.md §4, 256 CUs): the update alone -- stream from 131,072 groups,
-// flat above 49,152 (three 64-group tiles per CU), woven 8-wave from 24 k, pipe below;
-// the fused step -- stream from 131,072, tiled from 65,536, flat from 40 k, woven 6-wave
-// from 32 k, woven 8-wave from 14 k, pipe below; Kardam's side outputs -- stream from
-// 131,072, flat from 32 k, pipe below.
-struct UpdatePlan {
-  int kind;       // 0 stream, 1 tiled, 2 pipe, 3 woven tiles (k_update_weave<nw>), 4 flat tiles
-  int nA;         // stream: blocks of group-per-lane waves (the rest a value per lane)
-  int64_t blocks; // stream / tiled / pipe grid
-  int nw;         // woven tiles: waves per block (6 or 8)
-  FlatGrid fg;    // flat tiles
-};
-static UpdatePlan plan_update(int64_t groups, const PlanOverrides& o, bool fused = false) {
-  UpdatePlan p{0, 0, 0, 0, FlatGrid{0, 0, kFlatTG, kFlatTG}};
-  if (o.update == 1) p.kind = 0;
-  else if (o.update == 2) p.kind = 1;
-  else if (o.update == 3) p.kind = 2;
-  else {
-    // the tiles from 32 k groups; the update alone (auto tiles) from 24 k, where its woven
-    // tiles already beat the pipelined ones (cifar10_256's N = 4 window, 26 k groups: 100.8
-    // against 141.3 us; 20.9 k: 106.9 / 109.4; 18.4 k and below the pipelined tiles win;
-    // r05, profiles/r05/ab_weave_vs_pipe.txt)
-    const int64_t tile_min = (!fused && o.tile == 0) ? 24LL * 1024 : 32LL * 1024;
-    p.kind = groups >= 256LL * 4 * 2 * 64 ? 0 : groups >= tile_min ? 1 : 2;
-  }
-  if (p.kind == 1 && o.tile >= 3) {  // the woven tiles (one width)
-    p.kind = 3;
-    p.nw = o.tile;
-  }
-  // the flat tiles for the update alone; the fused step keeps the one-width 64-group tiles
-  // from 64 k groups, whose free block slots start the encode's blocks beside them
-  // (same-process A/B, r05: the update alone 276 -> 261 us on cifar10_256, 241 -> 227 on
-  // the N = 4 window, 1133 -> 1099 on cifar100_1024; the fused step 380 against 392 on
-  // cifar10_256, but 170.6 against 181.4 us on the N = 8 window)
-  // the update alone up to three 64-group tiles per CU (the N = 8 window: 2.7, latency-
-  // bound): the woven 8-wave tiles, whose serial steps run between the producers' stages,
-  // one round of them at most (synth1m_256's N = 8 window 125.3 against 143.8 us for the
-  // flat tiles, cifar10_256's N = 3 122.2 against 146.2; at 3.2 and 3.6 tiles per CU they
-  // lose, 190-194 against 161-165 us; r05 same-process A/B, profiles/r05/ab_weave_small.txt)
-  if (p.kind == 1 && o.tile == 0 && !fused && groups <= 3LL * 64 * (device_simds() / 4)) {
-    p.kind = 3;
-    p.nw = 8;
-  }
-  // the fused step on small windows: the woven tiles with the encode's blocks after them
-  // from 14 k to 40 k groups (8 waves up to 32 k, 6 above), the pipelined tiles below
-  // (cifar10_256's N = 5 window 134.7 -> 107.5 us, cifar100_1024's N = 4 672.4 -> 463.0,
-  // cifar10_256's N = 3 160.2 -> 147.6 against the flat tiles; 13 k groups: 90.0 pipelined
-  // against 94.1; r05 same-process A/B, profiles/r05/ab_weave_fused.txt)
-  if (fused && o.update == 0 && o.tile == 0 && groups >= 14LL * 1024 && groups < 40LL * 1024) {
-    p.kind = 3;
-    p.nw = groups < 32LL * 1024 ? 8 : 6;
-  }
-  if (p.kind == 1 && (o.tile == 2 || (o.tile == 0 && (!fused || groups < 65536)))) p.kind = 4;
-  if (p.kind == 2) {
-    p.blocks = (groups + 15) / 16;
-  } else if (p.kind == 4) {
-    p.fg = flat_grid(groups, o, fused);
-    p.blocks = p.fg.nU;
-  } else if (p.kind == 3) {
-    p.blocks = (groups + kWeaveTG - 1) / kWeaveTG;
-  } else if (p.kind == 1) {  // one width (the fused step's tiles; the update alone under tile=classic)
-    p.blocks = (groups + 63) / 64;
-  } else {
-    const int64_t plain = (groups + 255) / 256;
-    if (o.grid == 1) {
-      p.nA = (int)plain;
-    } else if (o.grid == 2) {
-      p.nA = 0;
-    } else {  // whole rounds of group-per-lane waves (a multiple of one wave per SIMD)
-      const int simds = device_simds();
-      const int64_t waves = (groups + 63) / 64;
-      p.nA = waves < simds ? (int)plain : (int)(waves / simds * simds * 64 / 256);
-    }
-    // the value-per-lane blocks take what the group-per-lane rounds leave (none when
-    // the plain grid covers every group: its last block is ragged)
-    const int64_t rest = groups - (int64_t)p.nA * 256;
-    p.blocks = p.nA + (rest > 0 ? (rest + 83) / 84 : 0);
-  }
-  return p;
-}
-
+// The launchers of the update: the overrides' snapshot, the plan (launch_plan.h) for this
+// device's CUs, then one switch that launches what the plan says -- so the names below
+// report what is launched.
 std::string update_kernel_name(int64_t groups) {
-  const UpdatePlan p = plan_update(groups, plan_overrides());
-  char buf[64];
-  if (p.kind == 0) snprintf(buf, sizeof buf, "k_update_mixed<256, false>");
-  else if (p.kind == 2) snprintf(buf, sizeof buf, "k_update_pipe<16, 1, 5, 0, false>");
-  else if (p.kind == 3) snprintf(buf, sizeof buf, "k_update_weave<%d>", p.nw);
-  else if (p.kind == 4) snprintf(buf, sizeof buf, "k_update_flat");
-  else snprintf(buf, sizeof buf, "k_update_tiled_encode<64>");  // its tiles alone, no encode blocks
-  return buf;
+  return kernel_name(plan_update(groups, plan_overrides(), device_simds() / 4));
+}
+
+std::string update_encode_kernel_name(int64_t groups) {  // (the rows only size the grid)
+  return kernel_name(plan_update_encode(groups, 1, plan_overrides(), device_simds() / 4));
 }
 
 void update_plan_grid(int64_t groups, int* kind, int64_t* blocks, int64_t* n_a, int64_t* n_w, int64_t* n_n) {
-  const UpdatePlan p = plan_update(groups, plan_overrides());
-  *kind = p.kind;
+  const LaunchPlan p = plan_update(groups, plan_overrides(), device_simds() / 4);
+  *kind = (int)p.kind;
   *blocks = p.blocks;
   *n_a = p.nA;
   *n_w = -1;  // one width: blocks = ceil(groups / 64)
   *n_n = 0;
-  if (p.kind == 4) {  // flat: n_w tiles of kFlatTG groups, n_n tiles of n_a groups
+  if (p.kind == UpdateKind::Flat) {  // flat: n_w tiles of kFlatTG groups, n_n tiles of n_a groups
     *n_a = p.fg.w2;
     *n_w = p.fg.nW;
     *n_n = p.fg.nU - p.fg.nW;
   }
 }
 
-std::string update_encode_kernel_name(int64_t groups) {
-  const PlanOverrides o = plan_overrides();
-  const UpdatePlan p = plan_update(groups, o, true);
-  if (!o.fused) return update_kernel_name(groups) + " + k_encode_f32";
-  if (p.kind == 0) return "k_update_encode<256>";
-  if (p.kind == 1) return "k_update_tiled_encode<64>";
-  if (p.kind == 3) return "k_update_weave_encode<" + std::to_string(p.nw) + ">";
-  if (p.kind == 4) return "k_update_flat";
-  return "k_update_pipe<16, 1, 5, 0, false> (with the encode's blocks)";
-}
+// plan p's grid of the kernel; every update kernel begins with the same arguments. (The
+// cases below stand in the order the kernel templates were first launched in: the
+// compiler emits instantiations in that order, and the code object keeps its layout.)
+#define FLEET_UPDATE_ARGS \
+  uploads, pitch, M, d_dampen, inv_avg, n_up, g_begin, g_end, d_hdr_block, merged, merged_f32, d_err
+#define FLEET_LAUNCH(kernel, ...) \
+  hipLaunchKernelGGL(kernel, dim3((unsigned)p.grid), dim3(p.threads), 0, s, FLEET_UPDATE_ARGS, ##__VA_ARGS__)
 
-// The classic one-width tiles alone (tile=classic for the update without the encode):
-// k_update_tiled_encode<64> with no encode blocks
-static void launch_tiled(const UpdatePlan& p, const uint8_t* uploads, size_t pitch, int M, const double* d_dampen,
-                         double inv_avg, int64_t n_up, int64_t g_begin, int64_t g_end, const int32_t* d_hdr_block,
-                         uint8_t* merged, float* merged_f32, int* d_err, hipStream_t s) {
-  hipLaunchKernelGGL((k_update_tiled_encode<64>), dim3((unsigned)p.blocks), dim3(256), 0, s, uploads, pitch, M, d_dampen,
-                     inv_avg, n_up, g_begin, g_end, d_hdr_block, merged, merged_f32, d_err, (int)p.blocks, EncodeJob{});
-}
-
-// k_update_weave<nw> (nw = 6 or 8 waves per block)
-static void launch_weave(int nw, unsigned blocks, hipStream_t s, const uint8_t* uploads, size_t pitch, int M,
-                         const double* d_dampen, double inv_avg, int64_t n_up, int64_t g_begin, int64_t g_end,
-                         const int32_t* d_hdr_block, uint8_t* merged, float* merged_f32, int* d_err) {
-#define FLEET_WEAVE_LAUNCH(NWV)                                                                                   \
-  hipLaunchKernelGGL(k_update_weave<NWV>, dim3(blocks), dim3(64 * NWV), 0, s, uploads, pitch, M, d_dampen, inv_avg, \
-                     n_up, g_begin, g_end, d_hdr_block, merged, merged_f32, d_err)
-  if (nw == 6) FLEET_WEAVE_LAUNCH(6);
-  else FLEET_WEAVE_LAUNCH(8);
-#undef FLEET_WEAVE_LAUNCH
+static hipError_t launch_planned_update(const LaunchPlan& p, const uint8_t* uploads, size_t pitch, int M,
+                                        const double* d_dampen, double inv_avg, int64_t n_up, int64_t g_begin,
+                                        int64_t g_end, const int32_t* d_hdr_block, uint8_t* merged, float* merged_f32,
+                                        int* d_err, hipStream_t s) {
+  switch (p.kind) {
+    // The classic one-width tiles alone (tile=classic for the update without the encode):
+    // k_update_tiled_encode<64> with no encode blocks
+    case UpdateKind::Tiled: FLEET_LAUNCH((k_update_tiled_encode<64>), (int)p.blocks, EncodeJob{}); break;
+    case UpdateKind::Weave:  // k_update_weave<nw> (nw = 6 or 8 waves per block)
+      if (p.nw == 6) FLEET_LAUNCH(k_update_weave<6>);
+      else FLEET_LAUNCH(k_update_weave<8>);
+      break;
+    case UpdateKind::Pipe: FLEET_LAUNCH((k_update_pipe<16, 1, kPipeNW, 0>), INT32_MAX, EncodeJob{}); break;
+    case UpdateKind::Flat: FLEET_LAUNCH(k_update_flat, p.fg, EncodeJob{}); break;
+    case UpdateKind::Stream: FLEET_LAUNCH((k_update_mixed<256, false>), p.nA, KardamOut{}); break;
+  }
+  return hipGetLastError();
 }
 
 hipError_t launch_update(const uint8_t* uploads, size_t pitch, int M, const double* d_dampen, double inv_avg,
@@ -3153,25 +2886,8 @@ hipError_t launch_update(const uint8_t* uploads, size_t pitch, int M, const doub
                          uint8_t* merged, float* merged_f32, int* d_err, hipStream_t s) {
   if (!row_fits(n_up)) return hipErrorInvalidValue;
   if (g_end <= g_begin) return hipSuccess;
-  const UpdatePlan p = plan_update(g_end - g_begin, plan_overrides());
-  if (p.kind == 2)
-    hipLaunchKernelGGL((k_update_pipe<16, 1, 5, 0>), dim3((unsigned)p.blocks), dim3(64 * 5), 0, s, uploads, pitch, M,
-                       d_dampen, inv_avg, n_up, g_begin, g_end, d_hdr_block, merged, merged_f32, d_err, INT32_MAX,
-                       EncodeJob{});
-  else if (p.kind == 1)
-    launch_tiled(p, uploads, pitch, M, d_dampen, inv_avg, n_up, g_begin, g_end, d_hdr_block, merged, merged_f32, d_err,
-                 s);
-  else if (p.kind == 3)
-    launch_weave(p.nw, (unsigned)p.blocks, s, uploads, pitch, M, d_dampen, inv_avg, n_up, g_begin, g_end, d_hdr_block,
-                 merged, merged_f32, d_err);
-  else if (p.kind == 4)
-    hipLaunchKernelGGL(k_update_flat, dim3((unsigned)p.blocks), dim3(256), 0, s, uploads, pitch, M, d_dampen,
-                       inv_avg, n_up, g_begin, g_end, d_hdr_block, merged, merged_f32, d_err, p.fg, EncodeJob{});
-  else
-    hipLaunchKernelGGL((k_update_mixed<256, false>), dim3((unsigned)p.blocks), dim3(256), 0, s, uploads, pitch, M,
-                       d_dampen, inv_avg, n_up, g_begin, g_end, d_hdr_block, merged, merged_f32, d_err, p.nA,
-                       KardamOut{});
-  return hipGetLastError();
+  const LaunchPlan p = plan_update(g_end - g_begin, plan_overrides(), device_simds() / 4);
+  return launch_planned_update(p, FLEET_UPDATE_ARGS, s);
 }
 
 // per client: the (client, wave or tile) partials of the update summed in a fixed
@@ -3223,82 +2939,38 @@ __global__ void __launch_bounds__(NT) k_kardam_reduce(const double* __restrict__
   }
 }
 
-// waves per block of the Kardam pipelined form (one consumer, the rest producers): the
-// side outputs double the producers' work, and 8 producer waves keep the consumer fed
-// where 4 do not (mnist64 under rocprof, r06 call a10: 27.3 us with 4 producer waves,
-// 24.4 with 8, 28.3 with 10, 43.2 with 12; the plain update 16.1 us)
-#ifndef FLEET_KD_NW
-#define FLEET_KD_NW 9
-#endif
-constexpr int kKdPipeNW = FLEET_KD_NW;
-
 hipError_t launch_update_kardam(const uint8_t* uploads, size_t pitch, int M, const double* d_dampen, double inv_avg,
                                 int64_t n_up, int64_t g_begin, int64_t g_end, const int32_t* d_hdr_block,
                                 uint8_t* merged, float* merged_f32, int* d_err, const KardamOut& kd, int* n_waves,
                                 double* norms, int* norm_parts, int* flag_slots, uint32_t* kd_flags,
                                 uint32_t kd_epoch, const PlanOverrides& o, hipStream_t s, uint32_t kd_wait_skew) {
   if (!row_fits(n_up)) return hipErrorInvalidValue;
-  const int64_t groups = g_end - g_begin;
-  // the update's own launch plan with the side outputs: the pipelined tiles (side outputs
-  // from the producers, the reduce blocks in the same launch), the wide tiles (side
-  // outputs from the tile producers), or the stream kernel's SIMD-balanced grid
-  PlanOverrides ok = o;
-  // Kardam's side outputs ride in the flat tiles at every tile size (kardam_items: narrow
-  // widths 16 / 32 / 64 only, so another forced width is ignored here), never in the
-  // classic or woven ones
-  const bool flat_ok = o.flat_w2 == 0 || o.flat_w2 == 16 || o.flat_w2 == 32 || o.flat_w2 == 64;
-  ok.tile = 2;
-  if (!flat_ok) ok.flat_w2 = 0;
-  UpdatePlan p = plan_update(groups, ok);
-  if (p.kind == 0 && o.grid == 0) {
-    // the stream form on the plain grid unless a grid is asked for: value-per-lane waves
-    // pay the per-client wave sums for a third of the values (synth1m_256: 1747 vs
-    // 1724 us, r04 call a6)
-    p.nA = (int)((groups + 255) / 256);
-    p.blocks = p.nA;
-  }
-  const unsigned blocks = (unsigned)p.blocks;
-  // partial slots per client: a wave of the stream grid or a tile
-  *n_waves = p.kind == 0 ? (int)blocks * 4 : (int)blocks;
-  *flag_slots = p.kind == 2 ? (int)blocks * (kKdPipeNW - 1) : 0;  // the pipelined form's tile flags (per producer wave)
-  *norm_parts = 1;                                   // one pair per client
-  if (groups <= 0) return hipSuccess;
+  const LaunchPlan p = plan_update_kardam(g_end - g_begin, M, o, device_simds() / 4);
+  *n_waves = p.n_waves;
+  *flag_slots = p.flag_slots;
+  *norm_parts = p.norm_parts;
+  if (g_end <= g_begin) return hipSuccess;
   if (!kd.partials) return hipErrorInvalidValue;  // sizing call: *n_waves only
-  if (p.kind == 2 && !kd_flags) return hipErrorInvalidValue;
-  if (p.kind == 2) {  // the tiles, then one reduce block per client
-    const KardamReduceJob kr{norms, kd_flags, kd_epoch, kd_wait_skew};
-    hipLaunchKernelGGL((k_update_pipe<16, 1, kKdPipeNW, 0, true>), dim3((unsigned)(blocks + (unsigned)M)),
-                       dim3(64 * kKdPipeNW), 0, s,
-                       uploads, pitch, M, d_dampen, inv_avg, n_up, g_begin, g_end, d_hdr_block, merged, merged_f32,
-                       d_err, (int)blocks, EncodeJob{}, kd, kr);
-    return hipGetLastError();
+  if (p.kind == UpdateKind::Pipe && !kd_flags) return hipErrorInvalidValue;
+  switch (p.kind) {
+    case UpdateKind::Pipe:  // the tiles, then one reduce block per client
+      FLEET_LAUNCH((k_update_pipe<16, 1, kKdPipeNW, 0, true>), (int)p.blocks, EncodeJob{}, kd,
+                   KardamReduceJob{norms, kd_flags, kd_epoch, kd_wait_skew});
+      break;
+    case UpdateKind::Flat: FLEET_LAUNCH(k_update_flat_kd, p.fg, kd); break;
+    default: FLEET_LAUNCH((k_update_mixed<256, true>), p.nA, kd); break;  // Stream: the plan has no other
   }
-  if (p.kind == 4)
-    hipLaunchKernelGGL(k_update_flat_kd, dim3(blocks), dim3(256), 0, s, uploads, pitch, M, d_dampen, inv_avg, n_up,
-                       g_begin, g_end, d_hdr_block, merged, merged_f32, d_err, p.fg, kd);
-  else
-    hipLaunchKernelGGL((k_update_mixed<256, true>), dim3(blocks), dim3(256), 0, s, uploads, pitch, M, d_dampen,
-                       inv_avg, n_up, g_begin, g_end, d_hdr_block, merged, merged_f32, d_err, p.nA, kd);
-  if (*n_waves <= 512)
-    hipLaunchKernelGGL((k_kardam_reduce<64, 8>), dim3((unsigned)M), dim3(64), 0, s, kd.partials, (int64_t)*n_waves,
-                       norms);
-  else if (*n_waves <= 2048)
-    hipLaunchKernelGGL((k_kardam_reduce<64, 32>), dim3((unsigned)M), dim3(64), 0, s, kd.partials, (int64_t)*n_waves,
-                       norms);
-  else
-    hipLaunchKernelGGL((k_kardam_reduce<256, 32>), dim3((unsigned)M), dim3(256), 0, s, kd.partials,
-                       (int64_t)*n_waves, norms);
+#define FLEET_KD_REDUCE(NT, U)                                                                       \
+  hipLaunchKernelGGL((k_kardam_reduce<NT, U>), dim3((unsigned)M), dim3(NT), 0, s, kd.partials, \
+                     (int64_t)p.n_waves, norms)
+  switch (p.reduce) {
+    case KardamReduce::InLaunch: break;
+    case KardamReduce::Wave8: FLEET_KD_REDUCE(64, 8); break;
+    case KardamReduce::Wave32: FLEET_KD_REDUCE(64, 32); break;
+    case KardamReduce::Block32: FLEET_KD_REDUCE(256, 32); break;
+  }
+#undef FLEET_KD_REDUCE
   return hipGetLastError();
-}
-
-// rows per block of the standalone client encode: about 65,536 blocks in all (a
-// lane walks its group down rpb rows, so the LDS table copy is paid once per rpb
-// rows). Measured on one box (gpu_encode_rpb.sh (r04 tree), two rows of loads in
-// flight): synth1m_256 encodes in 478-480 us at 4-8 rows per block, 483 at 16, 501
-// at 2 and 32, 595 at 1; the same access pattern without the codec arithmetic
-// (scripts/ubench_stream.hip, 12 B in / 16 B out per lane) runs 452-486 us.
-static int encode_rows_per_block(int64_t gx, int rows) {
-  return (int)std::min<int64_t>(rows, std::max<int64_t>(1, (gx * rows + 65535) / 65536));
 }
 
 // The standalone client encode keeps the VarEntry digit counts: it is HBM-bound, and
@@ -3318,115 +2990,34 @@ hipError_t launch_encode_f32(const float* values, int64_t n, size_t vpitch, int 
 }
 
 // The aggregation of `uploads` and the client encode of `values` into `enc_out`
-// (another buffer) in one launch (the pipelined step): k_update_encode on the stream
-// grid, k_update_tiled_encode on the wide tiles, the pipelined tiles with the encode's
-// blocks after them; plan fused=off runs the two kernels back to back.
+// (another buffer) in one launch (the pipelined step), as plan_update_encode lays it out:
+// the update's blocks, then the encode's. The EncodeJob is the plan's encode side.
 hipError_t launch_update_encode(const uint8_t* uploads, size_t pitch, int M, const double* d_dampen, double inv_avg,
                                 int64_t n_up, const int32_t* d_hdr_block, uint8_t* merged, float* merged_f32,
                                 int* d_err, const float* values, size_t vpitch, uint8_t* enc_out, hipStream_t s) {
   if (!row_fits(n_up)) return hipErrorInvalidValue;
-  const int64_t groups = (n_up + 2) / 3;
-  const PlanOverrides o = plan_overrides();
-  const UpdatePlan p = plan_update(groups, o, true);
-  // the tiles' encode blocks at issue priority 3 beside the tiles' ladder (3 -> 0) from
-  // 64 k groups, 0 below: cifar10_256 394 -> 380 us, the N = 4 window 319 -> 311,
-  // cifar100_1024 1622 -> 1593, the N = 8 window 174.5 -> 178.5 (r05 same-process A/B)
-  const int tprio = o.tile_enc_prio >= 0 ? o.tile_enc_prio : groups >= 65536 ? 3 : 0;
-  if (groups == 0 || !o.fused) {
-    hipError_t e = launch_update(uploads, pitch, M, d_dampen, inv_avg, n_up, 0, groups, d_hdr_block, merged, merged_f32,
-                                 d_err, s);
-    if (e != hipSuccess) return e;
-    return launch_encode_f32(values, n_up, vpitch, M, enc_out, pitch, s);
+  const int64_t g_begin = 0, g_end = (n_up + 2) / 3;
+  if (g_end == 0) return hipSuccess;
+  const LaunchPlan p = plan_update_encode(g_end, M, plan_overrides(), device_simds() / 4);
+  if (p.step == PlanStep::UpdateThenEncode) {
+    const hipError_t e = launch_planned_update(p, FLEET_UPDATE_ARGS, s);
+    return e != hipSuccess ? e : launch_encode_f32(values, n_up, vpitch, M, enc_out, pitch, s);
   }
-  if (p.kind == 3) {  // the woven tiles, then the encode's blocks (64 * nw lanes each)
-    const int nt = 64 * p.nw;
-    const int64_t gx = (groups + nt - 1) / nt;
-    // 24 rows per encode block as in the other fused forms (the standalone encode's rule
-    // gave these blocks one or two rows each, every block copying the tables for them)
-    const int rpb = std::min(M, o.tile_enc_rows > 0 ? o.tile_enc_rows : 24);
-    const int64_t nU = p.blocks, nE = gx * ((M + rpb - 1) / rpb);
-    const EncodeJob ej{values, n_up, vpitch, enc_out, pitch, groups, gx, M, rpb,
-                       o.tile_enc_prio >= 0 ? o.tile_enc_prio : 0};
-#define FLEET_WEAVE_ENC_LAUNCH(NWV)                                                                             \
-  hipLaunchKernelGGL(k_update_weave_encode<NWV>, dim3((unsigned)(nU + nE)), dim3(64 * NWV), 0, s, uploads, pitch, M, \
-                     d_dampen, inv_avg, n_up, (int64_t)0, groups, d_hdr_block, merged, merged_f32, d_err, (int)nU, ej)
-    if (p.nw == 6) FLEET_WEAVE_ENC_LAUNCH(6);
-    else FLEET_WEAVE_ENC_LAUNCH(8);
-#undef FLEET_WEAVE_ENC_LAUNCH
-    return hipGetLastError();
+  const EncodeJob ej{values, n_up, vpitch, enc_out, pitch, g_end, p.enc_gx, M, p.enc_rpb, p.enc_prio};
+  switch (p.kind) {
+    case UpdateKind::Weave:
+      if (p.nw == 6) FLEET_LAUNCH(k_update_weave_encode<6>, (int)p.blocks, ej);
+      else FLEET_LAUNCH(k_update_weave_encode<8>, (int)p.blocks, ej);
+      break;
+    case UpdateKind::Flat: FLEET_LAUNCH(k_update_flat, p.fg, ej); break;
+    case UpdateKind::Tiled: FLEET_LAUNCH((k_update_tiled_encode<64>), (int)p.blocks, ej); break;
+    case UpdateKind::Pipe: FLEET_LAUNCH((k_update_pipe<16, 1, kPipeNW, 0>), (int)p.blocks, ej); break;
+    case UpdateKind::Stream: FLEET_LAUNCH((k_update_encode<256>), p.nA, (int)p.blocks, ej); break;
   }
-  if (p.kind == 4) {  // the flat tiles' round, then the encode's blocks (24 rows each, as below)
-    const int64_t gx = blocks_for(groups, 256);
-    const int rpb = std::min(M, o.tile_enc_rows > 0 ? o.tile_enc_rows : 24);
-    const int64_t nU = p.blocks, nE = gx * ((M + rpb - 1) / rpb);
-    const EncodeJob ej{values, n_up, vpitch, enc_out, pitch, groups, gx, M, rpb, tprio};
-    hipLaunchKernelGGL(k_update_flat, dim3((unsigned)(nU + nE)), dim3(256), 0, s, uploads, pitch, M, d_dampen,
-                       inv_avg, n_up, (int64_t)0, groups, d_hdr_block, merged, merged_f32, d_err, p.fg, ej);
-    return hipGetLastError();
-  }
-  if (p.kind == 1) {  // the wide tiles on one width, then the encode's blocks
-    // 24 rows per encode block, as in k_update_encode: each block copies the tile's
-    // 14 KB of tables into LDS, so the standalone encode's ~65,536 blocks (2 rows each at
-    // CIFAR sizes) spent the step on table copies -- the encode ran mostly after the
-    // tiles, 230 us of it on cifar10_256 against 157 us alone (r05 residency trace)
-    const int64_t gx = blocks_for(groups, 256);
-    const int rpb = std::min(M, o.tile_enc_rows > 0 ? o.tile_enc_rows : 24);
-    const int64_t nU = (groups + 63) / 64, nE = gx * ((M + rpb - 1) / rpb);
-    const EncodeJob ej{values, n_up, vpitch, enc_out, pitch, groups, gx, M, rpb, tprio};
-    hipLaunchKernelGGL((k_update_tiled_encode<64>), dim3((unsigned)(nU + nE)), dim3(256), 0, s, uploads, pitch, M,
-                       d_dampen, inv_avg, n_up, (int64_t)0, groups, d_hdr_block, merged, merged_f32, d_err, (int)nU, ej);
-    return hipGetLastError();
-  }
-  if (p.kind == 2) {  // small buckets: the pipelined tiles, the encode's 320-lane blocks after them
-    const int64_t gxp = (groups + 319) / 320;
-    const int rpb = encode_rows_per_block(gxp, M);
-    const EncodeJob ej{values, n_up, vpitch, enc_out, pitch, groups, gxp, M, rpb};
-    hipLaunchKernelGGL((k_update_pipe<16, 1, 5, 0>), dim3((unsigned)(p.blocks + gxp * ((M + rpb - 1) / rpb))),
-                       dim3(64 * 5), 0, s, uploads, pitch, M, d_dampen, inv_avg, n_up, (int64_t)0, groups, d_hdr_block,
-                       merged, merged_f32, d_err, (int)p.blocks, ej);
-    return hipGetLastError();
-  }
-  // the stream grid group-per-lane everywhere: the encode's blocks fill the SIMDs the
-  // last round of update waves leaves idle, so the value-per-lane balancing of
-  // k_update_mixed only adds instructions here (same-box A/B on synth1m_256: 1172.7 vs
-  // 1181.3 us, gpu_fused_ab.sh (r04 tree)). 24 rows per encode block: short blocks that
-  // fill the slots the update's waves leave (a lane walks its group down the rows with
-  // two loads in flight, so a block of hundreds of rows is a latency-bound straggler);
-  // same-box A/B on synth1m_256: 1179 / 1170 us at 6 / 12 rows per block in r03; with
-  // the encode's waves at priority 3 (r04) 1130 / 1097-1100 / 1084-1090 us at 6 / 12 /
-  // 24, and 48 no better (r04 call a31, a32.sh).
-  // (grid=lanes: the update's blocks a value per lane, for experiments on small windows)
-  const int64_t gx = blocks_for(groups, 256);
-  // Below four waves of group-per-lane update per SIMD (the N = 2 strong window: 2.7) the
-  // update alone's SIMD-balanced split -- whole rounds of group-per-lane waves, the rest a
-  // value per lane -- also under the encode's blocks (grid=balanced): synth1m_256's N = 2
-  // window 635.3 -> 604.3 us, configs[4]'s N = 8 window 11.09 -> 10.05 ms, while the full
-  // width (5.3 waves per SIMD) loses with it, 1106.6 -> 1159.8 us; one group-per-lane round
-  // fewer loses at N = 2 (624.0 us) (r05 same-process A/B, profiles/r05/ab_fused_balanced.txt)
-  const bool lanes = o.grid == 2;
-  int nAf = lanes ? 0 : (int)gx, nUf = lanes ? (int)((groups + 83) / 84) : (int)gx;
-  const bool balanced = o.grid == 3 || (o.grid == 0 && groups < 4LL * 64 * device_simds());
-  if (balanced) {
-    PlanOverrides ob = o;
-    ob.grid = 0;
-    const UpdatePlan pb = plan_update(groups, ob);
-    if (pb.kind == 0) {
-      nAf = pb.nA;
-      nUf = (int)pb.blocks;
-    }
-  }
-  const int rpb = std::min(M, o.tile_enc_rows > 0 ? o.tile_enc_rows : 24);
-  const int64_t nE = gx * ((M + rpb - 1) / rpb);
-  // the encode's waves at priority 3 over the full width (r04, see k_update_encode), at 0
-  // under the balanced split of a small window: there the update waves, 2.7 per SIMD, are
-  // the critical path (the N = 2 window 588.9 -> 572.5 us, while the full width loses at 2,
-  // 1083.7 -> 1108.4; r05 same-process A/B, profiles/r05/ab_stream_encode_prio.txt)
-  const EncodeJob ej{values, n_up, vpitch, enc_out, pitch, groups, gx, M, rpb,
-                     o.tile_enc_prio >= 0 ? o.tile_enc_prio : balanced ? 0 : 3};
-  hipLaunchKernelGGL((k_update_encode<256>), dim3((unsigned)(nUf + nE)), dim3(256), 0, s, uploads, pitch, M, d_dampen,
-                     inv_avg, n_up, (int64_t)0, groups, d_hdr_block, merged, merged_f32, d_err, nAf, nUf, ej);
   return hipGetLastError();
 }
+#undef FLEET_LAUNCH
+#undef FLEET_UPDATE_ARGS
 
 hipError_t launch_encode_i32(const int32_t* codes, int64_t n, uint8_t* out, hipStream_t s) {
   int64_t groups = (n + 2) / 3;

@@ -1,5 +1,7 @@
 // scripts/ubench_tiled.hip -- phase timing of the pipelined tiles k_update_pipe (dev tool).
 // Builds kernels.hip with FLEET_TIMING and prints per-block phase durations.
+// build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -Ifleet_amd/csrc -Iinclude scripts/ubench_tiled.hip
+//        fleet_amd/csrc/launch_plan.cpp -o /tmp/ubench_tiled
 #define FLEET_TIMING 1
 #define FLEET_DEV_ALL_KERNELS 1
 #include "../fleet_amd/csrc/kernels.hip"

@@ -8,6 +8,8 @@
 // waves and their client positions, and per-segment rates, and dumps the raw
 // stamps under gpurun_out/.
 //
+// build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -Ifleet_amd/csrc -Iinclude scripts/ubench_window.hip
+//        fleet_amd/csrc/launch_plan.cpp -o /tmp/ubench_window
 // usage: ubench_window GROUPS M[,M...] [plain|mixed] [rep]
 #include <hip/hip_runtime.h>
 

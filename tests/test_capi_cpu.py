@@ -83,16 +83,17 @@ def test_plan_overrides_validated_on_host():
     csrc = os.path.join(F.ROOT, "fleet_amd", "csrc")
     files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
     assert len(files) >= 10  # the kernel units and their headers are all here
-    src = "".join(open(f).read() for f in files + [os.path.join(csrc, "fleet_codec.cpp")])
+    src = "".join(open(f).read() for f in files + [os.path.join(csrc, "fleet_codec.cpp"),
+                                                   os.path.join(csrc, "launch_plan.cpp")])
     assert src.count("getenv(") == 1 and 'getenv("FLEET_EXPERIMENTS")' in src
-    assert 'getenv("FLEET_EXPERIMENTS")' in open(os.path.join(csrc, "kernels.hip")).read()
+    assert 'getenv("FLEET_EXPERIMENTS")' in open(os.path.join(csrc, "launch_plan.cpp")).read()
 
 
 GRID_SIZES = [1, 2, 16, 17, 83, 84, 85, 255, 256, 257, 6_667, 7_654, 16_668, 32_768, 50_001, 65_537, 100_001,
               104_623, 110_413, 131_072, 174_763, 349_526, 1_398_102]
 
 
-# The default launch plan per size (DESIGN.md §4 "Launch choice", kernels.hip plan_update),
+# The default launch plan per size (DESIGN.md §4 "Launch choice", launch_plan.cpp plan_update),
 # planned for 256 CUs (the host has no device: device_simds' fallback). (groups, update
 # alone, fused step) at the ends of every range.
 DEFAULT_PLAN = [

@@ -36,11 +36,16 @@ def test_edges_follow_the_constants_in_the_sources():
     assert int(_one(r"__shared__ TileShared<TG, (\d+), true> sh;", k)) == A.NW_TILED
     assert int(_one(r"__shared__ TileShared<kFlatTG, (\d+), true> sh;", k)) == A.NW_TILED
     assert "__shared__ TileShared<TG, NW, (bool)FLEET_PIPE_D16> sh;" in k
-    nw, nw2 = _one(r"k_update_pipe<16, 1, (\d+), 0>\), dim3\(\(unsigned\)p\.blocks\), dim3\(64 \* (\d+)\)", k)
-    assert int(nw) == int(nw2) == A.NW_PIPE
-    a, b, c = _one(r"if \(nw == (\d+)\) FLEET_WEAVE_LAUNCH\((\d+)\);\s*else FLEET_WEAVE_LAUNCH\((\d+)\);", k)
-    assert (int(a), int(c)) == (int(b), int(c)) == A.NW_WEAVE
-    assert int(_one(r"#define FLEET_KD_NW (\d+)", k)) == A.NW_PIPE_KD and "kKdPipeNW = FLEET_KD_NW" in k
+    # the launchers take the block from the plan (launch_plan.cpp), both from launch_plan.h's constants
+    lp, lc = _src("launch_plan.h"), _src("launch_plan.cpp")
+    assert int(_one(r"constexpr int kPipeNW = (\d+);", lp)) == A.NW_PIPE
+    assert "FLEET_LAUNCH((k_update_pipe<16, 1, kPipeNW, 0>), INT32_MAX" in k and "p->threads = 64 * kPipeNW;" in lc
+    assert "dim3(p.threads), 0, s, FLEET_UPDATE_ARGS" in k
+    a, b, c = _one(r"if \(p\.nw == (\d+)\) FLEET_LAUNCH\(k_update_weave<(\d+)>\);\s*"
+                   r"else FLEET_LAUNCH\(k_update_weave<(\d+)>\);", k)
+    assert (int(a), int(c)) == (int(b), int(c)) == A.NW_WEAVE and "p->threads = 64 * p->nw;" in lc
+    assert int(_one(r"#define FLEET_KD_NW (\d+)", lp)) == A.NW_PIPE_KD and "kKdPipeNW = FLEET_KD_NW" in lp
+    assert "FLEET_LAUNCH((k_update_pipe<16, 1, kKdPipeNW, 0, true>)" in k and "p.threads = 64 * kKdPipeNW;" in lc
     assert int(_one(r"constexpr int kAccLdsHdr = (\d+);", _src("acc_kernels.hip"))) == A.ACC_LDS_HDR
     h = _src("kernels.h")
     assert int(_one(r"constexpr int kMaxDescentSegs = (\d+);", h)) == A.MAX_DESCENT_SEGS
