@@ -137,6 +137,21 @@ def lib() -> C.CDLL:
         "fleet_kledger_read": (i32, [vp, i32, vp, sz]),
         "fleet_kledger_update": (i32, [vp, vp, i32, vp, vp, vp, C.c_double, vp, sz, szp, vp, vp, vp, vp]),
         "fleet_kledger_update_device": (i32, [vp, vp, i32, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp]),
+        "fleet_mledger_create": (i32, [vp, sz, sz, i32, i32, i32, C.POINTER(vp)]),
+        "fleet_mledger_destroy": (None, [vp]),
+        "fleet_mledger_shape": (i32, [vp, szp, szp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "fleet_mledger_launch_shape": (i32, [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "fleet_mledger_stage": (i32, [vp, i64, vp, vp]),
+        "fleet_mledger_stage_device": (i32, [vp, i64, vp, vp, vp]),
+        "fleet_mledger_resident": (i32, [vp, i64]),
+        "fleet_mledger_update": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+        "fleet_mledger_has": (i32, [vp, i32]),
+        "fleet_mledger_version": (i32, [vp, i32, C.POINTER(i64)]),
+        "fleet_mledger_forget": (i32, [vp, i32]),
+        "fleet_mledger_read": (i32, [vp, i32, vp, sz]),
+        "fleet_mledger_read_version": (i32, [vp, i64, vp, sz]),
+        "fleet_mledger_stage_model": (i32, [vp, vp, i32, C.POINTER(i64)]),
+        "fleet_model_version_id": (i32, [vp, i32, C.POINTER(i64)]),
         "fleet_update_kernel": (C.c_char_p, [sz]),
         "fleet_update_plan_grid": (i32, [sz, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -487,6 +502,14 @@ class Codec:
         uploads are put into slots when they arrive, and ``update`` over any subset of the
         slots, in any order, returns what ``update`` returns for those uploads in that order."""
         return Pool(self, length, header_pos, slots, group_begin, group_end)
+
+    def model_ledger(self, n_weights: int, n_biases: int, graph_edges: int, workers: int,
+                     max_versions: Optional[int] = None):
+        """A Kardam model ledger (fleet_mledger) for models of ``n_weights`` non-null W floats
+        and ``n_biases`` use_bias() biases over ``graph_edges`` layer-graph edges: ``workers``
+        worker ids, at most ``max_versions`` (default: ``workers``) resident versions that no
+        worker holds."""
+        return ModelLedger(self, n_weights, n_biases, graph_edges, workers, max_versions)
 
     def update_rows(self, rows: np.ndarray, length: int, dampen: Sequence[float], want_f32: bool = False):
         """fleet_update over a uint8 host array [M, row_pitch] whose row i holds upload i's
@@ -1194,6 +1217,137 @@ class Ledger:
         return ng, nd, st.astype(bool)
 
 
+class ModelLedger:
+    """Kardam's ``models`` map kept in HBM (fleet_mledger, include/fleet_codec.h;
+    Kardam.java:114-125). Model versions are made resident under caller-chosen ids
+    (``stage``, ``stage_model``) as the fp32 rows decoding their getModelParametersNative
+    text would give; ``update`` is ``setModel`` for every pick of an update, in pick order,
+    with the norms of all the row pairs it needs from one device pass. Rows belong to
+    versions: a worker's model is a reference to a row. Close it before its codec."""
+
+    STATUS_SKIPPED, STATUS_FIRST, STATUS_IGNORED, STATUS_SET = 0, 1, 2, 3
+
+    def __init__(self, codec: "Codec", n_weights: int, n_biases: int, graph_edges: int, workers: int,
+                 max_versions: Optional[int] = None):
+        self.codec = codec
+        self._L = codec._L
+        self._h = None
+        self.n_weights, self.n_biases, self.graph_edges = int(n_weights), int(n_biases), int(graph_edges)
+        self.workers = int(workers)
+        self.max_versions = self.workers if max_versions is None else int(max_versions)
+        self.n = self.n_biases * self.graph_edges + self.n_weights
+        h = C.c_void_p()
+        codec._check(self._L.fleet_mledger_create(codec._h, self.n_weights, self.n_biases, self.graph_edges, self.workers,
+                                                  self.max_versions, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.codec, "_h", None):
+            self._L.fleet_mledger_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _live(self):
+        if not getattr(self, "_h", None) or not getattr(self.codec, "_h", None):
+            raise ValueError("the model ledger or its codec is closed")
+        return self._h
+
+    @staticmethod
+    def launch_shape():
+        """(lanes per wave, values a block takes per pass, blocks per pair at most) of the pair kernel."""
+        w, b, m = C.c_int(0), C.c_int(0), C.c_int(0)
+        lib().fleet_mledger_launch_shape(C.byref(w), C.byref(b), C.byref(m))
+        return w.value, b.value, m.value
+
+    def stage(self, version_id: int, weights, biases) -> None:
+        """Make a version resident from its weights and use_bias() biases (``Model.export``'s
+        vectors); a resident id is a no-op."""
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        b = np.ascontiguousarray(biases, dtype=np.float32)
+        if len(w) != self.n_weights or len(b) != self.n_biases:
+            raise ValueError(f"the ledger holds {self.n_weights} weights and {self.n_biases} biases")
+        self.codec._check(self._L.fleet_mledger_stage(self._live(), int(version_id), w.ctypes.data if len(w) else None,
+                                                      b.ctypes.data if len(b) else None))
+
+    def stage_device(self, version_id: int, weights_f32, biases_f32, stream=None) -> None:
+        """``stage`` from float32 tensors on the codec's device, on ``stream``."""
+        if weights_f32.numel() != self.n_weights or biases_f32.numel() != self.n_biases:
+            raise ValueError(f"the ledger holds {self.n_weights} weights and {self.n_biases} biases")
+        self.codec._check(self._L.fleet_mledger_stage_device(
+            self._live(), int(version_id), weights_f32.data_ptr() if self.n_weights else None,
+            biases_f32.data_ptr() if self.n_biases else None, _stream(stream)))
+
+    def stage_model(self, model: "Model", version: int) -> int:
+        """Make ``models[version]`` of a :class:`Model` resident under its ``version_id``; returns the id."""
+        vid = C.c_int64(-1)
+        rc = self._L.fleet_mledger_stage_model(self._live(), model._h, int(version), C.byref(vid))
+        if rc != FLEET_OK:
+            model._check(rc)
+        return int(vid.value)
+
+    def resident(self, version_id: int) -> bool:
+        return bool(self._L.fleet_mledger_resident(self._live(), int(version_id)))
+
+    def update(self, version_ids, workers):
+        """``setModel(workers[k], version version_ids[k])`` for each pick in order (``workers[k]
+        < 0``: Kardam does not run for that pick). Returns ``(norm_model, norm_diff,
+        status)``: status 0 skipped, 1 first model (stored), 2 ignored (norm == 0, nothing
+        changes), 3 set (stored, ``norm_diff`` the norm); a norm not computed is NaN."""
+        ids = np.ascontiguousarray(version_ids, dtype=np.int64)
+        w = np.ascontiguousarray(workers, dtype=np.int32)
+        if len(ids) != len(w):
+            raise ValueError("one version id and one worker per pick")
+        K = len(w)
+        nm, nd, st = np.full(K, np.nan), np.full(K, np.nan), np.zeros(K, np.uint8)
+        h = self._live()
+        if K:  # (no pick: nothing to ask)
+            self.codec._check(self._L.fleet_mledger_update(h, ids.ctypes.data, w.ctypes.data, K, nm.ctypes.data,
+                                                           nd.ctypes.data, st.ctypes.data))
+        return nm, nd, st
+
+    def has(self, worker: int) -> bool:
+        v = self._L.fleet_mledger_has(self._live(), int(worker))
+        if v < 0:
+            raise FleetError(v, f"worker {worker} outside [0, {self.workers})")
+        return bool(v)
+
+    def version(self, worker: int) -> int:
+        """The id of the version the worker holds (the worker must hold one)."""
+        vid = C.c_int64(0)
+        self.codec._check(self._L.fleet_mledger_version(self._live(), int(worker), C.byref(vid)))
+        return int(vid.value)
+
+    def forget(self, worker: int) -> None:
+        self.codec._check(self._L.fleet_mledger_forget(self._live(), int(worker)))
+
+    def read(self, worker: int) -> np.ndarray:
+        """decodeFloat of the worker's model text: the values of its row."""
+        p = np.zeros(self.n, np.float32)
+        self.codec._check(self._L.fleet_mledger_read(self._live(), int(worker), p.ctypes.data, len(p)))
+        return p
+
+    def read_version(self, version_id: int) -> np.ndarray:
+        p = np.zeros(self.n, np.float32)
+        self.codec._check(self._L.fleet_mledger_read_version(self._live(), int(version_id), p.ctypes.data, len(p)))
+        return p
+
+    @property
+    def resident_bytes(self) -> int:
+        """HBM the rows take: workers + max_versions rows of n floats rounded up to 4."""
+        return 4 * ((self.n + 3) // 4 * 4) * (self.workers + self.max_versions)
+
+
 def update_multi(codecs: Sequence["Codec"], uploads: Sequence, dampen: Sequence[float], want_f32: bool = False):
     """Codec.update spread over several device contexts from one process
     (fleet_update_multi): context k aggregates a contiguous range of the 3-value
@@ -1331,6 +1485,18 @@ class Model:
         ge, nl = C.c_int(0), C.c_int(0)
         self._check(self._L.fleet_model_shape(self._h, C.byref(nw), C.byref(nb), C.byref(ge), C.byref(nl)))
         return nw.value, nb.value, ge.value, nl.value
+
+    def version_id(self, version: int) -> int:
+        """A stable id of ``models[version]``: indices shift when descentNative drops the
+        oldest version, the id of a version never changes."""
+        vid = C.c_int64(-1)
+        self._check(self._L.fleet_model_version_id(self._h, int(version), C.byref(vid)))
+        return int(vid.value)
+
+    def kardam_ledger(self, workers: int, max_versions: Optional[int] = None) -> "ModelLedger":
+        """A :class:`ModelLedger` of this model's shape on its codec."""
+        nw, nb, ge, _ = self.shape()
+        return self.codec.model_ledger(nw, nb, ge, workers, max_versions)
 
     def export(self, version: int = -1):
         """(weights, biases) of models[version]; version -1 = the current model."""

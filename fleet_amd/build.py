@@ -28,6 +28,7 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", f"-I{INCLUDE}", f"-I{CSRC}"]
 
 SOURCES = [("kernels.hip", True), ("stream_kernels.hip", True), ("acc_kernels.hip", True), ("model_codec.hip", True),
+           ("mledger_kernels.hip", True), ("mledger_table.cpp", False),
            ("fleet_codec.cpp", True), ("launch_plan.cpp", False),  # (file, needs HIP)
            ("model_state.cpp", True), ("teacher.hip", True), ("sampler_state.cpp", True)]
 
@@ -60,7 +61,7 @@ def build_codec(force: bool = False, out: str = LIB, defines=()) -> str:
 
     def compile_one(src):
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
-        # launch_plan.cpp is plain C++ (it includes no HIP header)
+        # launch_plan.cpp and mledger_table.cpp are plain C++ (they include no HIP header)
         lang = ["-x", "hip", f"--offload-arch={ARCH}"] if dict(SOURCES)[os.path.basename(src)] else []
         # the stream kernels are VALU-issue bound at 5-6 waves per SIMD: the ILP-first
         # machine scheduler beats the default there and loses on the tiles, hence their

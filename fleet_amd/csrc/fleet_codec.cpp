@@ -29,6 +29,7 @@
 static_assert(FLEET_MAX_HEADERS == fleet::kMaxHeaderSlots, "the kernels size their LDS header lists by it");
 #include "model_codec.h"
 #include "codec_device.h"
+#include "mledger_table.h"
 
 #define FLEET_VERSION "fleet-mi355x 0.1.0 (gfx950)"
 
@@ -2755,6 +2756,283 @@ int fleet_kledger_update_device(fleet_kledger* l, const int32_t* picks, int K, c
   HIP_TRY(c, hipStreamSynchronize(s));
   p->fly.done();
   return kledger_commit(l, picks, K, norm_g, norm_diff, set);
+}
+
+// --------------------------------------------------------- Kardam model ledger
+
+// Kardam.java's `models` map (worker -> model, Kardam.java:114-125) over a slab of fp32
+// rows that belong to model versions (mledger_table.h keeps the tables and resolves an
+// update into row pairs; mledger_kernels.hip fills rows and computes the pairs' norms).
+struct fleet_mledger {
+  fleet_ctx* c = nullptr;
+  size_t n_w = 0, n_b = 0, n = 0;
+  int edges = 0;
+  size_t vpitch = 0;            // floats per row: n rounded up to 4
+  std::unique_ptr<fleet::MledgerTable> t;
+  float* d_slab = nullptr;
+  float* d_w = nullptr;         // the host form's staging of one version
+  float* d_b = nullptr;
+  double* d_stage_part = nullptr;  // kMlMaxTiles partials per row: stages on different streams do not meet
+  double* d_row_sq = nullptr;   // per row: sum (double)(a * a)
+  double* d_pair_part = nullptr;   // one launch of pairs
+  double* d_pair_sq = nullptr;  // an update's pairs
+  size_t pair_cap = 0;
+  double* h_sq = nullptr;       // pinned: rows row sums, then the pairs'
+  size_t h_cap = 0;
+  hipEvent_t staged = nullptr;  // orders the context's stream after a stage on a caller's stream
+  std::vector<double> pair_norm;
+};
+
+namespace {
+
+static void release_mledger(fleet_mledger* l) {
+  for (void* d : {(void*)l->d_slab, (void*)l->d_w, (void*)l->d_b, (void*)l->d_stage_part, (void*)l->d_row_sq,
+                  (void*)l->d_pair_part, (void*)l->d_pair_sq})
+    if (d) (void)hipFree(d);
+  if (l->h_sq) (void)hipHostFree(l->h_sq);
+  if (l->staged) (void)hipEventDestroy(l->staged);
+  delete l;
+}
+
+static int mledger_worker_arg(const fleet_mledger* l, int worker, const char* what) {
+  if (worker < 0 || worker >= l->t->workers())
+    return fail(l->c, FLEET_ERR_ARG, "%s: worker %d outside [0, %d)", what, worker, l->t->workers());
+  if (l->t->row_of_worker(worker) < 0) return fail(l->c, FLEET_ERR_ARG, "%s: worker %d holds no model", what, worker);
+  return FLEET_OK;
+}
+
+// room for an update's P pairs in HBM and pinned memory
+static int mledger_pair_room(fleet_mledger* l, size_t P) {
+  fleet_ctx* c = l->c;
+  const size_t rows = (size_t)l->t->rows();
+  if (P > l->pair_cap) {
+    if (l->d_pair_sq) (void)hipFree(l->d_pair_sq);
+    l->d_pair_sq = nullptr, l->pair_cap = 0;
+    const size_t cap = std::max<size_t>(2 * P, 4 * (size_t)fleet::kAccBurst);
+    HIP_TRY(c, hipMalloc((void**)&l->d_pair_sq, sizeof(double) * cap));
+    l->pair_cap = cap;
+  }
+  if (rows + l->pair_cap > l->h_cap) {
+    if (l->h_sq) (void)hipHostFree(l->h_sq);
+    l->h_sq = nullptr, l->h_cap = 0;
+    HIP_TRY(c, hipHostMalloc((void**)&l->h_sq, sizeof(double) * (rows + l->pair_cap), hipHostMallocDefault));
+    l->h_cap = rows + l->pair_cap;
+  }
+  return FLEET_OK;
+}
+
+// version `id` from device vectors on stream s; the caller holds the context's mutex
+static int mledger_stage_on(fleet_mledger* l, int64_t id, const float* d_w, const float* d_b, hipStream_t s) {
+  fleet_ctx* c = l->c;
+  bool fresh = false;
+  const int row = l->t->stage(id, &fresh);
+  if (!fresh) return FLEET_OK;
+  const hipError_t e = fleet::launch_mrow_stage(d_w, (int64_t)l->n_w, d_b, (int64_t)l->n_b, l->n_b ? (int64_t)l->edges : 0,
+                                                l->d_slab + (size_t)row * l->vpitch,
+                                                l->d_stage_part + (size_t)row * fleet::kMlMaxTiles, l->d_row_sq + row, s);
+  if (e != hipSuccess) {
+    l->t->unstage(id);
+    return fail(c, FLEET_ERR_HIP, "launch_mrow_stage: %s", hipGetErrorString(e));
+  }
+  return FLEET_OK;
+}
+
+static int mledger_read_row(fleet_mledger* l, int row, float* params, size_t cap) {
+  fleet_ctx* c = l->c;
+  if (cap < l->n) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu values", cap, l->n);
+  HIP_TRY(c, hipMemcpyAsync(params, l->d_slab + (size_t)row * l->vpitch, sizeof(float) * l->n, hipMemcpyDeviceToHost,
+                            c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return FLEET_OK;
+}
+
+}  // namespace
+
+int fleet_mledger_create(fleet_ctx* c, size_t n_weights, size_t n_biases, int graph_edges, int workers,
+                         int max_versions, fleet_mledger** out) {
+  if (!c || !out) return FLEET_ERR_ARG;
+  *out = nullptr;
+  if (workers < 1 || max_versions < 1 || graph_edges < 0) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  if (n_weights >= (size_t)fleet::kMlMaxValues || n_biases >= (size_t)fleet::kMlMaxValues ||
+      (size_t)workers + (size_t)max_versions > (size_t)1 << 24)
+    return fail(c, FLEET_ERR_ARG, "fleet_mledger_create: %zu weights, %zu biases, %d workers + %d versions", n_weights,
+                n_biases, workers, max_versions);
+  const size_t n = n_biases * (size_t)graph_edges + n_weights;
+  if (n == 0 || n >= (size_t)fleet::kMlMaxValues)
+    return fail(c, FLEET_ERR_ARG, "fleet_mledger_create: a model of %zu values", n);
+  fleet_mledger* l = new fleet_mledger();
+  l->c = c;
+  l->n_w = n_weights, l->n_b = n_biases, l->edges = graph_edges, l->n = n;
+  l->vpitch = (n + 3) / 4 * 4;
+  l->t.reset(new fleet::MledgerTable(workers, max_versions));
+  const size_t rows = (size_t)l->t->rows();
+  const size_t slab_bytes = sizeof(float) * l->vpitch * rows;
+  const bool ok =
+      hipMalloc((void**)&l->d_slab, slab_bytes) == hipSuccess && hipMemset(l->d_slab, 0, slab_bytes) == hipSuccess &&
+      hipMalloc((void**)&l->d_w, sizeof(float) * std::max<size_t>(1, n_weights)) == hipSuccess &&
+      hipMalloc((void**)&l->d_b, sizeof(float) * std::max<size_t>(1, n_biases)) == hipSuccess &&
+      hipMalloc((void**)&l->d_stage_part, sizeof(double) * rows * fleet::kMlMaxTiles) == hipSuccess &&
+      hipMalloc((void**)&l->d_row_sq, sizeof(double) * rows) == hipSuccess &&
+      hipMemset(l->d_row_sq, 0, sizeof(double) * rows) == hipSuccess &&
+      hipMalloc((void**)&l->d_pair_part, sizeof(double) * fleet::kAccBurst * fleet::kMlMaxTiles) == hipSuccess &&
+      hipEventCreateWithFlags(&l->staged, hipEventDisableTiming) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    release_mledger(l);
+    return fail(c, FLEET_ERR_NOMEM, "fleet_mledger_create: allocating %zu rows of %zu values failed", rows, n);
+  }
+  *out = l;
+  return FLEET_OK;
+}
+
+void fleet_mledger_destroy(fleet_mledger* l) {
+  if (!l) return;
+  fleet_ctx* c = l->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard dg(c->device);
+  (void)hipStreamSynchronize(c->stream);
+  release_mledger(l);
+}
+
+int fleet_mledger_shape(const fleet_mledger* l, size_t* n_weights, size_t* n_biases, int* graph_edges, int* workers,
+                        int* max_versions) {
+  if (!l) return FLEET_ERR_ARG;
+  if (n_weights) *n_weights = l->n_w;
+  if (n_biases) *n_biases = l->n_b;
+  if (graph_edges) *graph_edges = l->edges;
+  if (workers) *workers = l->t->workers();
+  if (max_versions) *max_versions = l->t->max_versions();
+  return FLEET_OK;
+}
+
+int fleet_mledger_launch_shape(int* wave, int* block_values, int* max_blocks) {
+  if (wave) *wave = 64;
+  if (block_values) *block_values = fleet::mrow_block_values();
+  if (max_blocks) *max_blocks = fleet::kMlMaxTiles;
+  return FLEET_OK;
+}
+
+int fleet_mledger_stage(fleet_mledger* l, int64_t id, const float* weights, const float* biases) {
+  if (!l || (l->n_w && !weights) || (l->n_b && !biases)) return FLEET_ERR_ARG;
+  fleet_ctx* c = l->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  if (l->t->row_of_id(id) >= 0) {  // resident: only its age changes
+    bool fresh;
+    (void)l->t->stage(id, &fresh);
+    return FLEET_OK;
+  }
+  if (l->n_w) HIP_TRY(c, hipMemcpyAsync(l->d_w, weights, sizeof(float) * l->n_w, hipMemcpyHostToDevice, c->stream));
+  if (l->n_b) HIP_TRY(c, hipMemcpyAsync(l->d_b, biases, sizeof(float) * l->n_b, hipMemcpyHostToDevice, c->stream));
+  const int rc = mledger_stage_on(l, id, l->d_w, l->d_b, c->stream);
+  if (rc) return rc;
+  const hipError_t e = hipStreamSynchronize(c->stream);  // the caller's vectors and d_w / d_b are free again
+  if (e != hipSuccess) {
+    l->t->unstage(id);
+    return fail(c, FLEET_ERR_HIP, "fleet_mledger_stage: %s", hipGetErrorString(e));
+  }
+  return FLEET_OK;
+}
+
+int fleet_mledger_stage_device(fleet_mledger* l, int64_t id, const float* d_weights, const float* d_biases,
+                               void* stream) {
+  if (!l || (l->n_w && !d_weights) || (l->n_b && !d_biases)) return FLEET_ERR_ARG;
+  fleet_ctx* c = l->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  hipStream_t s = pick(c, stream);
+  const bool was = l->t->row_of_id(id) >= 0;
+  const int rc = mledger_stage_on(l, id, d_weights, d_biases, s);
+  if (rc || was || s == c->stream) return rc;
+  HIP_TRY(c, hipEventRecord(l->staged, s));
+  HIP_TRY(c, hipStreamWaitEvent(c->stream, l->staged, 0));
+  return FLEET_OK;
+}
+
+int fleet_mledger_resident(const fleet_mledger* l, int64_t id) {
+  if (!l) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(l->c->mu);
+  return l->t->row_of_id(id) >= 0 ? 1 : 0;
+}
+
+int fleet_mledger_has(const fleet_mledger* l, int worker) {
+  if (!l || worker < 0 || worker >= l->t->workers()) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(l->c->mu);
+  return l->t->row_of_worker(worker) >= 0 ? 1 : 0;
+}
+
+int fleet_mledger_version(const fleet_mledger* l, int worker, int64_t* id) {
+  if (!l || !id) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(l->c->mu);
+  const int rc = mledger_worker_arg(l, worker, "fleet_mledger_version");
+  if (rc) return rc;
+  *id = l->t->id_of_row(l->t->row_of_worker(worker));
+  return FLEET_OK;
+}
+
+int fleet_mledger_forget(fleet_mledger* l, int worker) {
+  if (!l) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(l->c->mu);
+  const int rc = mledger_worker_arg(l, worker, "fleet_mledger_forget");
+  if (rc) return rc;
+  (void)l->t->forget(worker);
+  return FLEET_OK;
+}
+
+int fleet_mledger_read(fleet_mledger* l, int worker, float* params, size_t cap) {
+  if (!l || !params) return FLEET_ERR_ARG;
+  fleet_ctx* c = l->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  const int rc = mledger_worker_arg(l, worker, "fleet_mledger_read");
+  if (rc) return rc;
+  return mledger_read_row(l, l->t->row_of_worker(worker), params, cap);
+}
+
+int fleet_mledger_read_version(fleet_mledger* l, int64_t id, float* params, size_t cap) {
+  if (!l || !params) return FLEET_ERR_ARG;
+  fleet_ctx* c = l->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  const int row = l->t->row_of_id(id);
+  if (row < 0) return fail(c, FLEET_ERR_ARG, "fleet_mledger_read_version: version %lld is not resident", (long long)id);
+  return mledger_read_row(l, row, params, cap);
+}
+
+int fleet_mledger_update(fleet_mledger* l, const int64_t* id, const int32_t* worker, int K, double* norm_model,
+                         double* norm_diff, uint8_t* status) {
+  if (!l || K < 0 || !id || !worker || !norm_model || !norm_diff || !status) return FLEET_ERR_ARG;
+  if (K == 0) return FLEET_OK;
+  fleet_ctx* c = l->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  fleet::MledgerTable& t = *l->t;
+  std::string why;
+  if (!t.resolve(id, worker, K, &why)) return fail(c, FLEET_ERR_ARG, "fleet_mledger_update: %s", why.c_str());
+  const size_t rows = (size_t)t.rows(), P = t.pair_cur().size();
+  if (t.active()) {  // (none: every pick is skipped and nothing is launched or copied)
+    int rc = mledger_pair_room(l, P);
+    if (rc) return rc;
+    constexpr int B = fleet::kAccBurst;
+    for (size_t p0 = 0; p0 < P; p0 += B) {
+      const int pc = (int)std::min<size_t>(B, P - p0);
+      HIP_TRY(c, fleet::launch_mrow_pair_norms(l->d_slab, l->vpitch, (int)rows, (int64_t)l->n, t.pair_cur().data() + p0,
+                                               t.pair_prev().data() + p0, pc, l->d_pair_part, l->d_pair_sq + p0,
+                                               c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(l->h_sq, l->d_row_sq, sizeof(double) * rows, hipMemcpyDeviceToHost, c->stream));
+    if (P)
+      HIP_TRY(c, hipMemcpyAsync(l->h_sq + rows, l->d_pair_sq, sizeof(double) * P, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  l->pair_norm.resize(P);
+  for (size_t i = 0; i < P; ++i) l->pair_norm[i] = std::sqrt(l->h_sq[rows + i]);
+  t.replay(l->pair_norm.data(), norm_diff, status);  // Kardam.java:114-125 in pick order; the tables change here
+  for (int k = 0; k < K; ++k)
+    norm_model[k] = t.pick_row(k) >= 0 ? std::sqrt(l->h_sq[(size_t)t.pick_row(k)]) : std::nan("");
+  return FLEET_OK;
 }
 
 const char* fleet_update_kernel(size_t len) {

@@ -126,6 +126,24 @@ int64_t pool_kd_partial_doubles(const AccWindow& w);
 hipError_t launch_pool_fold_kd(const uint8_t* pool, size_t pitch, const int32_t* slots, float* st, int first, int K,
                                const double* dampen, bool finish, double inv, const AccWindow& w, int* d_status,
                                uint8_t* merged, float* merged_f32, const PoolKd& kd, hipStream_t s);
+// The Kardam model ledger (mledger_kernels.hip). A model version is one fp32 row of
+// 4 * ceil(n / 4) floats, n = n_b * reps + n_w < kMlMaxValues values in getModelParams'
+// order, row[i] = Q(param(i)), the padding 0. A row or a pair runs on mrow_tiles(n) <=
+// kMlMaxTiles blocks of mrow_block_values() values a pass, and `partials` holds one double
+// per block: mrow_tiles(n) for a stage, kAccBurst * kMlMaxTiles for a launch of pairs.
+// launch_mrow_stage: the row, and *norm_sq = sum (double)(row[i]^2) (k_mrow_stage, then
+// k_mrow_reduce on the same stream). launch_mrow_pair_norms: P <= kAccBurst ordered pairs
+// of rows of `slab` (`rows` rows of vpitch floats, 16-byte aligned; cur / prev are host
+// arrays), sums[p] = sum (double)(D^2), D = Q(cur[i] - prev[i]) (k_mrow_pair_norms, then
+// k_mrow_reduce). hipErrorInvalidValue for a row outside the slab or a size that does not fit.
+constexpr int kMlMaxTiles = 64;
+constexpr int64_t kMlMaxValues = ((int64_t)1 << 31) - 4096;
+int mrow_block_values();
+int mrow_tiles(int64_t n);
+hipError_t launch_mrow_stage(const float* weights, int64_t n_w, const float* biases, int64_t n_b, int64_t reps,
+                             float* row, double* partials, double* norm_sq, hipStream_t s);
+hipError_t launch_mrow_pair_norms(const float* slab, size_t vpitch, int rows, int64_t n, const int32_t* cur,
+                                  const int32_t* prev, int P, double* partials, double* sums, hipStream_t s);
 hipError_t launch_encode_minibatch(const float* images, int64_t n_images, int F, const int32_t* labels,
                                    const int32_t* idx, int B, const float* teacher, int NL, const float header[7],
                                    uint8_t* out, int* err, hipStream_t s);

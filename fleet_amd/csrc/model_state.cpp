@@ -64,6 +64,7 @@ struct fleet_model {
   std::vector<uint8_t> fc;           // per layer: fully_connected (update_bias applies)
   Version cnn;                       // `cnn`
   std::deque<Version> models;        // `models`
+  int64_t pushed = 0;                // versions ever pushed: models[v]'s id is pushed - models.size() + v
   std::vector<double> lrates;        // `lrates_vec`
   float lr = 0.0f;                   // cnn's learning rate (set_learning_rate(double) -> float)
   int epoch = 0, priority = 0;
@@ -292,6 +293,7 @@ int fleet_model_init_updater(fleet_model* m, const double* lrates, int n_lrates)
   const int rc = version_of(m, m->cnn, &v);
   if (rc) return rc;
   m->models.push_back(std::move(v));
+  m->pushed++;
   m->priority = 0;
   m->epoch = 0;
   return FLEET_OK;
@@ -357,6 +359,7 @@ int fleet_model_descent(fleet_model* m, const char* merged, size_t len, int clie
   Version v;
   if ((rc = version_of(m, m->cnn, &v))) return rc;
   m->models.push_back(std::move(v));
+  m->pushed++;
   if (m->models.size() > (size_t)std::max(0, stale_size)) m->models.pop_front();
   return FLEET_OK;
 }
@@ -470,6 +473,35 @@ int fleet_model_shape(fleet_model* m, size_t* n_weights_out, size_t* n_biases_ou
   if (n_biases_out) *n_biases_out = m->cnn.b.size();
   if (graph_edges) *graph_edges = (int)m->edge_w_size.size();
   if (n_layers) *n_layers = (int)m->layers.size();
+  return FLEET_OK;
+}
+
+int fleet_model_version_id(fleet_model* m, int version, int64_t* id) {
+  if (!m || !id) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (version < 0 || (size_t)version >= m->models.size())
+    return mfail(m, FLEET_ERR_ARG, "model version %d of %zu", version, m->models.size());
+  *id = m->pushed - (int64_t)m->models.size() + version;
+  return FLEET_OK;
+}
+
+int fleet_mledger_stage_model(fleet_mledger* ledger, fleet_model* m, int version, int64_t* id) {
+  if (!ledger || !m) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (version < 0 || (size_t)version >= m->models.size())
+    return mfail(m, FLEET_ERR_ARG, "model version %d of %zu", version, m->models.size());
+  size_t nw = 0, nb = 0;
+  int edges = 0;
+  int rc = fleet_mledger_shape(ledger, &nw, &nb, &edges, nullptr, nullptr);
+  if (rc) return rc;
+  const Version& v = m->models[(size_t)version];
+  if (nw != v.w.size() || nb != v.b.size() || edges != (int)m->edge_w_size.size())
+    return mfail(m, FLEET_ERR_ARG, "the ledger holds %zu weights, %zu biases, %d edges; the model %zu, %zu, %zu", nw, nb,
+                 edges, v.w.size(), v.b.size(), m->edge_w_size.size());
+  const int64_t vid = m->pushed - (int64_t)m->models.size() + version;
+  if ((rc = fleet_mledger_stage(ledger, vid, v.w.data(), v.b.data())))
+    return mfail(m, rc, "stage_model: %s", fleet_last_error(m->ctx));
+  if (id) *id = vid;
   return FLEET_OK;
 }
 

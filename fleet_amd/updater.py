@@ -22,7 +22,9 @@ in which order, and the rest stay buffered. Staleness simulation itself
 controls and are not rebuilt; their O(N) natives (getNorm,
 subtract) are on :class:`Codec`. Kardam's bookkeeping of the picked uploads (:470-484)
 is opt-in in the picker mode (``kardam=``): its gradients live in a ledger beside the
-pool, and the pool's fold computes their norms as side outputs.
+pool, and the pool's fold computes their norms as side outputs; with ``kardam_models=`` its
+models live in a model ledger too, and one pass over the picked versions' rows gives every
+pick's setModel result.
 """
 from __future__ import annotations
 
@@ -80,16 +82,21 @@ class Kardam:
     """utils/Kardam.java's bookkeeping (setGrad :48-62, setModel :93-106, updateLip
     :190-203) with its O(N) vector work on the GPU: the gradient texts and norms of
     all picked uploads come from one ``Codec.kardam_grads`` call,
-    the model-difference norm from ``subtractNative`` + ``getNorm``. ``checkByz``
-    is not rebuilt: CppNNUpdater bypasses it (``if (true || ...)``, :488)."""
+    the model-difference norm from ``subtractNative`` + ``getNorm`` over two texts, or,
+    with a model ledger (``apply_model``), from one device pass over the picked versions'
+    resident rows. ``checkByz`` is not rebuilt: CppNNUpdater bypasses it (``if (true ||
+    ...)``, :488)."""
 
-    def __init__(self, codec, workers: int = 10, ledger=None):
+    def __init__(self, codec, workers: int = 10, ledger=None, model_ledger=None):
         self.codec = codec
         self.workers = workers
         # ledger-backed mode: `grads` lives in HBM (fleet_amd.Ledger, which an update through
         # the upload pool keeps current); setGrad's results arrive through apply(), and
         # set_grads, which computes texts, is not used
         self.ledger = ledger
+        # likewise `models` (fleet_amd.ModelLedger): setModel's results arrive through
+        # apply_model(), and set_model, which subtracts texts, is not used
+        self.model_ledger = model_ledger
         self.grads = {}           # worker -> (g text, epoch)
         self.models = {}          # worker -> model text
         self.model_diff_norm = {}
@@ -137,6 +144,15 @@ class Kardam:
             self.model_diff_norm[worker] = norm
         self.models[worker] = model_text
 
+    def apply_model(self, worker: int, status: int, norm_diff: float) -> int:
+        """One pick's setModel result as the model ledger computed it (``ModelLedger.update``'s
+        ``status`` and ``norm_diff``): modelDiffNorm is recorded when the model was set over a
+        previous one (status 3, Kardam.java:122); a first model (1) and an ignored one (2,
+        :118-121) record nothing. The models themselves stay in the ledger. Returns ``status``."""
+        if int(status) == 3:
+            self.model_diff_norm[worker] = float(norm_diff)
+        return int(status)
+
     def update_lip(self, worker: int) -> None:
         lip = self.grad_diff_norm[worker] / self.model_diff_norm[worker]
         lst = self.lips.setdefault(worker, [])
@@ -166,10 +182,13 @@ class FleetUpdater:
     def __init__(self, codec, layout, M: int, lrates: Sequence[float], weights, fc_bias, policy: int = 0,
                  alpha: float = 0.0, stale_size: int = 0, num_labels: int = 10, has_outlier: bool = False,
                  streaming: bool = False, picker=None, pool_slots: Optional[int] = None, kardam=None,
-                 kardam_model=None):
-        if kardam is not None and (picker is None or kardam_model is None):
+                 kardam_model=None, kardam_models=None):
+        if kardam_model is not None and kardam_models is not None:
+            raise ValueError("kardam_model (a callback that returns texts) and kardam_models (a fleet_amd.Model whose "
+                             "versions go through a model ledger) are two ways to the same models: give one")
+        if kardam is not None and (picker is None or (kardam_model is None and kardam_models is None)):
             raise ValueError("Kardam's bookkeeping runs in the staleSize > 0 branch: kardam needs a picker and a "
-                             "kardam_model")
+                             "kardam_model or kardam_models")
         if stale_size != 0 and picker is None:
             raise NotImplementedError("staleness simulation (StalenessSimulator) is not rebuilt: staleSize != 0 needs a "
                                       "picker")
@@ -215,9 +234,16 @@ class FleetUpdater:
         # the modelsSize() == staleSize gate stand (:472-474): the picked model's text, or
         # None when Kardam does not run for that pick (:483-484). The caller holds the
         # fleet_amd.Model with the versions.
+        # ``kardam_models`` instead: the fleet_amd.Model with the versions itself. The updater then
+        # applies the gate of :472-474 (v = modelsSize()-1-tau >= 0 and modelsSize() == staleSize)
+        # and `models` lives in a model ledger too (``Model.kardam_ledger``): the picked versions
+        # are made resident once each and one ``ModelLedger.update`` gives every pick's setModel
+        # result, so no model text is built and no pick makes a host round trip.
         self.kardam = kardam
         self.kardam_model = kardam_model
+        self.kardam_models = kardam_models
         self._ledger = None
+        self._mledger = None
 
     def _dampen_of(self, p: "Pending") -> float:
         """getDampen for one pick (:463-464) from the current epoch and label vector."""
@@ -277,13 +303,17 @@ class FleetUpdater:
             return None
         dampen = [self._dampen_of(q) for q in picked]  # tau from the epoch at pick time (:427)
         kd = None
+        versions = None
+        if self.kardam is not None and self.kardam_models is not None:
+            versions = self._kardam_versions(picked)  # before anything changes
         try:
             if self.kardam is None:
                 merged, grad = pool.update([q.slot for q in picked], dampen, want_f32=True)
             else:
                 if self._ledger is None:
                     self._ledger = self.kardam.ledger = pool.ledger(self.kardam.workers)
-                models = [self.kardam_model(self.curr_epoch - q.epoch) for q in picked]
+                models = versions if versions is not None else [
+                    self.kardam_model(self.curr_epoch - q.epoch) for q in picked]
                 workers = [-1 if m is None else q.client_id for q, m in zip(picked, models)]
                 # getLrate() before descentNative (:478): the rate of the previous step
                 merged, grad, _, diff, was_set = self._ledger.update(
@@ -296,7 +326,9 @@ class FleetUpdater:
                     pool.drop(q.slot)
             self.acc = [q for q in self.acc if q.slot not in bad]
             raise
-        if kd is not None:  # the loop's order (:476-480): a worker picked twice gets the reference's lips
+        if kd is not None and versions is not None:
+            self._kardam_models_loop(picked, *kd)
+        elif kd is not None:  # the loop's order (:476-480): a worker picked twice gets the reference's lips
             for q, m, dn, st in zip(picked, *kd):
                 if m is None:
                     continue
@@ -319,6 +351,42 @@ class FleetUpdater:
         self.acc = [q for q in self.acc if q.slot not in gone]
         self.last_merged = merged
         return merged
+
+    def _kardam_versions(self, picked) -> List[Optional[int]]:
+        """The gate of :472-474 for each pick, on ``kardam_models``: the index of the picked
+        model in ``models`` (modelsSize()-1-tau), or None when Kardam does not run for the pick
+        (no such version any more, :483-484, or modelsSize() != staleSize, :474)."""
+        n = self.kardam_models.modelsSize()
+        out: List[Optional[int]] = []
+        for q in picked:
+            v = n - 1 - (self.curr_epoch - q.epoch)
+            if v >= n:  # (the reference indexes past `models` here)
+                raise ValueError(f"an upload of epoch {q.epoch} at epoch {self.curr_epoch}: no such model version")
+            out.append(v if v >= 0 and n == self.stale_size else None)
+        return out
+
+    def _kardam_models_loop(self, picked, versions, diff, was_set) -> None:
+        """setModel for every pick from one model-ledger update, then the loop's host part in
+        pick order (:476-480): apply_model, apply, update_lip."""
+        m = self._mledger
+        if m is None:
+            m = self.kardam.model_ledger
+            if m is None:
+                m = self.kardam.model_ledger = self.kardam_models.kardam_ledger(self.kardam.workers,
+                                                                                max(1, self.stale_size))
+            self._mledger = m
+        ids = {}
+        for v in versions:
+            if v is not None and v not in ids:
+                ids[v] = m.stage_model(self.kardam_models, v)
+        _, mdiff, status = m.update([-1 if v is None else ids[v] for v in versions],
+                                    [-1 if v is None else q.client_id for q, v in zip(picked, versions)])
+        for q, v, md, ms, dn, st in zip(picked, versions, mdiff, status, diff, was_set):
+            if v is None:
+                continue
+            self.kardam.apply_model(q.client_id, int(ms), float(md))
+            if self.kardam.apply(q.client_id, bool(st), float(dn)):
+                self.kardam.update_lip(q.client_id)
 
     def _finish_batch(self, fused=None) -> bytes:
         """The M-th call's part after the arrival (:420-421, :463-464, :490-516): picks the

@@ -509,6 +509,83 @@ int fleet_kledger_update_device(fleet_kledger* ledger, const int32_t* picks, int
                                 const int32_t* worker, const int32_t* epoch, double lr, void* d_merged,
                                 void* d_merged_f32, double* norm_g, double* norm_diff, uint8_t* set, void* stream);
 
+/* Kardam model ledger: Kardam's `models` map kept in HBM -----------------------
+ * kardam.setModel(pickedId, pickedModel) (CppNNUpdater.java:472-476) with pickedModel =
+ * T_v = getModelParametersNative(v) (cppNN_backend.cpp:227-242: Base64::encode of
+ * getModelParams, n = n_biases * graph_edges + n_weights values, fleet_model_params'
+ * vector) is, per pick (Kardam.java:114-125):
+ *   if models.containsKey(w):
+ *     norm = mcurr.subtract(models.get(w)).getNorm()          (:117)
+ *     if norm == 0: return                                     (:118-121, nothing changes)
+ *     modelDiffNorm.put(w, norm)                               (:122)
+ *   models.put(w, mcurr)                                       (:124)
+ * and per element (cppNN_backend.cpp:779-795, 848-892), with Q = decodeFloat o encode:
+ *   a = Q(P_v[i]), b = Q(P_u[i]), D = Q(a - b), norm = sqrt(sum (double)(D * D)).
+ * A fleet_mledger keeps model VERSIONS as fp32 rows a[] in HBM (what decoding T_v gives:
+ * Q applied once, never again; no text is built) under caller-chosen 64-bit ids, and
+ * `models` as a worker -> row table with a reference count per row: storing a worker's
+ * model copies nothing, and workers at one version share its row. The slab has workers +
+ * max_versions rows of n floats rounded up to 4. Staging a version that is not resident
+ * first evicts unreferenced rows, the one staged longest ago first, while there are
+ * max_versions of them (staging a resident version renews its age); a row a worker holds
+ * is never evicted. One update computes the norms of all distinct ordered (cur, prev) row
+ * pairs its picks may need in launches of fleet_acc_burst() pairs (k_mrow_pair_norms); the
+ * subtraction is not symmetric, the rule is "norm == 0" and not "same id", and a NaN norm
+ * stores. Same context, mutex and device as `ctx`; destroy it before fleet_destroy.
+ * FLEET_ERR_ARG from create: NULLs, workers or max_versions < 1, graph_edges < 0, n = 0 or
+ * n >= 2^31 - 4096. */
+typedef struct fleet_mledger fleet_mledger;
+int fleet_mledger_create(fleet_ctx* ctx, size_t n_weights, size_t n_biases, int graph_edges, int workers,
+                         int max_versions, fleet_mledger** out);
+void fleet_mledger_destroy(fleet_mledger* ledger);
+/* the sizes given to create; any pointer may be NULL */
+int fleet_mledger_shape(const fleet_mledger* ledger, size_t* n_weights, size_t* n_biases, int* graph_edges,
+                        int* workers, int* max_versions);
+/* the pair kernel's launch shape, for tests and sizing: lanes per wave, values a block
+ * takes per pass, blocks per pair at most (a lane strides on beyond values * blocks) */
+int fleet_mledger_launch_shape(int* wave, int* block_values, int* max_blocks);
+/* Make version `id` resident from its weights and use_bias() biases (fleet_model_export's
+ * vectors): one pass (k_mrow_stage) writes a[i] = Q(param(i)) in getModelParams' order
+ * (network.h:708-723, the biases repeated per layer-graph edge) and the row's own
+ * getNorm (mcurr.getNorm(), Kardam.java:116). A resident id is a no-op (its content is not
+ * compared; its age is renewed). The host form synchronises; the device form runs on
+ * `stream`, and the ledger's later work is ordered after it. */
+int fleet_mledger_stage(fleet_mledger* ledger, int64_t id, const float* weights, const float* biases);
+int fleet_mledger_stage_device(fleet_mledger* ledger, int64_t id, const float* d_weights, const float* d_biases,
+                               void* stream);
+/* 1 / 0; FLEET_ERR_ARG for NULL */
+int fleet_mledger_resident(const fleet_mledger* ledger, int64_t id);
+/* setModel for K picks in pick order (CppNNUpdater.java:476, Kardam.java:114-125): pick k
+ * is version id[k] for worker[k]; worker[k] < 0 = Kardam does not run for that pick
+ * (CppNNUpdater.java:472-474, 483-484; id[k] is not looked at). status[k]:
+ *   0 skipped; 1 first model for that worker (stored, norm_diff NaN); 2 ignored (norm ==
+ *   0: nothing changes, norm_diff 0); 3 set (stored, norm_diff = the norm, NaN included).
+ * norm_model[k] = getNorm(T_v) (NaN for a skipped pick). A worker picked again later in
+ * the same update sees what its earlier pick left. The norms are getNorm's float products
+ * summed in double in another order (per wave, the waves and blocks in a fixed order: no
+ * floating-point atomics, the same bits for the same inputs on the same device); a norm
+ * that is exactly 0 in the reference is exactly 0 here.
+ * FLEET_ERR_ARG, before anything is launched and with every output and the ledger
+ * untouched: NULLs, K < 0, a worker >= workers, an id that is not resident, more distinct
+ * picked versions that no worker holds than max_versions. K = 0 or all workers < 0
+ * launches nothing. Synchronises once (the norms are host outputs); not for graph capture. */
+int fleet_mledger_update(fleet_mledger* ledger, const int64_t* id, const int32_t* worker, int K,
+                         double* norm_model, double* norm_diff, uint8_t* status);
+/* models.containsKey(worker) (Kardam.java:115): 1 / 0; FLEET_ERR_ARG for NULL or a worker
+ * outside [0, workers). */
+int fleet_mledger_has(const fleet_mledger* ledger, int worker);
+/* the id of the version models.get(worker) is; FLEET_ERR_ARG as fleet_mledger_has, or for
+ * a worker without a model (*id untouched) */
+int fleet_mledger_version(const fleet_mledger* ledger, int worker, int64_t* id);
+/* models.remove(worker): the row loses a reference (and stays resident until evicted).
+ * FLEET_ERR_ARG as fleet_mledger_version. */
+int fleet_mledger_forget(fleet_mledger* ledger, int worker);
+/* decodeFloat(models.get(worker)): the n values of the worker's row. Synchronous.
+ * FLEET_ERR_ARG as fleet_mledger_version; cap < n is FLEET_ERR_CAPACITY. */
+int fleet_mledger_read(fleet_mledger* ledger, int worker, float* params, size_t cap);
+/* the same for a resident version by id */
+int fleet_mledger_read_version(fleet_mledger* ledger, int64_t id, float* params, size_t cap);
+
 /* Self-test of the device codec arithmetic over whole input domains: an
  * order-independent 64-bit digest sum_i splitmix64(i<<32 | f(i)) of
  *   fn 0: int2float over all 2^32 codes      fn 1: float2int over all 2^32 bit patterns
@@ -714,6 +791,15 @@ double fleet_model_get_lrate(fleet_model* m);
 int fleet_model_shape(fleet_model* m, size_t* n_weights, size_t* n_biases, int* graph_edges, int* n_layers);
 /* weights / biases of models[version] (version -1: the current `cnn`) */
 int fleet_model_export(fleet_model* m, int version, float* weights, size_t n_weights, float* biases, size_t n_biases);
+/* A stable id of models[version]: the count of versions pushed before it (initUpdater's
+ * is 0). Indices into `models` shift when descentNative drops the oldest (:369-371); the
+ * id of a version never changes. FLEET_ERR_ARG for NULLs or a version outside models. */
+int fleet_model_version_id(fleet_model* m, int version, int64_t* id);
+/* fleet_mledger_stage of models[version] under its fleet_model_version_id (written to *id
+ * when not NULL): what kardam.setModel is given at CppNNUpdater.java:473-476, without the
+ * text. FLEET_ERR_ARG when the ledger's n_weights, n_biases or graph_edges differ from
+ * fleet_model_shape's, or as fleet_model_version_id. */
+int fleet_mledger_stage_model(fleet_mledger* ledger, fleet_model* m, int version, int64_t* id);
 
 /* The offline sampler's state (the CppNNOfflineSampler natives
  * of Server/src/main/c++/cppNN_backend.cpp and the globals they keep). Random
