@@ -161,6 +161,8 @@ def lib() -> C.CDLL:
         "fleet_model_quantize_index": (i32, [vp, vp, vp, i32, vp, vp, vp, vp]),
         "fleet_model_weights_text": (i32, [vp, vp, vp, i32, vp, sz, szp]),
         "fleet_model_read_weights": (i32, [vp, vp, sz, vp, i32, vp]),
+        "fleet_values_text": (i32, [vp, vp, sz, vp, i32, vp, sz, szp]),
+        "fleet_values_text_device": (i32, [vp, vp, sz, vp, i32, vp, sz, szp, vp]),
         "fleet_encode_device": (i32, [vp, vp, sz, sz, i32, vp, sz, vp]),
         "fleet_decode_device": (i32, [vp, vp, sz, sz, i32, vp, sz, vp]),
         "fleet_synth_device": (i32, [vp, C.c_uint64, i32, i32, vp, vp, i32, sz, vp, sz, vp]),
@@ -196,6 +198,31 @@ def lib() -> C.CDLL:
         "fleet_model_get_lrate": (C.c_double, [vp]),
         "fleet_model_shape": (i32, [vp, szp, szp, C.POINTER(i32), C.POINTER(i32)]),
         "fleet_model_export": (i32, [vp, i32, vp, sz, vp, sz]),
+        "fleet_ctx_device": (i32, [vp]),
+        "fleet_ctx_of_mledger": (vp, [vp]),
+        "fleet_rmodel_load": (i32, [vp, vp, sz, i32, i32, C.POINTER(vp)]),
+        "fleet_rmodel_destroy": (None, [vp]),
+        "fleet_rmodel_last_error": (C.c_char_p, [vp]),
+        "fleet_rmodel_init_updater": (i32, [vp, vp, i32]),
+        "fleet_rmodel_descent": (i32, [vp, vp, sz, i32, i32]),
+        "fleet_rmodel_descent_device": (i32, [vp, vp, sz, i32, vp]),
+        "fleet_rmodel_count": (i32, [vp]),
+        "fleet_rmodel_params_cap": (sz, [vp]),
+        "fleet_rmodel_get_params": (i32, [vp, i32, vp, sz, szp]),
+        "fleet_rmodel_get_model_params": (i32, [vp, i32, vp, sz, szp]),
+        "fleet_rmodel_get_model_params_device": (i32, [vp, i32, vp, vp]),
+        "fleet_rmodel_get_epoch": (i32, [vp]),
+        "fleet_rmodel_set_epoch": (None, [vp, i32]),
+        "fleet_rmodel_get_priority": (i32, [vp]),
+        "fleet_rmodel_set_priority": (None, [vp, i32]),
+        "fleet_rmodel_get_lrate": (C.c_double, [vp]),
+        "fleet_rmodel_shape": (i32, [vp, szp, szp, C.POINTER(i32), C.POINTER(i32)]),
+        "fleet_rmodel_export": (i32, [vp, i32, vp, sz, vp, sz]),
+        "fleet_rmodel_version_id": (i32, [vp, i32, C.POINTER(i64)]),
+        "fleet_rmodel_version_device": (i32, [vp, i32, C.POINTER(vp), C.POINTER(vp)]),
+        "fleet_rmodel_stage_mledger": (i32, [vp, vp, i32, C.POINTER(i64)]),
+        "fleet_rmodel_stats": (i32, [vp, szp, C.POINTER(i32)]),
+        "fleet_rmodel_workspace_bytes": (sz, [vp]),
         "fleet_sampler_create": (i32, [vp, C.c_char_p, i32, i32, i32, i32, i32, C.POINTER(vp)]),
         "fleet_sampler_create_from": (i32, [vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
         "fleet_sampler_destroy": (None, [vp]),
@@ -675,6 +702,37 @@ class Codec:
         buf = np.empty(max(1, need.value), np.uint8)
         self._check(self._L.fleet_model_weights_text(self._h, w.ctypes.data, d.ctypes.data, len(d) // 3,
                                                      buf.ctypes.data, need.value, C.byref(need)))
+        return buf[: need.value].tobytes()
+
+    def values_text(self, values, block_sizes=None, stream=None) -> bytes:
+        """The text of `ostream << float` ('%g') for these values, formatted on the device
+        (fleet_values_text). block_sizes: "value " per value and a newline after each block
+        (getParams' bias and mode-0 weight lines; an empty block prints its lone newline);
+        None: the "i\\nvalue\\n" pairs of the mode-1 dictionary section. `values` is a
+        numpy array, or a float32 device tensor that is read where it is."""
+        bs = None if block_sizes is None else np.ascontiguousarray(block_sizes, dtype=np.int64).reshape(-1)
+        if bs is not None and len(bs) == 0:
+            raise ValueError("block_sizes: at least one block (None selects the pairs form)")
+        nb, bp = (0, None) if bs is None else (len(bs), bs.ctypes.data)
+        if hasattr(values, "data_ptr"):
+            import torch
+            if values.dtype != torch.float32 or not values.is_cuda or not values.is_contiguous():
+                raise ValueError("values: a contiguous float32 device tensor")
+            n = values.numel()
+
+            def call(buf, cap, need):
+                return self._L.fleet_values_text_device(self._h, values.data_ptr(), n, bp, nb, buf, cap, C.byref(need),
+                                                        _stream(stream))
+        else:
+            v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+            n = len(v)
+
+            def call(buf, cap, need):
+                return self._L.fleet_values_text(self._h, v.ctypes.data, n, bp, nb, buf, cap, C.byref(need))
+        need = C.c_size_t(0)
+        cap = 14 * n + nb + 16 if bs is not None else 26 * n + 16  # 12 bytes + separators (+ an int key)
+        buf = np.empty(cap, np.uint8)
+        self._check(call(buf.ctypes.data, cap, need))
         return buf[: need.value].tobytes()
 
     def model_read_weights(self, text, dims) -> np.ndarray:
@@ -1288,10 +1346,13 @@ class ModelLedger:
             self._live(), int(version_id), weights_f32.data_ptr() if self.n_weights else None,
             biases_f32.data_ptr() if self.n_biases else None, _stream(stream)))
 
-    def stage_model(self, model: "Model", version: int) -> int:
-        """Make ``models[version]`` of a :class:`Model` resident under its ``version_id``; returns the id."""
+    def stage_model(self, model, version: int) -> int:
+        """Make ``models[version]`` of a :class:`Model` or a :class:`ResidentModel` (device to
+        device) resident under its ``version_id``; returns the id."""
         vid = C.c_int64(-1)
-        rc = self._L.fleet_mledger_stage_model(self._live(), model._h, int(version), C.byref(vid))
+        stage = (self._L.fleet_rmodel_stage_mledger if isinstance(model, ResidentModel)
+                 else self._L.fleet_mledger_stage_model)
+        rc = stage(self._live(), model._h, int(version), C.byref(vid))
         if rc != FLEET_OK:
             model._check(rc)
         return int(vid.value)
@@ -1504,6 +1565,159 @@ class Model:
         w, b = np.empty(nw, np.float32), np.empty(nb, np.float32)
         self._check(self._L.fleet_model_export(self._h, int(version), w.ctypes.data, nw, b.ctypes.data, nb))
         return w, b
+
+
+class ResidentModel:
+    """:class:`Model` with ``cnn`` and ``models`` resident in HBM (fleet_rmodel): the same
+    natives under the same names, bit for bit the same results. A step takes the merged
+    gradient where ``update_device`` left it (``descent_device``), a new version is staged
+    in a :class:`ModelLedger` device to device, and the parameter texts are formatted on
+    the device; no weight travels host to device after the load.
+
+    HBM: ``stats()['resident_bytes'] = 4 * roundup64(n_weights + n_biases) *
+    (max_versions + 2)`` -- cnn and a ring of ``max_versions + 1`` version rows (descentNative
+    pushes before it pops) -- plus ``stats()['workspace_bytes']`` allocated once at load.
+    ``stale_size`` of a step may not exceed ``max_versions``."""
+
+    def __init__(self, codec: "Codec", params_text, distillation_mode: int = 1, max_versions: int = 8):
+        t = _as_bytes(params_text)
+        h = C.c_void_p()
+        rc = codec._L.fleet_rmodel_load(codec._h, t, len(t), int(distillation_mode), int(max_versions), C.byref(h))
+        if rc != FLEET_OK:
+            raise FleetError(rc, "fleet_rmodel_load failed (see stderr): not a supported getParams text")
+        self._h, self._L, self.codec = h, codec._L, codec
+        self.max_versions = int(max_versions)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.fleet_rmodel_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != FLEET_OK:
+            msg = self._L.fleet_rmodel_last_error(self._h).decode(errors="replace")
+            raise (LayoutError if rc == FLEET_ERR_LAYOUT else Base64Error if rc == FLEET_ERR_BASE64 else FleetError)(rc, msg)
+
+    def _device_tensor(self, t, dtype: str, name: str) -> None:
+        """A kernel is handed t.data_ptr(): anything but a contiguous tensor of that type on the
+        codec's device is refused here."""
+        import torch
+        if (not isinstance(t, torch.Tensor) or t.dtype != getattr(torch, dtype) or not t.is_cuda
+                or t.device.index != self.codec.device or not t.is_contiguous()):
+            raise ValueError(f"{name}: a contiguous {dtype} tensor on cuda:{self.codec.device}")
+
+    def initUpdater(self, lrates) -> None:  # noqa: N802
+        lr = np.ascontiguousarray(lrates, dtype=np.float64)
+        self._check(self._L.fleet_rmodel_init_updater(self._h, lr.ctypes.data, len(lr)))
+
+    def descentNative(self, merged, client_batch_size: int, stale_size: int) -> None:  # noqa: N802
+        m = _as_bytes(merged)
+        self._check(self._L.fleet_rmodel_descent(self._h, m, len(m), int(client_batch_size), int(stale_size)))
+
+    def descent_device(self, merged_f32, stale_size: int, stream=None, n_values: Optional[int] = None) -> None:
+        """descentNative from decodeFloat of the merged text in a float32 device tensor (what
+        ``update_device`` / ``Pool.update_device`` / ``Ledger.update_device`` write); the first
+        ``n_values`` floats (default: all of them) are the gradient."""
+        self._device_tensor(merged_f32, "float32", "merged_f32")
+        n = merged_f32.numel() if n_values is None else int(n_values)
+        if n < 0 or n > merged_f32.numel():
+            raise ValueError("n_values exceeds the tensor")
+        self._check(self._L.fleet_rmodel_descent_device(self._h, merged_f32.data_ptr(), n, int(stale_size),
+                                                        _stream(stream)))
+
+    def modelsSize(self) -> int:  # noqa: N802
+        return self._L.fleet_rmodel_count(self._h)
+
+    def getParametersNative(self, priority: int) -> bytes:  # noqa: N802
+        cap = self._L.fleet_rmodel_params_cap(self._h)
+        out = np.empty(max(1, cap), np.uint8)
+        need = C.c_size_t(0)
+        self._check(self._L.fleet_rmodel_get_params(self._h, int(priority), out.ctypes.data, cap, C.byref(need)))
+        return out[: need.value].tobytes()
+
+    def getModelParametersNative(self, priority: int) -> bytes:  # noqa: N802
+        nw, nb, ge, _ = self.shape()
+        cap = b64_len(nb * ge + nw)
+        out = np.empty(max(1, cap), np.uint8)
+        need = C.c_size_t(0)
+        self._check(self._L.fleet_rmodel_get_model_params(self._h, int(priority), out.ctypes.data, cap, C.byref(need)))
+        return out[: need.value].tobytes()
+
+    def getModelParametersNative_device(self, priority: int, out_u8, stream=None) -> int:  # noqa: N802
+        """The a20 text into a uint8 device tensor (its length rounded up to 16, plus 16, at
+        least); returns the text's length."""
+        self._device_tensor(out_u8, "uint8", "out_u8")
+        nw, nb, ge, _ = self.shape()
+        n = b64_len(nb * ge + nw)
+        if out_u8.numel() < (n + 15) // 16 * 16 + 16:
+            raise ValueError("out_u8 smaller than the text's 16-byte groups")
+        self._check(self._L.fleet_rmodel_get_model_params_device(self._h, int(priority), out_u8.data_ptr(),
+                                                                 _stream(stream)))
+        return n
+
+    def getCurrEpoch(self) -> int:  # noqa: N802
+        return self._L.fleet_rmodel_get_epoch(self._h)
+
+    def setCurrEpoch(self, e: int) -> None:  # noqa: N802
+        self._L.fleet_rmodel_set_epoch(self._h, int(e))
+
+    def getPriority(self) -> int:  # noqa: N802
+        return self._L.fleet_rmodel_get_priority(self._h)
+
+    def setPriority(self, p: int) -> None:  # noqa: N802
+        self._L.fleet_rmodel_set_priority(self._h, int(p))
+
+    def getLrate(self) -> float:  # noqa: N802
+        return self._L.fleet_rmodel_get_lrate(self._h)
+
+    def shape(self):
+        nw, nb = C.c_size_t(0), C.c_size_t(0)
+        ge, nl = C.c_int(0), C.c_int(0)
+        self._check(self._L.fleet_rmodel_shape(self._h, C.byref(nw), C.byref(nb), C.byref(ge), C.byref(nl)))
+        return nw.value, nb.value, ge.value, nl.value
+
+    def version_id(self, version: int) -> int:
+        vid = C.c_int64(-1)
+        self._check(self._L.fleet_rmodel_version_id(self._h, int(version), C.byref(vid)))
+        return int(vid.value)
+
+    def version_tensors(self, version: int = -1):
+        """(weights, biases) of models[version] (-1: cnn) as float32 tensors over the resident
+        row itself: no copy, valid until that version is dropped."""
+        import torch
+        nw, nb, _, _ = self.shape()
+        pw, pb = C.c_void_p(), C.c_void_p()
+        self._check(self._L.fleet_rmodel_version_device(self._h, int(version), C.byref(pw), C.byref(pb)))
+
+        def view(ptr, n):
+            if n == 0:
+                return torch.empty(0, dtype=torch.float32, device=f"cuda:{self.codec.device}")
+            iface = {"shape": (n,), "typestr": "<f4", "data": (ptr.value, False), "version": 2}
+            holder = type("_Row", (), {"__cuda_array_interface__": iface})()
+            return torch.as_tensor(holder, device=f"cuda:{self.codec.device}")
+        return view(pw, nw), view(pb, nb)
+
+    def kardam_ledger(self, workers: int, max_versions: Optional[int] = None) -> "ModelLedger":
+        nw, nb, ge, _ = self.shape()
+        return self.codec.model_ledger(nw, nb, ge, workers, max_versions)
+
+    def export(self, version: int = -1):
+        nw, nb, _, _ = self.shape()
+        w, b = np.empty(nw, np.float32), np.empty(nb, np.float32)
+        self._check(self._L.fleet_rmodel_export(self._h, int(version), w.ctypes.data, nw, b.ctypes.data, nb))
+        return w, b
+
+    def stats(self) -> dict:
+        rb, na = C.c_size_t(0), C.c_int(0)
+        self._check(self._L.fleet_rmodel_stats(self._h, C.byref(rb), C.byref(na)))
+        return {"resident_bytes": rb.value, "device_allocs": na.value,
+                "workspace_bytes": self._L.fleet_rmodel_workspace_bytes(self._h)}
 
 
 class ByteVec:

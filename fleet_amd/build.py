@@ -30,7 +30,8 @@ COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "
 SOURCES = [("kernels.hip", True), ("stream_kernels.hip", True), ("acc_kernels.hip", True), ("model_codec.hip", True),
            ("mledger_kernels.hip", True), ("mledger_table.cpp", False),
            ("fleet_codec.cpp", True), ("launch_plan.cpp", False),  # (file, needs HIP)
-           ("model_state.cpp", True), ("teacher.hip", True), ("sampler_state.cpp", True)]
+           ("model_state.cpp", True), ("teacher.hip", True), ("sampler_state.cpp", True),
+           ("rmodel_kernels.hip", True), ("rmodel_state.cpp", True)]
 
 
 def _newer(target: str, deps) -> bool:

@@ -18,7 +18,9 @@
 // multiplications on 192-bit integers; the remainder decides the rounding.
 // Checked against libc (snprintf + strtof) on every finite binary32: digest
 // fn 22 (fleet_selftest_digest) against tests/golden/digests.json, and on the
-// CPU by tests/native/check_math.cpp g6.
+// CPU by tests/native/check_math.cpp g6. g6_text writes the text of step 1
+// itself (`ostream << v`), checked against snprintf("%g") on every binary32
+// by tests/native/check_g6text.cpp and digest fn 24.
 #pragma once
 #include <stdint.h>
 
@@ -126,10 +128,11 @@ FLEET_HD float ldexp_exact(float m, int e) {
   return (m * pow2f(e + 64)) * 0x1p-64f;
 }
 
-// strtof(sprintf("%.6g", (double)v)) for finite v.
-FLEET_HD float g6_roundtrip(float v) {
-  const uint32_t bits = f2u(v), a = bits & 0x7fffffffu, sign = bits & 0x80000000u;
-  if (a == 0) return v;  // "0" / "-0"
+// The six significant digits N in [10^5, 10^6) and the decimal exponent E of
+// `%.6g` for a finite non-zero v: |v| rounds (half-even on the exact binary
+// value) to N * 10^(E-5). Step 1 of the round trip, and what g6_text prints.
+FLEET_HD void g6_digits(float v, uint32_t* N_out, int* E_out) {
+  const uint32_t a = f2u(v) & 0x7fffffffu;
   const uint32_t be = a >> 23, mant = a & 0x7fffffu;
   const uint64_t m = be ? (uint64_t)(mant | 0x800000u) : (uint64_t)mant;
   const int e = be ? (int)be - 150 : -149;  // |v| = m * 2^e
@@ -192,6 +195,99 @@ FLEET_HD float g6_roundtrip(float v) {
     }
     break;
   }
+  *N_out = (uint32_t)N;
+  *E_out = E;
+}
+
+// The bytes of `ostream << v` at the default precision, i.e. snprintf("%g"):
+// fixed notation for -4 <= E < 6, scientific otherwise (a sign and two exponent
+// digits: binary32 never needs three), trailing zeros and a bare point
+// stripped; 0, -0, inf, -inf, nan, -nan for the rest. Returns the length, at
+// most kG6TextMax (-1.17549e-38, -0.000123456); no terminator is written.
+// Checked against libc on every binary32 by tests/native/check_g6text.cpp and
+// digest fn 24 (tests/golden/g6text_digest.json).
+constexpr int kG6TextMax = 12;
+
+FLEET_HD int g6_text(float v, char* out) {
+  const uint32_t bits = f2u(v), a = bits & 0x7fffffffu;
+  int n = 0;
+  if (bits >> 31) out[n++] = '-';
+  if (a == 0) {
+    out[n++] = '0';
+    return n;
+  }
+  if (a >= 0x7f800000u) {
+    const bool inf = a == 0x7f800000u;
+    out[n++] = inf ? 'i' : 'n';
+    out[n++] = inf ? 'n' : 'a';
+    out[n++] = inf ? 'f' : 'n';
+    return n;
+  }
+  uint32_t N;
+  int E;
+  g6_digits(v, &N, &E);
+  char d[6];
+  int nd = 0;  // significant digits left once the trailing zeros are gone
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {
+    const uint32_t q = N / 10u;
+    d[i] = (char)('0' + (N - 10u * q));
+    if (nd == 0 && d[i] != '0') nd = i + 1;
+    N = q;
+  }
+  if (E >= -4 && E < 6) {
+    if (E >= 0) {
+      for (int i = 0; i <= E; ++i) out[n++] = d[i];
+      if (nd > E + 1) {
+        out[n++] = '.';
+        for (int i = E + 1; i < nd; ++i) out[n++] = d[i];
+      }
+    } else {
+      out[n++] = '0';
+      out[n++] = '.';
+      for (int i = -1; i > E; --i) out[n++] = '0';
+      for (int i = 0; i < nd; ++i) out[n++] = d[i];
+    }
+    return n;
+  }
+  out[n++] = d[0];
+  if (nd > 1) {
+    out[n++] = '.';
+    for (int i = 1; i < nd; ++i) out[n++] = d[i];
+  }
+  out[n++] = 'e';
+  out[n++] = E < 0 ? '-' : '+';
+  const uint32_t ae = (uint32_t)(E < 0 ? -E : E);  // <= 45
+  out[n++] = (char)('0' + ae / 10u);
+  out[n++] = (char)('0' + ae % 10u);
+  return n;
+}
+
+// The digest term of one input's text (order-independent sum over inputs): the
+// bytes zero-padded to 12, little-endian in lo (0..7) and hi (8..11).
+FLEET_HD uint64_t g6_text_mix(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+FLEET_HD uint64_t g6_text_term(uint32_t u, const char* t, int len) {
+  uint64_t lo = 0, hi = 0;
+  for (int i = 0; i < len; ++i) {
+    const uint64_t b = (uint8_t)t[i];
+    if (i < 8) lo |= b << (8 * i);
+    else hi |= b << (8 * (i - 8));
+  }
+  return g6_text_mix(g6_text_mix(((uint64_t)u << 32) | hi) ^ lo);
+}
+
+// strtof(sprintf("%.6g", (double)v)) for finite v.
+FLEET_HD float g6_roundtrip(float v) {
+  const uint32_t bits = f2u(v), a = bits & 0x7fffffffu, sign = bits & 0x80000000u;
+  if (a == 0) return v;  // "0" / "-0"
+  uint32_t N = 0;
+  int E = 0;
+  g6_digits(v, &N, &E);
   // 2. strtof: the binary32 nearest to N * 10^p
   const int p = E - 5;
   float y;

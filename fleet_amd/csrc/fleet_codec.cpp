@@ -508,6 +508,8 @@ int fleet_sync(fleet_ctx* c, void* stream) {
   return FLEET_OK;
 }
 
+int fleet_ctx_device(const fleet_ctx* c) { return c ? c->device : -1; }
+
 int fleet_check(fleet_ctx* c, void* stream) {
   if (!c) return FLEET_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
@@ -1313,6 +1315,64 @@ int fleet_model_weights_text(fleet_ctx* c, const float* weights, const int32_t* 
   std::memcpy(out, head.data(), head.size());
   if (!body.empty()) std::memcpy(out + head.size(), body.data(), body.size());
   return FLEET_OK;
+}
+
+namespace {
+
+// the block offsets of fleet_values_text's sizes; empty for the pairs form
+static int values_offsets(fleet_ctx* c, size_t n, const int64_t* block_sizes, int n_blocks, std::vector<int64_t>* off) {
+  if (n_blocks < 0 || (n_blocks && !block_sizes)) return fail(c, FLEET_ERR_ARG, "values text: bad blocks");
+  if (n > (size_t)INT32_MAX) return fail(c, FLEET_ERR_ARG, "values text: %zu values (the limit is 2^31 - 1)", n);
+  off->assign((size_t)n_blocks + 1, 0);
+  for (int j = 0; j < n_blocks; ++j) {
+    if (block_sizes[j] < 0) return fail(c, FLEET_ERR_ARG, "values text: negative block size");
+    (*off)[(size_t)j + 1] = (*off)[(size_t)j] + block_sizes[j];
+  }
+  if (n_blocks && (size_t)off->back() != n)
+    return fail(c, FLEET_ERR_ARG, "values text: the blocks hold %lld values, not %zu", (long long)off->back(), n);
+  return FLEET_OK;
+}
+
+static int values_text_out(fleet_ctx* c, const float* d_values, size_t n, const std::vector<int64_t>& off,
+                           int n_blocks, char* out, size_t cap, size_t* out_len, hipStream_t s) {
+  std::vector<char> text;
+  const hipError_t e = fleet::model_values_text(d_values, (int64_t)n, off.data(), n_blocks, &text, s);
+  if (e == hipErrorInvalidValue)
+    return fail(c, FLEET_ERR_ARG, "values text: more than 254 empty blocks in a row");
+  HIP_TRY(c, e);
+  if (out_len) *out_len = text.size();
+  if (!out || cap < text.size()) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu", cap, text.size());
+  if (!text.empty()) std::memcpy(out, text.data(), text.size());
+  return FLEET_OK;
+}
+
+}  // namespace
+
+int fleet_values_text_device(fleet_ctx* c, const void* d_values, size_t n, const int64_t* block_sizes, int n_blocks,
+                             char* out, size_t cap, size_t* out_len, void* stream) {
+  if (!c || (n && !d_values)) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(c->mu);
+  std::vector<int64_t> off;
+  int rc = values_offsets(c, n, block_sizes, n_blocks, &off);
+  if (rc) return rc;
+  DEVICE_SCOPE(c);
+  return values_text_out(c, (const float*)d_values, n, off, n_blocks, out, cap, out_len, pick(c, stream));
+}
+
+int fleet_values_text(fleet_ctx* c, const float* values, size_t n, const int64_t* block_sizes, int n_blocks, char* out,
+                      size_t cap, size_t* out_len) {
+  if (!c || (n && !values)) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(c->mu);
+  std::vector<int64_t> off;
+  int rc = values_offsets(c, n, block_sizes, n_blocks, &off);
+  if (rc) return rc;
+  DEVICE_SCOPE(c);
+  DevMem dv;
+  if (n) {
+    HIP_TRY(c, hipMalloc(&dv.p, n * sizeof(float)));
+    HIP_TRY(c, hipMemcpyAsync(dv.p, values, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  }
+  return values_text_out(c, (const float*)dv.p, n, off, n_blocks, out, cap, out_len, c->stream);
 }
 
 int fleet_model_read_weights(fleet_ctx* c, const char* text, size_t len, const int32_t* dims, int n_mats,
@@ -2896,6 +2956,8 @@ void fleet_mledger_destroy(fleet_mledger* l) {
   release_mledger(l);
 }
 
+fleet_ctx* fleet_ctx_of_mledger(const fleet_mledger* l) { return l ? l->c : nullptr; }
+
 int fleet_mledger_shape(const fleet_mledger* l, size_t* n_weights, size_t* n_biases, int* graph_edges, int* workers,
                         int* max_versions) {
   if (!l) return FLEET_ERR_ARG;
@@ -3068,7 +3130,7 @@ const char* fleet_plan(void) {
 
 int fleet_selftest_digest(fleet_ctx* c, int fn, uint64_t* out) {
   if (!c || !out) return FLEET_ERR_ARG;
-  if (fn < 0 || fn > 23) return fail(c, FLEET_ERR_ARG, "no self-test function %d", fn);
+  if (fn < 0 || fn > 24) return fail(c, FLEET_ERR_ARG, "no self-test function %d", fn);
   std::lock_guard<std::mutex> lk(c->mu);
   DEVICE_SCOPE(c);
   unsigned long long* d = nullptr;

@@ -17,6 +17,7 @@
 
 #include "codec_device.h"
 #include "decimal6.h"
+#include "descent_math.h"
 #include "teacher_math.h"
 
 // Experiment switches of the stream kernels (r05 A/Bs; the defaults are the product):
@@ -2748,16 +2749,8 @@ __global__ void k_synth_headers(float* __restrict__ out, size_t vpitch, const in
 // network.h:1185-1202,1334-1353. Per segment: a weight block (kind 0,
 // sgd::increment_w, solver.h:88-94: w -= lr*(dW + 0*w)) or a fully-connected
 // layer's bias block (kind 1, update_bias, layer.h:241-243: b -= db*lr), each
-// op one fp32 rounding as in the reference's SSE build (no contraction).
-// NaN results as the reference's x86 SSE build produces them (the GPU's own
-// canonical NaN is 0x7FC00000): a NaN operand propagates quieted, the
-// instruction's first operand winning; an invalid operation gives 0xFFC00000.
-__device__ __forceinline__ float x86_nan(float a, float b, float r) {
-  if (r == r) return r;
-  if (a != a) return u2f(f2u(a) | 0x00400000u);
-  if (b != b) return u2f(f2u(b) | 0x00400000u);
-  return u2f(0xFFC00000u);
-}
+// op one fp32 rounding as in the reference's SSE build (no contraction); the
+// two update bodies and their x86 NaN rule are descent_math.h's.
 
 __global__ void __launch_bounds__(256) k_descent(float* __restrict__ weights, float* __restrict__ fc_bias,
                                                  const float* __restrict__ grad, DescentSegs segs, float lr) {
@@ -2767,15 +2760,10 @@ __global__ void __launch_bounds__(256) k_descent(float* __restrict__ weights, fl
   const float g = grad[segs.grad_off[sg] + i];
   if (segs.kind[sg] == 0) {
     float* w = weights + segs.model_off[sg] + i;
-    const float x = *w;
-    const float t = x86_nan(0.0f, x, 0.0f * x);  // w_decay * w
-    const float u = x86_nan(t, g, t + g);        // dW + t (the product is the x86 first operand)
-    const float v = x86_nan(lr, u, lr * u);
-    *w = x86_nan(x, v, x - v);
+    *w = descent_weight(*w, g, lr);
   } else {
     float* b = fc_bias + segs.model_off[sg] + i;
-    const float v = x86_nan(g, lr, g * lr);
-    *b = x86_nan(*b, v, *b - v);
+    *b = descent_bias(*b, g, lr);
   }
 }
 
@@ -3192,6 +3180,10 @@ __global__ void __launch_bounds__(256) k_digest(int fn, unsigned long long* __re
                o = use ? f2u(g6_roundtrip(x)) : 0u; break; }
       case 18: { const float e = glibc_expf(u2f(u));                 // the teacher's expf (libm's)
                o = e != e ? 0x7fc00000u : f2u(e); break; }
+      case 24: { char t[kG6TextMax];                                  // `ostream << float`: the text itself
+               const int l = g6_text(u2f(u), t);
+               sum += g6_text_term(u, t, l);
+               o = 0; use = false; break; }
       default: o = 0; use = false;
     }
     if (use) sum += splitmix64(((uint64_t)u << 32) | o);

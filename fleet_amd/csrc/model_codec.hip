@@ -294,6 +294,77 @@ __global__ void __launch_bounds__(256) k_text_write(const int32_t* __restrict__ 
   if (i + 1 == off[j + 1]) p[l + 1] = '\n';
 }
 
+// ------------------------------------------------------------ value text
+// `ostream << float` (decimal6.h g6_text) for a run of n values, in the shape of
+// k_text_len / k_text_write. The exact digits cost a few hundred integer
+// operations, so they are derived once: k_vtext_len leaves each value's bytes
+// in a 16-byte cell (bytes 0..11 text, byte 12 its length) and k_vtext_write
+// only copies them to the scanned position.
+//   lines (n_blocks > 0): "value " per value, '\n' after a block's last value;
+//     a block of size 0 still prints its lone '\n' -- those of the blocks before
+//     the first value ride with value 0, the others with the value before them.
+//   pairs (n_blocks == 0): "i\nvalue\n", the mode-1 dictionary section.
+struct VCell {
+  char t[12];
+  uint8_t len, lead, trail, pad;  // '\n's before (value 0 only) and after this value's "text "
+};
+static_assert(sizeof(VCell) == 16, "one 16-byte cell per value");
+
+__global__ void __launch_bounds__(256) k_vtext_len(const float* __restrict__ v, int64_t n,
+                                                   const int64_t* __restrict__ off, int n_blocks,
+                                                   VCell* __restrict__ cell, int64_t* __restrict__ len) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  VCell c;
+#pragma unroll
+  for (int k = 0; k < 12; ++k) c.t[k] = 0;
+  c.len = (uint8_t)g6_text(v[i], c.t);
+  c.lead = c.trail = c.pad = 0;
+  int64_t l = c.len + 1;
+  if (n_blocks > 0) {
+    const int j = mat_of(off, n_blocks, i);  // off[j] <= i < off[j + 1]: never an empty block
+    int lead = 0, trail = 0;
+    if (i == 0) lead = j;  // every block before value 0's is empty
+    if (i + 1 == off[j + 1])
+      for (int k = j + 1; k <= n_blocks && off[k] == i + 1; ++k) ++trail;
+    // more than 254 empty blocks in a row do not fit the cell's counters: the host refuses them
+    c.lead = (uint8_t)lead;
+    c.trail = (uint8_t)trail;
+    l += lead + trail;
+  } else {
+    l += dec_len((int32_t)i) + 1;
+  }
+  cell[i] = c;
+  len[i] = l;
+}
+
+__global__ void __launch_bounds__(256) k_vtext_write(const VCell* __restrict__ cell, int64_t n, int n_blocks,
+                                                     const int64_t* __restrict__ pos, char* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const VCell c = cell[i];
+  char* p = out + pos[i];
+  if (n_blocks > 0) {
+    for (int k = 0; k < c.lead; ++k) *p++ = '\n';
+  } else {
+    const int l = dec_len((int32_t)i);
+    uint32_t a = (uint32_t)i;
+    for (int q = l - 1; q >= 0; --q) {
+      p[q] = (char)('0' + a % 10u);
+      a /= 10u;
+    }
+    p += l;
+    *p++ = '\n';
+  }
+  for (int k = 0; k < c.len; ++k) *p++ = c.t[k];
+  if (n_blocks > 0) {
+    *p++ = ' ';
+    for (int k = 0; k < c.trail; ++k) *p++ = '\n';
+  } else {
+    *p++ = '\n';
+  }
+}
+
 // ------------------------------------------------------------ read (a19)
 
 __device__ __forceinline__ bool is_ws(uint8_t c) { return c == ' ' || c == '\n' || c == '\t' || c == '\r'; }
@@ -346,9 +417,17 @@ inline unsigned nb(int64_t n) { return (unsigned)((n + 255) / 256); }
 template <typename T>
 struct DevBuf {
   T* p = nullptr;
+  bool own = true;
   hipError_t alloc(size_t n) { return hipMalloc((void**)&p, sizeof(T) * (n ? n : 1)); }
+  // a caller-owned workspace's buffer when there is one, else an allocation of n
+  hipError_t take(T* from_ws, size_t n) {
+    if (!from_ws) return alloc(n);
+    p = from_ws;
+    own = false;
+    return hipSuccess;
+  }
   ~DevBuf() {
-    if (p) (void)hipFree(p);
+    if (p && own) (void)hipFree(p);
   }
 };
 
@@ -361,7 +440,7 @@ struct DevBuf {
 }  // namespace
 
 hipError_t model_quantize_index(const float* d_w, const int32_t* h_dims, int n_mats, float* d_wq, float* d_dict,
-                                int32_t* d_index, int32_t* h_U, hipStream_t s, bool quantize) {
+                                int32_t* d_index, int32_t* h_U, hipStream_t s, bool quantize, const DictWs* ws) {
   std::vector<int64_t> off(n_mats + 1, 0);
   for (int j = 0; j < n_mats; ++j) off[j + 1] = off[j] + (int64_t)h_dims[3 * j] * h_dims[3 * j + 1] * h_dims[3 * j + 2];
   const int64_t n = off[n_mats];
@@ -370,9 +449,9 @@ hipError_t model_quantize_index(const float* d_w, const int32_t* h_dims, int n_m
   DevBuf<int64_t> d_off;
   DevBuf<int32_t> d_dims;
   DevBuf<MatParams> d_prm;
-  MC_TRY(d_off.alloc(n_mats + 1));
-  MC_TRY(d_dims.alloc(3 * n_mats));
-  MC_TRY(d_prm.alloc(n_mats));
+  MC_TRY(d_off.take(ws ? ws->off : nullptr, n_mats + 1));
+  MC_TRY(d_dims.take(ws ? ws->dims : nullptr, 3 * n_mats));
+  MC_TRY(d_prm.take(ws ? (MatParams*)ws->prm : nullptr, n_mats));
   MC_TRY(hipMemcpyAsync(d_off.p, off.data(), sizeof(int64_t) * (n_mats + 1), hipMemcpyHostToDevice, s));
   MC_TRY(hipMemcpyAsync(d_dims.p, h_dims, sizeof(int32_t) * 3 * n_mats, hipMemcpyHostToDevice, s));
   if (quantize) {
@@ -387,18 +466,18 @@ hipError_t model_quantize_index(const float* d_w, const int32_t* h_dims, int n_m
   DevBuf<uint32_t> key, key2;
   DevBuf<int32_t> idx, sidx, start, cid, cbeg, creator, scratch, rank, flag32;
   DevBuf<uint8_t> is_creator;
-  MC_TRY(key.alloc(n));
-  MC_TRY(key2.alloc(n));
-  MC_TRY(idx.alloc(n));
-  MC_TRY(sidx.alloc(n));
-  MC_TRY(start.alloc(n));
-  MC_TRY(cid.alloc(n));
-  MC_TRY(cbeg.alloc(n + 1));
-  MC_TRY(creator.alloc(n));
-  MC_TRY(scratch.alloc(n));
-  MC_TRY(rank.alloc(n));
-  MC_TRY(flag32.alloc(n));
-  MC_TRY(is_creator.alloc(n));
+  MC_TRY(key.take(ws ? ws->key : nullptr, n));
+  MC_TRY(key2.take(ws ? ws->key2 : nullptr, n));
+  MC_TRY(idx.take(ws ? ws->idx : nullptr, n));
+  MC_TRY(sidx.take(ws ? ws->sidx : nullptr, n));
+  MC_TRY(start.take(ws ? ws->start : nullptr, n));
+  MC_TRY(cid.take(ws ? ws->cid : nullptr, n));
+  MC_TRY(cbeg.take(ws ? ws->cbeg : nullptr, n + 1));
+  MC_TRY(creator.take(ws ? ws->creator : nullptr, n));
+  MC_TRY(scratch.take(ws ? ws->scratch : nullptr, n));
+  MC_TRY(rank.take(ws ? ws->rank : nullptr, n));
+  MC_TRY(flag32.take(ws ? ws->flag32 : nullptr, n));
+  MC_TRY(is_creator.take(ws ? ws->is_creator : nullptr, n));
   hipLaunchKernelGGL(k_dict_keys, dim3(nb(n)), dim3(256), 0, s, d_wq, n, key.p, idx.p);
   size_t tmp_bytes = 0, t2 = 0, t3 = 0;
   MC_TRY(sort_pairs(nullptr, tmp_bytes, key.p, key2.p, idx.p, sidx.p, n, s));
@@ -406,7 +485,8 @@ hipError_t model_quantize_index(const float* d_w, const int32_t* h_dims, int n_m
   MC_TRY(exclusive_sum(nullptr, t3, flag32.p, rank.p, n, s));
   tmp_bytes = std::max(tmp_bytes, std::max(t2, t3));
   DevBuf<uint8_t> tmp;
-  MC_TRY(tmp.alloc(tmp_bytes));
+  if (ws && ws->tmp_bytes < tmp_bytes) return hipErrorInvalidValue;  // (sized by model_dict_ws_carve for this n)
+  MC_TRY(tmp.take(ws ? (uint8_t*)ws->tmp : nullptr, tmp_bytes));
   MC_TRY(sort_pairs(tmp.p, tmp_bytes, key.p, key2.p, idx.p, sidx.p, n, s));
   hipLaunchKernelGGL(k_dict_starts, dim3(nb(n)), dim3(256), 0, s, d_wq, sidx.p, n, start.p);
   size_t tb = tmp_bytes;
@@ -519,6 +599,121 @@ hipError_t model_index_text(const int32_t* d_index, const int32_t* h_dims, int n
     p = q;
   }
   return hipSuccess;
+}
+
+hipError_t model_values_text(const float* d_v, int64_t n, const int64_t* h_off, int n_blocks, std::vector<char>* out,
+                             hipStream_t s) {
+  out->clear();
+  if (n == 0) {  // nothing but the empty blocks' '\n's
+    out->assign((size_t)std::max(0, n_blocks), '\n');
+    return hipSuccess;
+  }
+  if (n_blocks > 0) {
+    if (h_off[0] != 0 || h_off[n_blocks] != n) return hipErrorInvalidValue;
+    int run = 0;
+    for (int j = 0; j < n_blocks; ++j) {
+      if (h_off[j + 1] < h_off[j]) return hipErrorInvalidValue;
+      run = h_off[j + 1] == h_off[j] ? run + 1 : 0;
+      // VCell's 8-bit counters: `trail` holds a block's own '\n' and those of the empty
+      // blocks after it, `lead` those before value 0
+      if (run > 254) return hipErrorInvalidValue;
+    }
+  } else if (n > 0x7fffffff) {
+    return hipErrorInvalidValue;  // the pairs' keys are ints
+  }
+  DevBuf<int64_t> d_off;
+  DevBuf<uint8_t> wsmem;
+  MC_TRY(d_off.alloc((size_t)n_blocks + 1));
+  TextWs ws;
+  const size_t ws_bytes = model_text_ws_carve(nullptr, n, &ws);
+  if (!ws_bytes) return hipErrorUnknown;
+  MC_TRY(wsmem.alloc(ws_bytes));
+  model_text_ws_carve(wsmem.p, n, &ws);
+  if (n_blocks > 0)
+    MC_TRY(hipMemcpyAsync(d_off.p, h_off, sizeof(int64_t) * ((size_t)n_blocks + 1), hipMemcpyHostToDevice, s));
+  // 12 bytes and a separator per value, an int key and its newline (pairs) or the blocks' newlines
+  const int64_t cap = n_blocks > 0 ? 13 * n + n_blocks : 24 * n;
+  DevBuf<char> txt;
+  MC_TRY(txt.alloc((size_t)cap));
+  int64_t total = 0;
+  MC_TRY(model_values_text_ws(d_v, n, d_off.p, n_blocks, ws, txt.p, cap, &total, s));
+  out->resize((size_t)total);
+  MC_TRY(hipMemcpyAsync(out->data(), txt.p, (size_t)total, hipMemcpyDeviceToHost, s));
+  return hipStreamSynchronize(s);
+}
+
+size_t model_text_ws_carve(void* base, int64_t n, TextWs* ws) {
+  Carver c{(uint8_t*)base};
+  ws->len = c.take<int64_t>((size_t)n);
+  ws->pos = c.take<int64_t>((size_t)n);
+  ws->cell = c.take<VCell>((size_t)n);
+  size_t tb = 0;
+  if (n > 0 && exclusive_sum<int64_t>(nullptr, tb, nullptr, nullptr, (size_t)n, nullptr) != hipSuccess) return 0;
+  ws->tmp_bytes = tb;
+  ws->tmp = c.take<uint8_t>(tb);
+  return c.at;
+}
+
+size_t model_dict_ws_carve(void* base, int64_t n, int n_mats, DictWs* ws) {
+  Carver c{(uint8_t*)base};
+  const size_t m = (size_t)n;
+  ws->off = c.take<int64_t>((size_t)n_mats + 1);
+  ws->dims = c.take<int32_t>(3 * (size_t)n_mats);
+  ws->prm = c.take<MatParams>((size_t)n_mats);
+  ws->key = c.take<uint32_t>(m);
+  ws->key2 = c.take<uint32_t>(m);
+  ws->idx = c.take<int32_t>(m);
+  ws->sidx = c.take<int32_t>(m);
+  ws->start = c.take<int32_t>(m);
+  ws->cid = c.take<int32_t>(m);
+  ws->cbeg = c.take<int32_t>(m + 1);
+  ws->creator = c.take<int32_t>(m);
+  ws->scratch = c.take<int32_t>(m);
+  ws->rank = c.take<int32_t>(m);
+  ws->flag32 = c.take<int32_t>(m);
+  ws->is_creator = c.take<uint8_t>(m);
+  size_t t1 = 0, t2 = 0, t3 = 0;
+  if (n > 0 && (sort_pairs(nullptr, t1, nullptr, nullptr, nullptr, nullptr, m, nullptr) != hipSuccess ||
+                inclusive_sum<int32_t>(nullptr, t2, nullptr, nullptr, m, nullptr) != hipSuccess ||
+                exclusive_sum<int32_t>(nullptr, t3, nullptr, nullptr, m, nullptr) != hipSuccess))
+    return 0;
+  ws->tmp_bytes = std::max(t1, std::max(t2, t3));
+  ws->tmp = c.take<uint8_t>(ws->tmp_bytes);
+  return c.at;
+}
+
+// scan the lengths, read the total back, refuse a text the buffer cannot hold
+static hipError_t text_positions(int64_t n, const TextWs& ws, int64_t cap, int64_t* h_total, hipStream_t s) {
+  size_t tb = ws.tmp_bytes;
+  MC_TRY(exclusive_sum(ws.tmp, tb, ws.len, ws.pos, (size_t)n, s));
+  int64_t last_pos = 0, last_len = 0;
+  MC_TRY(hipMemcpyAsync(&last_pos, ws.pos + (n - 1), sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  MC_TRY(hipMemcpyAsync(&last_len, ws.len + (n - 1), sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  MC_TRY(hipStreamSynchronize(s));
+  *h_total = last_pos + last_len;
+  return *h_total > cap ? hipErrorOutOfMemory : hipSuccess;
+}
+
+hipError_t model_values_text_ws(const float* d_v, int64_t n, const int64_t* d_off, int n_blocks, const TextWs& ws,
+                                char* d_out, int64_t cap, int64_t* h_total, hipStream_t s) {
+  *h_total = 0;
+  if (n <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_vtext_len, dim3(nb(n)), dim3(256), 0, s, d_v, n, d_off, n_blocks, (VCell*)ws.cell, ws.len);
+  MC_TRY(hipGetLastError());
+  MC_TRY(text_positions(n, ws, cap, h_total, s));
+  hipLaunchKernelGGL(k_vtext_write, dim3(nb(n)), dim3(256), 0, s, (const VCell*)ws.cell, n, n_blocks, ws.pos, d_out);
+  return hipGetLastError();
+}
+
+hipError_t model_index_text_ws(const int32_t* d_index, int64_t n, const int64_t* d_off, int n_mats, const TextWs& ws,
+                               char* d_out, int64_t cap, int64_t* h_total, hipStream_t s) {
+  *h_total = 0;
+  if (n <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_text_len, dim3(nb(n)), dim3(256), 0, s, d_index, n, d_off, n_mats, ws.len);
+  MC_TRY(hipGetLastError());
+  MC_TRY(text_positions(n, ws, cap, h_total, s));
+  hipLaunchKernelGGL(k_text_write, dim3(nb(n)), dim3(256), 0, s, d_index, n, d_off, n_mats, ws.pos, d_out);
+  return hipGetLastError();
 }
 
 hipError_t model_read_index(const uint8_t* d_text, int64_t len, int64_t n_w, const int32_t* d_keys,

@@ -177,12 +177,18 @@ class FleetUpdater:
     ``weights`` (the non-null W concatenated in slot order) and ``fc_bias`` (the
     fully-connected layers' biases) are the model the server keeps
     (``cnn`` in cppNN_backend.cpp); ``lrates`` is initUpdater's schedule
-    (cppNN_backend.cpp:161-172)."""
+    (cppNN_backend.cpp:161-172). With ``model=`` (a ``fleet_amd.ResidentModel``) the model lives in
+    HBM instead: ``weights`` and ``fc_bias`` may be None, every path runs the device form of its
+    update into tensors the updater keeps and steps the model there (``descent_device``), and
+    only the merged text comes back to the host. ``kardam_models=`` may be that same model."""
 
     def __init__(self, codec, layout, M: int, lrates: Sequence[float], weights, fc_bias, policy: int = 0,
                  alpha: float = 0.0, stale_size: int = 0, num_labels: int = 10, has_outlier: bool = False,
                  streaming: bool = False, picker=None, pool_slots: Optional[int] = None, kardam=None,
-                 kardam_model=None, kardam_models=None):
+                 kardam_model=None, kardam_models=None, model=None):
+        if model is None and (weights is None or fc_bias is None):
+            raise ValueError("weights and fc_bias are the model the updater steps: give them, or model= (a "
+                             "fleet_amd.ResidentModel that holds them in HBM)")
         if kardam_model is not None and kardam_models is not None:
             raise ValueError("kardam_model (a callback that returns texts) and kardam_models (a fleet_amd.Model whose "
                              "versions go through a model ledger) are two ways to the same models: give one")
@@ -203,8 +209,15 @@ class FleetUpdater:
         self.has_outlier = has_outlier
         self.lrates = [float(v) for v in lrates]
         self.lr = np.float32(self.lrates[0])  # initUpdater: cnn.set_learning_rate(lrates_vec[0])
-        self.weights = np.array(weights, dtype=np.float32, copy=True)
-        self.fc_bias = np.array(fc_bias, dtype=np.float32, copy=True)
+        # model: a fleet_amd.ResidentModel. The model step then is its descent_device on the merged
+        # gradient where the update left it (tensors the updater keeps); only the merged text
+        # comes back to the host, for the return value. weights / fc_bias are not used.
+        self.model = model
+        self.weights = None if model is not None else np.array(weights, dtype=np.float32, copy=True)
+        self.fc_bias = None if model is not None else np.array(fc_bias, dtype=np.float32, copy=True)
+        self._merged_u8 = self._merged_f32 = None
+        if model is not None and model.modelsSize() == 0:
+            model.initUpdater(self.lrates)
         self.curr_epoch = 0
         self.acc: List[Pending] = []
         self.global_labels = [0] * num_labels
@@ -261,6 +274,25 @@ class FleetUpdater:
         a.push(p.upload, p.dampen)  # a malformed upload raises here and joins nothing
         p.upload = b""
 
+    def _device_out(self, length: int):
+        """The tensors a device-form update writes: the merged text and decodeFloat of it."""
+        import torch
+        from . import b64_count
+        groups = (b64_count(length) + 2) // 3
+        if self._merged_u8 is None or self._merged_u8.numel() < 16 * groups + 16:
+            dev = f"cuda:{self.codec.device}"
+            self._merged_u8 = torch.zeros(16 * groups + 16, dtype=torch.uint8, device=dev)
+            self._merged_f32 = torch.zeros(3 * groups + 4, dtype=torch.float32, device=dev)
+        return self._merged_u8, self._merged_f32
+
+    def _step_resident(self, length: int) -> bytes:
+        """descentNative on the resident model from the merged gradient in HBM; the merged text
+        is the one thing copied to the host."""
+        from . import b64_count
+        self.model.descent_device(self._merged_f32, self.stale_size, n_values=b64_count(length))
+        self.lr = np.float32(self.model.getLrate())
+        return self._merged_u8[:length].cpu().numpy().tobytes()
+
     def update(self, upload: bytes, labels: Sequence[int], epoch: int, client_id: int = 0) -> Optional[bytes]:
         """One client upload (CppNNUpdater.update, :330-518). Returns the merged
         gradient when this upload completed a batch of M (and the model stepped),
@@ -307,7 +339,11 @@ class FleetUpdater:
         if self.kardam is not None and self.kardam_models is not None:
             versions = self._kardam_versions(picked)  # before anything changes
         try:
-            if self.kardam is None:
+            if self.model is not None:
+                mu8, mf32 = self._device_out(pool.length)
+            if self.kardam is None and self.model is not None:
+                pool.update_device([q.slot for q in picked], dampen, mu8, mf32)
+            elif self.kardam is None:
                 merged, grad = pool.update([q.slot for q in picked], dampen, want_f32=True)
             else:
                 if self._ledger is None:
@@ -316,8 +352,14 @@ class FleetUpdater:
                     self.kardam_model(self.curr_epoch - q.epoch) for q in picked]
                 workers = [-1 if m is None else q.client_id for q, m in zip(picked, models)]
                 # getLrate() before descentNative (:478): the rate of the previous step
-                merged, grad, _, diff, was_set = self._ledger.update(
-                    [q.slot for q in picked], dampen, workers, [q.epoch for q in picked], float(self.lr), want_f32=True)
+                if self.model is not None:
+                    _, diff, was_set = self._ledger.update_device(
+                        [q.slot for q in picked], dampen, workers, [q.epoch for q in picked],
+                        float(self.model.getLrate()), mu8, mf32)
+                else:
+                    merged, grad, _, diff, was_set = self._ledger.update(
+                        [q.slot for q in picked], dampen, workers, [q.epoch for q in picked], float(self.lr),
+                        want_f32=True)
                 kd = (models, diff, was_set)
         except Exception as e:
             bad = set(getattr(e, "slots", ()))  # Base64Error / LayoutError: the slots at fault leave, the model stays
@@ -341,9 +383,12 @@ class FleetUpdater:
                 window[j] += v
         for j, v in enumerate(window):
             self.global_labels[j] += v
-        if self.curr_epoch < len(self.lrates):
-            self.lr = np.float32(self.lrates[self.curr_epoch])
-        self.weights, self.fc_bias = self.codec.descent(self.weights, self.fc_bias, grad, self.layout, self.lr)
+        if self.model is not None:
+            merged = self._step_resident(pool.length)
+        else:
+            if self.curr_epoch < len(self.lrates):
+                self.lr = np.float32(self.lrates[self.curr_epoch])
+            self.weights, self.fc_bias = self.codec.descent(self.weights, self.fc_bias, grad, self.layout, self.lr)
         self.curr_epoch += 1
         for q in picked:  # the picked uploads leave `acc` (:421), everything else stays buffered
             pool.drop(q.slot)
@@ -402,6 +447,8 @@ class FleetUpdater:
                 window[j] += v
         for j, v in enumerate(window):
             self.global_labels[j] += v
+        if self.model is not None:
+            return self._finish_resident(picked, dampen)
         if fused is not None:
             merged, grad = fused
         elif self.streaming:
@@ -412,6 +459,32 @@ class FleetUpdater:
         if self.curr_epoch < len(self.lrates):
             self.lr = np.float32(self.lrates[self.curr_epoch])
         self.weights, self.fc_bias = self.codec.descent(self.weights, self.fc_bias, grad, self.layout, self.lr)
+        self.curr_epoch += 1
+        self.acc.clear()  # aggregated.clear() (:516)
+        self.last_merged = merged
+        return merged
+
+    def _finish_resident(self, picked, dampen) -> bytes:
+        """_finish_batch's merge and step with a resident model: the accumulator's finish_device,
+        or update_device over the batch's uploads, then the step in HBM."""
+        if self.streaming:
+            length = self._stream_acc.length
+            mu8, mf32 = self._device_out(length)
+            self._stream_acc.finish_device(mu8, mf32)
+        else:
+            import torch
+            length = len(picked[0])
+            if any(len(u) != length for u in picked):
+                raise ValueError("the batch's uploads differ in length (one model layout)")
+            mu8, mf32 = self._device_out(length)
+            pitch = (length + 15) // 16 * 16 + 16
+            rows = np.zeros((len(picked), pitch), np.uint8)
+            for i, u in enumerate(picked):
+                rows[i, :length] = np.frombuffer(u, np.uint8)
+            d_rows = torch.from_numpy(rows).to(f"cuda:{self.codec.device}")
+            self.codec.update_device(d_rows, length, dampen, self.layout.header_positions(), mu8, mf32)
+            self.codec.check()  # a malformed upload raises before the model steps
+        merged = self._step_resident(length)
         self.curr_epoch += 1
         self.acc.clear()  # aggregated.clear() (:516)
         self.last_merged = merged
@@ -446,13 +519,13 @@ class FleetUpdater:
                 p.dampen = self._dampen_of(p)
             ups, d = [p.upload for p in run], [p.dampen for p in run]
             fused = None
-            if len(run) == room:
+            if len(run) == room and self.model is None:
                 fused = a.push_finish(ups, d, want_f32=True)
-            else:
+            else:  # (a resident model: the finish is the device form's, in _finish_batch)
                 a.push_many(ups, d)
             for p in run:
                 p.upload = b""
             self.acc.extend(run)
             out += [None] * (len(run) - 1)
-            out.append(self._finish_batch(fused) if fused is not None else None)
+            out.append(self._finish_batch(fused) if len(run) == room else None)
         return out

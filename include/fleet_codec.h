@@ -57,6 +57,8 @@ int fleet_create(int device, fleet_ctx** out);
 void fleet_destroy(fleet_ctx* ctx);
 const char* fleet_last_error(const fleet_ctx* ctx);
 int fleet_sync(fleet_ctx* ctx, void* stream);
+/* the HIP device the context was created on (-1 for NULL) */
+int fleet_ctx_device(const fleet_ctx* ctx);
 
 /* Base64 length of n int32/fp32 values: 4*ceil(4n/3) (Base64.cpp:129-136). */
 size_t fleet_b64_len(size_t n_values);
@@ -541,6 +543,8 @@ void fleet_mledger_destroy(fleet_mledger* ledger);
 /* the sizes given to create; any pointer may be NULL */
 int fleet_mledger_shape(const fleet_mledger* ledger, size_t* n_weights, size_t* n_biases, int* graph_edges,
                         int* workers, int* max_versions);
+/* the context the ledger was made on (NULL for NULL) */
+fleet_ctx* fleet_ctx_of_mledger(const fleet_mledger* ledger);
 /* the pair kernel's launch shape, for tests and sizing: lanes per wave, values a block
  * takes per pass, blocks per pair at most (a lane strides on beyond values * blocks) */
 int fleet_mledger_launch_shape(int* wave, int* block_values, int* max_blocks);
@@ -605,6 +609,10 @@ int fleet_mledger_read_version(fleet_mledger* ledger, int64_t id, float* params,
  *   fn 21: the serial accumulation's Q with VarEntry digit offsets (var_d16; as fn 6)
  *   fn 22: the model-version copy's strtof("%.6g") round trip over every finite
  *          binary32 (decimal6.h; against libc's snprintf/strtof)
+ *   fn 23: the stream kernels' int2float (dec_d16; as fn 0)
+ *   fn 24: the text of `ostream << float` (decimal6.h g6_text) over all 2^32 bit
+ *          patterns: sum_i g6_text_term(i, text) against libc's snprintf("%g")
+ *          (tests/native/check_g6text.cpp, tests/golden/g6text_digest.json)
  * computed on the GPU; compare with the oracle's digests. */
 int fleet_selftest_digest(fleet_ctx* ctx, int fn, uint64_t* out);
 
@@ -626,6 +634,20 @@ int fleet_model_quantize_index(fleet_ctx* ctx, const float* weights, const int32
  * after the bias lines (getParametersNative, Server/.../cppNN_backend.cpp:244-280). */
 int fleet_model_weights_text(fleet_ctx* ctx, const float* weights, const int32_t* dims, int n_mats, char* out,
                              size_t cap, size_t* out_len);
+/* The text of `ostream << float` (default precision: snprintf("%g")) for n
+ * values, every byte formatted on the device (decimal6.h g6_text: the exact six
+ * digits from integer arithmetic; 0, -0, inf, -inf, nan, -nan for the rest).
+ *   n_blocks > 0: block_sizes[n_blocks] sums to n; "value " per value and '\n'
+ *     after each block -- the bias lines and DISTILLATION_MODE=0 weight lines of
+ *     getParams (network.h:611-706). A block of size 0 prints its lone '\n';
+ *     at most 254 empty blocks may follow one another.
+ *   n_blocks == 0: "i\nvalue\n" for i = 0..n-1, the mode-1 dictionary section.
+ * n < 2^31. *out_len is set even when cap is too small (FLEET_ERR_CAPACITY).
+ * The _device form reads the values where they are (no host to device copy). */
+int fleet_values_text(fleet_ctx* ctx, const float* values, size_t n, const int64_t* block_sizes, int n_blocks,
+                      char* out, size_t cap, size_t* out_len);
+int fleet_values_text_device(fleet_ctx* ctx, const void* d_values, size_t n, const int64_t* block_sizes, int n_blocks,
+                             char* out, size_t cap, size_t* out_len, void* stream);
 /* network::read's DISTILLATION_MODE=1 weights branch (network.h:958-997): such a
  * section back to weights (W[i] = value of the index's dictionary key; a key
  * the dictionary lacks gives 0.0f, std::map::operator[]). */
@@ -800,6 +822,82 @@ int fleet_model_version_id(fleet_model* m, int version, int64_t* id);
  * text. FLEET_ERR_ARG when the ledger's n_weights, n_biases or graph_edges differ from
  * fleet_model_shape's, or as fleet_model_version_id. */
 int fleet_mledger_stage_model(fleet_mledger* ledger, fleet_model* m, int version, int64_t* id);
+
+/* The same model resident in HBM (fleet_rmodel): `cnn` and every entry of `models`
+ * live on the device, so a model step takes a merged gradient that is already there
+ * (fleet_update_device / fleet_pool_update_device / fleet_kledger_update_device's
+ * d_merged_f32) and leaves the new version where the Kardam model ledger stages it
+ * device to device; only texts leave the device. Same natives, same results bit for
+ * bit as fleet_model (the yardstick). Errors: fleet_rmodel_last_error.
+ *
+ * HBM: (max_versions + 2) rows of [weights | use_bias() biases], 64 floats aligned
+ * (cnn and a ring of max_versions + 1 versions: descentNative pushes before it pops),
+ * plus a workspace allocated once at load (the dictionary pipeline's buffers and
+ * rocPRIM storage, the text emitters', the text and a20 buffers; fleet_rmodel_
+ * workspace_bytes). After load only the staging of a host gradient text grows, on the
+ * first fleet_rmodel_descent (and for a longer text); fleet_rmodel_stats counts every
+ * hipMalloc / hipHostMalloc made. Guarded by a mutex; every entry restores the
+ * caller's device. max_versions >= 1.
+ * Streams: the _device entry points (fleet_rmodel_descent_device,
+ * fleet_rmodel_get_model_params_device) run on the stream they are given, NULL
+ * meaning the null stream as in the rest of this C-ABI, so they order with the
+ * work that wrote their inputs and with the caller's next use of their outputs
+ * on that stream. fleet_rmodel_descent_device synchronises it (the error word);
+ * fleet_rmodel_get_model_params_device does not, and its version must not be
+ * dropped before the stream has passed it. The host-buffer entry points run on a
+ * stream of the model's own and return synchronised. */
+typedef struct fleet_rmodel fleet_rmodel;
+int fleet_rmodel_load(fleet_ctx* ctx, const char* text, size_t len, int distillation_mode, int max_versions,
+                      fleet_rmodel** out);
+void fleet_rmodel_destroy(fleet_rmodel* m);
+const char* fleet_rmodel_last_error(const fleet_rmodel* m);
+int fleet_rmodel_init_updater(fleet_rmodel* m, const double* lrates, int n_lrates);
+/* descentNative from the merged text: decoded on the device; fleet_model_descent's
+ * header checks and errors (FLEET_ERR_BASE64, FLEET_ERR_LAYOUT, FLEET_ERR_ARG), made
+ * by a check kernel before any weight is written: a refused gradient changes nothing.
+ * A step after which more than max_versions versions would be kept (stale_size larger
+ * than the model was loaded for) is refused with FLEET_ERR_ARG before anything
+ * changes. DISTILLATION_MODE=1 with a non-finite weight or bias after the step:
+ * FLEET_ERR_ARG with cnn stepped, the epoch advanced and no version pushed, as
+ * fleet_model_descent leaves its model. */
+int fleet_rmodel_descent(fleet_rmodel* m, const char* merged, size_t len, int client_batch_size, int stale_size);
+/* The same from decodeFloat of the merged text on the device (n_values floats).
+ * n_values below the model's shortest gradient (2 + graph edges + layers + weights +
+ * fc biases) is FLEET_ERR_ARG with nothing launched; the exact length follows from the
+ * gradient's own bias-block sizes and is checked with the header slots on the device.
+ * Synchronous: one 4-byte error word is read back per step. */
+int fleet_rmodel_descent_device(fleet_rmodel* m, const void* d_merged_f32, size_t n_values, int stale_size,
+                                void* stream);
+int fleet_rmodel_count(fleet_rmodel* m);
+/* getParametersNative: the header is constant; the bias lines, the mode-0 weight lines,
+ * the mode-1 dictionary lines and the index section are formatted on the device from
+ * the resident row into one buffer and copied out once. No weight travels host to
+ * device. fleet_rmodel_params_cap: a capacity that always suffices. */
+size_t fleet_rmodel_params_cap(const fleet_rmodel* m);
+int fleet_rmodel_get_params(fleet_rmodel* m, int version, char* out, size_t cap, size_t* out_len);
+int fleet_rmodel_get_model_params(fleet_rmodel* m, int version, char* out, size_t cap, size_t* out_len);
+/* the a20 text into a device buffer of fleet_b64_len(n_biases * graph_edges + n_weights)
+ * bytes rounded up to 16, plus 16 (fleet_model_params_device's kernel, on `stream`) */
+int fleet_rmodel_get_model_params_device(fleet_rmodel* m, int version, void* d_out, void* stream);
+int fleet_rmodel_get_epoch(fleet_rmodel* m);
+void fleet_rmodel_set_epoch(fleet_rmodel* m, int epoch);
+int fleet_rmodel_get_priority(fleet_rmodel* m);
+void fleet_rmodel_set_priority(fleet_rmodel* m, int priority);
+double fleet_rmodel_get_lrate(fleet_rmodel* m);
+int fleet_rmodel_shape(fleet_rmodel* m, size_t* n_weights, size_t* n_biases, int* graph_edges, int* n_layers);
+int fleet_rmodel_export(fleet_rmodel* m, int version, float* weights, size_t n_weights, float* biases,
+                        size_t n_biases);
+int fleet_rmodel_version_id(fleet_rmodel* m, int version, int64_t* id);
+/* models[version]'s weights and biases where they live (version -1: cnn); valid until
+ * that version is dropped */
+int fleet_rmodel_version_device(fleet_rmodel* m, int version, const float** d_weights, const float** d_biases);
+/* fleet_mledger_stage_model from the resident row, device to device, same ids; FLEET_ERR_ARG
+ * for a ledger of another context than the model's */
+int fleet_rmodel_stage_mledger(fleet_mledger* ledger, fleet_rmodel* m, int version, int64_t* id);
+/* resident_bytes: the rows, 4 * roundup64(n_weights + n_biases) * (max_versions + 2);
+ * device_allocs: every hipMalloc / hipHostMalloc made on the model's behalf so far */
+int fleet_rmodel_stats(fleet_rmodel* m, size_t* resident_bytes, int* device_allocs);
+size_t fleet_rmodel_workspace_bytes(const fleet_rmodel* m);
 
 /* The offline sampler's state (the CppNNOfflineSampler natives
  * of Server/src/main/c++/cppNN_backend.cpp and the globals they keep). Random
