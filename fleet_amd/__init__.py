@@ -137,6 +137,15 @@ def lib() -> C.CDLL:
         "fleet_kledger_read": (i32, [vp, i32, vp, sz]),
         "fleet_kledger_update": (i32, [vp, vp, i32, vp, vp, vp, C.c_double, vp, sz, szp, vp, vp, vp, vp]),
         "fleet_kledger_update_device": (i32, [vp, vp, i32, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp]),
+        "fleet_kfilter_create": (i32, [vp, sz, sz, i32, C.POINTER(vp)]),
+        "fleet_kfilter_destroy": (None, [vp]),
+        "fleet_kfilter_has_last": (i32, [vp]),
+        "fleet_kfilter_set_model": (i32, [vp, vp, vp, vp, vp]),
+        "fleet_kfilter_set_model_device": (i32, [vp, vp, vp, vp, vp, vp]),
+        "fleet_kfilter_update": (i32, [vp, vp, i32, vp, vp, vp, C.c_double, vp, sz, szp, vp, vp, vp, vp, vp, vp]),
+        "fleet_kfilter_update_device": (i32, [vp, vp, i32, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "fleet_kfilter_resolve": (i32, [vp, vp, i32, vp, sz, szp, vp]),
+        "fleet_kfilter_resolve_device": (i32, [vp, vp, i32, vp, vp, szp, vp]),
         "fleet_mledger_create": (i32, [vp, sz, sz, i32, i32, i32, C.POINTER(vp)]),
         "fleet_mledger_destroy": (None, [vp]),
         "fleet_mledger_shape": (i32, [vp, szp, szp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
@@ -1273,6 +1282,144 @@ class Ledger:
             merged_u8.data_ptr(), merged_f32.data_ptr() if merged_f32 is not None else None, ng.ctypes.data,
             nd.ctypes.data, st.ctypes.data, _stream(stream)), pk)
         return ng, nd, st.astype(bool)
+
+    def filter(self, n_weights: int, n_biases: int, graph_edges: int) -> "KardamFilter":
+        """A Kardam filter (fleet_kfilter) over this ledger for a model of ``n_weights``
+        weights and ``n_biases`` biases repeated ``graph_edges`` times (``Model.shape()``)."""
+        return KardamFilter(self, n_weights, n_biases, graph_edges)
+
+
+class KardamFilter:
+    """What ``Kardam.checkByz`` reads of an update's picks, kept in HBM beside a ledger
+    (fleet_kfilter, include/fleet_codec.h; Kardam.java:136-185). ``set_model`` stages
+    currModel and returns its norms; ``update`` is ``Ledger.update`` plus, for every pick,
+    the norm of its dampened gradient and of its difference to the last average, and leaves
+    the update pending; the caller decides (``updater.Kardam.check_byz``) and ``resolve``
+    gives the merged bytes of the accepted picks, or None when none was accepted. Between
+    ``update`` and ``resolve`` no picked slot may be put into or dropped. Close it before
+    its ledger."""
+
+    def __init__(self, ledger: Ledger, n_weights: int, n_biases: int, graph_edges: int):
+        self.ledger = ledger
+        self.pool = ledger.pool
+        self._L = ledger._L
+        self._h = None
+        self.n_weights, self.n_biases, self.graph_edges = int(n_weights), int(n_biases), int(graph_edges)
+        h = C.c_void_p()
+        self.pool.codec._check(self._L.fleet_kfilter_create(ledger._live(), self.n_weights, self.n_biases,
+                                                            self.graph_edges, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if (getattr(self, "_h", None) and getattr(self.ledger, "_h", None) and getattr(self.pool, "_h", None)
+                and getattr(self.pool.codec, "_h", None)):
+            self._L.fleet_kfilter_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _live(self):
+        if not getattr(self, "_h", None):
+            raise ValueError("the filter is closed")
+        self.ledger._live()
+        return self._h
+
+    @property
+    def has_last(self) -> bool:
+        """lastGrad != null: an earlier update of this filter ended with an average."""
+        return bool(self._L.fleet_kfilter_has_last(self._live()))
+
+    def set_model(self, weights, biases):
+        """currModel from its weights and use_bias() biases (``Model.export``'s vectors).
+        Returns ``(norm_model, norm_model_diff)``, the second NaN while there is no last model."""
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        b = np.ascontiguousarray(biases, dtype=np.float32)
+        if len(w) != self.n_weights or len(b) != self.n_biases:
+            raise ValueError(f"the filter holds {self.n_weights} weights and {self.n_biases} biases")
+        nm, nd = C.c_double(0), C.c_double(0)
+        self.pool.codec._check(self._L.fleet_kfilter_set_model(
+            self._live(), w.ctypes.data if len(w) else None, b.ctypes.data if len(b) else None, C.byref(nm), C.byref(nd)))
+        return float(nm.value), float(nd.value)
+
+    def set_model_device(self, weights_f32, biases_f32, stream=None):
+        """``set_model`` from float32 tensors on the codec's device (``ResidentModel.version_tensors``)."""
+        if weights_f32.numel() != self.n_weights or biases_f32.numel() != self.n_biases:
+            raise ValueError(f"the filter holds {self.n_weights} weights and {self.n_biases} biases")
+        nm, nd = C.c_double(0), C.c_double(0)
+        self.pool.codec._check(self._L.fleet_kfilter_set_model_device(
+            self._live(), weights_f32.data_ptr() if self.n_weights else None,
+            biases_f32.data_ptr() if self.n_biases else None, C.byref(nm), C.byref(nd), _stream(stream)))
+        return float(nm.value), float(nd.value)
+
+    def _check_tensors(self, merged_u8, merged_f32):
+        if merged_u8.numel() < 16 * self.pool.groups or (
+                merged_f32 is not None and merged_f32.numel() < b64_count(self.pool.length)):
+            raise ValueError("merged tensors smaller than the upload's groups")
+
+    def update(self, picks, dampens, workers, epochs, lr: float, want_f32: bool = False):
+        """``Ledger.update`` with every pick accepted, plus the filter's norms. Returns
+        ``(merged, f32 or None, norm_g, norm_diff, set, norm_p, norm_pdiff)``; ``norm_pdiff``
+        is NaN while ``has_last`` is false. The update is then pending."""
+        pk, d, w, e, ng, nd, st = self.ledger._args(picks, dampens, workers, epochs)
+        K = len(pk)
+        np_, npd = np.full(K, np.nan), np.full(K, np.nan)
+        length = self.pool.length
+        out = np.zeros(length + 16, np.uint8)
+        n = C.c_size_t(0)
+        f32 = np.zeros(b64_count(length) + 1, np.float32) if want_f32 else None
+        self.pool._check(self._L.fleet_kfilter_update(
+            self._live(), pk.ctypes.data, K, d.ctypes.data, w.ctypes.data, e.ctypes.data, float(lr), out.ctypes.data,
+            len(out), C.byref(n), f32.ctypes.data if want_f32 else None, ng.ctypes.data, nd.ctypes.data, st.ctypes.data,
+            np_.ctypes.data, npd.ctypes.data), pk)
+        return (out[: n.value].tobytes(), f32[: b64_count(length)].copy() if want_f32 else None, ng, nd,
+                st.astype(bool), np_, npd)
+
+    def update_device(self, picks, dampens, workers, epochs, lr: float, merged_u8, merged_f32=None, stream=None):
+        """The device form. Returns ``(norm_g, norm_diff, set, norm_p, norm_pdiff)``."""
+        pk, d, w, e, ng, nd, st = self.ledger._args(picks, dampens, workers, epochs)
+        K = len(pk)
+        np_, npd = np.full(K, np.nan), np.full(K, np.nan)
+        self._check_tensors(merged_u8, merged_f32)
+        self.pool._check(self._L.fleet_kfilter_update_device(
+            self._live(), pk.ctypes.data, K, d.ctypes.data, w.ctypes.data, e.ctypes.data, float(lr),
+            merged_u8.data_ptr(), merged_f32.data_ptr() if merged_f32 is not None else None, ng.ctypes.data,
+            nd.ctypes.data, st.ctypes.data, np_.ctypes.data, npd.ctypes.data, _stream(stream)), pk)
+        return ng, nd, st.astype(bool), np_, npd
+
+    def resolve(self, accept, want_f32: bool = False):
+        """The pending update's result for the decisions ``accept`` (one per pick): the merged
+        bytes (``(merged, f32)`` with ``want_f32``), or None when no pick was accepted."""
+        a = np.ascontiguousarray(np.asarray(accept, dtype=bool), dtype=np.uint8)
+        length = self.pool.length
+        out = np.zeros(length + 16, np.uint8)
+        n = C.c_size_t(0)
+        f32 = np.zeros(b64_count(length) + 1, np.float32) if want_f32 else None
+        self.pool._check(self._L.fleet_kfilter_resolve(self._live(), a.ctypes.data, len(a), out.ctypes.data, len(out),
+                                                       C.byref(n), f32.ctypes.data if want_f32 else None))
+        if n.value == 0:
+            return None
+        merged = out[: n.value].tobytes()
+        return (merged, f32[: b64_count(length)].copy()) if want_f32 else merged
+
+    def resolve_device(self, accept, merged_u8, merged_f32=None, stream=None) -> bool:
+        """The device form: writes the tensors when a pick was accepted and returns whether one was."""
+        a = np.ascontiguousarray(np.asarray(accept, dtype=bool), dtype=np.uint8)
+        self._check_tensors(merged_u8, merged_f32)
+        n = C.c_size_t(0)
+        self.pool._check(self._L.fleet_kfilter_resolve_device(
+            self._live(), a.ctypes.data, len(a), merged_u8.data_ptr(),
+            merged_f32.data_ptr() if merged_f32 is not None else None, C.byref(n), _stream(stream)))
+        return n.value != 0
 
 
 class ModelLedger:

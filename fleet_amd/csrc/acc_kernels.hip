@@ -586,6 +586,223 @@ __global__ void __launch_bounds__(kAccNT) k_pool_kd_reduce(const double* __restr
   }
 }
 
+// The average as the next update's lastGrad reads it (CppNNUpdater.java:507, 510): avg =
+// scalarMultiply(1 / avgSize) of the running value, decoded -- Q(f32(f64(A) * inv)) per
+// slot. Not decodeFloat(merged): the merge decodes and encodes that value once more
+// (merged_code), and Q is not idempotent on every value. Every lane of the wave calls
+// (the stage's fallback is behind a ballot); a live lane stores its 12 bytes.
+__device__ __forceinline__ void acc_lane_avg(const AccShared& sh, const float (&A)[3], double inv, bool live, float* out) {
+  float r[3] = {A[0], A[1], A[2]}, q[3];
+  dampen_stage<3>(r, inv);
+  q_stage_d16x<3>(q, r, &sh.dtab, sh.tab.var);
+  if (live) *reinterpret_cast<f3u*>(out) = f3u{q[0], q[1], q[2]};
+}
+
+// The filter form of k_pool_fold_kd (fleet_kfilter_update*): beside everything that kernel
+// does, per pick k what Kardam.checkByz's checkNorm reads of the pick (Kardam.java:136-185,
+// CppNNUpdater.java:488 without its `true ||`): sp = sum (double)(p * p) over the flat slots,
+// p the pick's dampened value before the learning rate, and, with a previous average
+// `lastg` (one fp32 row in upload coordinates, the avg of the last update that had one as
+// acc_lane_avg leaves it; nullptr: none), E = Q(p - L) and se = sum (double)(E * E). A lane loads
+// its 12 bytes of L once per group, before the pick loop. sp does not depend on the pick's
+// mode: the filter's norm is taken of every pick, a worker[k] < 0 one included. The finish
+// form also leaves this update's avg in `avg_out` (another row than `lastg`).
+// The wave's slots are kfp[wave][pick][4] = {sg, sd, sp, se}: sg / sd go through
+// k_pool_fold_kd's reduction line for line (the same bits as the ledger form gives), and
+// sp / se through a second one of the same shape. partials[(k * waves + w) * 4 + 0..3];
+// k_pool_kf_reduce adds the waves in k_pool_kd_reduce's order. A sibling, not a flag of
+// k_pool_fold_kd: that kernel's instantiations stay what they were.
+// Occupancy: the ledger form's finish instantiation takes 91 VGPRs, five waves a SIMD.
+// Left to itself this kernel takes 99, one wave fewer; asked for five waves it fits 89
+// without scratch. Its 26432 bytes of LDS (AccShared + 8 KiB of slots) allow six blocks a
+// CU, so the registers stay the bound, as they are for the ledger form (22336 bytes, seven).
+template <bool FINISH>
+__global__ void __launch_bounds__(kAccNT) __attribute__((amdgpu_waves_per_eu(5))) k_pool_fold_kf(const uint8_t* pool, size_t pitch, PoolPicks picks, float* st,
+                                                         int first, int K, AccDampen dampen, double inv, int64_t n_up,
+                                                         int64_t g_begin, int64_t g_end,
+                                                         const int32_t* __restrict__ hdr_block, int32_t* hfirst,
+                                                         int* __restrict__ status, uint8_t* merged, float* merged_f32,
+                                                         PoolKdRows rows, PoolKdModes modes, double lr, float* slab,
+                                                         size_t vpitch, double* __restrict__ partials,
+                                                         const float* __restrict__ lastg, float* __restrict__ avg_out) {
+  __shared__ AccShared sh;
+  __shared__ double kfp[kAccNT / 64][kAccBurst][4];
+  for (int i = threadIdx.x; i < (kAccNT / 64) * kAccBurst * 4; i += kAccNT) (&kfp[0][0][0])[i] = 0.0;
+  const AccHdr H = acc_block_open(sh, hdr_block);  // (its barrier covers the zeroes)
+  const int64_t ng = g_end - g_begin;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool has_last = lastg != nullptr;
+  uint64_t bad_picks = 0, layout_picks = 0;
+  for (int64_t base = (int64_t)blockIdx.x * kAccNT; base < ng; base += (int64_t)gridDim.x * kAccNT) {
+    const int64_t gl = base + threadIdx.x;
+    const bool live = gl < ng;
+    const int64_t gs = live ? gl : 0, g = g_begin + gs;
+    float A[3] = {0.f, 0.f, 0.f};
+    if (!first && live) {
+      const f3u a = *reinterpret_cast<const f3u*>(st + 3 * gs);
+      A[0] = a.x, A[1] = a.y, A[2] = a.z;
+    }
+    float Lv[3] = {0.f, 0.f, 0.f};
+    if (has_last && live) {
+      const f3u t = *reinterpret_cast<const f3u*>(lastg + 3 * gs);
+      Lv[0] = t.x, Lv[1] = t.y, Lv[2] = t.z;
+    }
+    const uint32_t need = needed_chars_mask((int)min<int64_t>(3, max<int64_t>(0, n_up - 3 * g)));
+    int h0;
+    const uint32_t hbits = acc_header_bits(sh, H.hdr, H.n_hdr, 3 * g, &h0);
+    const uint32_t kbits = keep_bits<3>(hbits, true, 3 * g, H.walk_end);
+    const bool wave_keep = __ballot(kbits != 0) != 0;
+    const uint32_t flat = live ? ~kbits & 7u : 0u;
+    int32_t href[3] = {0, 0, 0}, keepc[3] = {0, 0, 0};
+    if (wave_keep && !first) {
+      int hi = h0;
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        if ((hbits >> i) & 1u) href[i] = hfirst[hi++];
+    }
+    double sg0 = 0.0, sd0 = 0.0, sp0 = 0.0, se0 = 0.0;  // an even pick's sums, held for the pair
+    int mode0 = 0;
+    for (int k = 0; k < K; ++k) {
+      const int mode = modes.m[k];
+      float pv[3] = {0.f, 0.f, 0.f};
+      if ((mode & kKdDiff) && live) {
+        const f3u t = *reinterpret_cast<const f3u*>(slab + (size_t)rows.prev[k] * vpitch + 3 * gs);
+        pv[0] = t.x, pv[1] = t.y, pv[2] = t.z;
+      }
+      const uint8_t* src = pool + (size_t)picks.slot[k] * pitch + 16 * gs;
+      uint32_t bad = 0, layout_bad = 0;
+      float p[3];
+      acc_lane_value<FINISH>(sh, src, live, need, wave_keep, hbits, kbits, h0, first && k == 0, dampen.d[k], hfirst, href,
+                             keepc, p, bad, layout_bad);
+      bad_picks |= (uint64_t)(bad != 0) << k;
+      layout_picks |= (uint64_t)(layout_bad != 0) << k;
+      double sg = 0.0, sd = 0.0, sp = 0.0, se = 0.0;
+      float pf[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        pf[i] = ((flat >> i) & 1u) ? p[i] : 0.0f;
+        sp += (double)(pf[i] * pf[i]);
+      }
+      if (has_last) {
+        float ev[3], E[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) ev[i] = ((flat >> i) & 1u) ? pf[i] - Lv[i] : 0.0f;
+        q_stage_d16x<3>(E, ev, &sh.dtab, sh.tab.var);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) se += (double)(E[i] * E[i]);
+      }
+      if (mode & kKdNorm) {
+        float rg[3] = {p[0], p[1], p[2]}, G[3];
+        dampen_stage<3>(rg, lr);
+        q_stage_d16x<3>(G, rg, &sh.dtab, sh.tab.var);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          G[i] = ((flat >> i) & 1u) ? G[i] : 0.0f;
+          sg += (double)(G[i] * G[i]);
+        }
+        if (mode & kKdDiff) {
+          float dv[3], D[3];
+#pragma unroll
+          for (int i = 0; i < 3; ++i) dv[i] = ((flat >> i) & 1u) ? G[i] - pv[i] : 0.0f;
+          q_stage_d16x<3>(D, dv, &sh.dtab, sh.tab.var);
+#pragma unroll
+          for (int i = 0; i < 3; ++i) sd += (double)(D[i] * D[i]);
+        }
+        if ((mode & kKdStore) && live)
+          *reinterpret_cast<f3u*>(slab + (size_t)rows.out[k] * vpitch + 3 * gs) = f3u{G[0], G[1], G[2]};
+      }
+      acc_lane_add(sh, first && k == 0, p, A);
+      if (k & 1) {
+        if ((mode | mode0) & kKdNorm) {
+          const double s = quad_sum_f64(sg0, sd0, sg, sd);
+          if ((lane & 15) == 15)  // rows 0..3: (k - 1, g), (k, g), (k - 1, d), (k, d)
+            kfp[wave][k - 1 + ((lane >> 4) & 1)][lane >> 5] += s;
+        }
+        const double t = quad_sum_f64(sp0, se0, sp, se);
+        if ((lane & 15) == 15) kfp[wave][k - 1 + ((lane >> 4) & 1)][2 + (lane >> 5)] += t;
+      } else if (k + 1 == K) {
+        if (mode & kKdNorm) {
+          const double s = pair_sum_f64<64>(sg, sd);
+          if ((lane & 31) == 31) kfp[wave][k][lane >> 5] += s;
+        }
+        const double t = pair_sum_f64<64>(sp, se);
+        if ((lane & 31) == 31) kfp[wave][k][2 + (lane >> 5)] += t;
+      } else {
+        sg0 = sg, sd0 = sd, sp0 = sp, se0 = se, mode0 = mode;
+      }
+    }
+    if (!FINISH) {
+      if (live) *reinterpret_cast<f3u*>(st + 3 * gs) = f3u{A[0], A[1], A[2]};
+    } else {
+      if (live) acc_lane_finish(sh, A, keepc, kbits, inv, n_up, g, merged, merged_f32);
+      acc_lane_avg(sh, A, inv, live, avg_out + 3 * gs);
+    }
+  }
+  if (bad_picks | layout_picks) {
+    for (int k = 0; k < K; ++k) {
+      const int e = (((bad_picks >> k) & 1) ? FLEET_ERRBIT_BASE64 : 0) | (((layout_picks >> k) & 1) ? FLEET_ERRBIT_LAYOUT : 0);
+      if (e) atomicOr(status + picks.slot[k], e);
+    }
+  }
+  __syncthreads();  // the wave's slots were written by four (or two) of its lanes
+  if (lane < K) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    const size_t w = (size_t)blockIdx.x * (kAccNT / 64) + wave, waves = (size_t)gridDim.x * (kAccNT / 64);
+    d2* out = reinterpret_cast<d2*>(partials) + ((size_t)lane * waves + w) * 2;
+    out[0] = d2{kfp[wave][lane][0], kfp[wave][lane][1]};
+    out[1] = d2{kfp[wave][lane][2], kfp[wave][lane][3]};
+  }
+}
+
+// k_pool_kd_reduce over four sums per pick: the same lanes add the same waves in the same
+// order per component. sums[4 k + 0..3].
+__global__ void __launch_bounds__(kAccNT) k_pool_kf_reduce(const double* __restrict__ partials, int64_t waves,
+                                                           double* __restrict__ sums) {
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  __shared__ double red[4][kAccNT / 64];
+  const int k = blockIdx.x;
+  const d2* p = reinterpret_cast<const d2*>(partials) + (size_t)k * waves * 2;
+  d2 v = d2{0.0, 0.0}, u = d2{0.0, 0.0};
+  for (int64_t w = threadIdx.x; w < waves; w += kAccNT) {
+    v += p[2 * w];
+    u += p[2 * w + 1];
+  }
+  const double a = group_sum_f64<64>(v.x), b = group_sum_f64<64>(v.y);  // valid in lane 63
+  const double c = group_sum_f64<64>(u.x), d = group_sum_f64<64>(u.y);
+  if ((threadIdx.x & 63) == 63) {
+    red[0][threadIdx.x / 64] = a;
+    red[1][threadIdx.x / 64] = b;
+    red[2][threadIdx.x / 64] = c;
+    red[3][threadIdx.x / 64] = d;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    double s = 0.0;
+    for (int i = 0; i < kAccNT / 64; ++i) s += red[threadIdx.x][i];
+    sums[4 * k + threadIdx.x] = s;
+  }
+}
+
+// acc_lane_avg over a state: the avg row of a fold that ran without its finish (the
+// filter's refold, whose finish is k_acc_finish).
+__global__ void __launch_bounds__(kAccNT) k_acc_avg_row(const float* __restrict__ st, double inv, int64_t ng,
+                                                        const int32_t* __restrict__ hdr_block,
+                                                        float* __restrict__ avg_out) {
+  __shared__ AccShared sh;
+  (void)acc_block_open(sh, hdr_block);
+  for (int64_t base = (int64_t)blockIdx.x * kAccNT; base < ng; base += (int64_t)gridDim.x * kAccNT) {
+    const int64_t gl = base + threadIdx.x;
+    const bool live = gl < ng;
+    const int64_t gs = live ? gl : 0;
+    float A[3] = {0.f, 0.f, 0.f};
+    if (live) {
+      const f3u a = *reinterpret_cast<const f3u*>(st + 3 * gs);
+      A[0] = a.x, A[1] = a.y, A[2] = a.z;
+    }
+    acc_lane_avg(sh, A, inv, live, avg_out + 3 * gs);
+  }
+}
+
 // Element-wise kernels: a grid of whole blocks per CU (8 x 256 lanes fill a CU's wave
 // slots), striding over the groups, so the tables are copied into LDS once per block.
 static unsigned acc_grid(int64_t groups) {
@@ -657,6 +874,47 @@ hipError_t launch_pool_fold(const uint8_t* pool, size_t pitch, const int32_t* sl
 
 int64_t pool_kd_partial_doubles(const AccWindow& w) {
   return (int64_t)acc_grid(std::max<int64_t>(1, w.g_end - w.g_begin)) * (kAccNT / 64) * kAccBurst * 2;
+}
+int64_t pool_kf_partial_doubles(const AccWindow& w) { return 2 * pool_kd_partial_doubles(w); }
+
+// the picks, rows and modes of a launch by value; false for a mode that names no row, or
+// a row outside the slab: such a launch never reaches the kernel
+static bool pool_kd_args(const int32_t* slots, int K, const PoolKd& kd, PoolPicks* p, PoolKdRows* r, PoolKdModes* m) {
+  for (int k = 0; k < kAccBurst; ++k) {
+    p->slot[k] = k < K ? slots[k] : 0;
+    m->m[k] = k < K ? kd.mode[k] : 0;
+    r->prev[k] = k < K && (m->m[k] & kKdDiff) ? kd.prev[k] : -1;
+    r->out[k] = k < K && (m->m[k] & kKdStore) ? kd.out[k] : -1;
+    if ((m->m[k] & (kKdDiff | kKdStore)) && !(m->m[k] & kKdNorm)) return false;
+    if ((m->m[k] & kKdDiff) && (r->prev[k] < 0 || r->prev[k] >= kd.rows)) return false;
+    if ((m->m[k] & kKdStore) && (r->out[k] < 0 || r->out[k] >= kd.rows)) return false;
+  }
+  return true;
+}
+
+hipError_t launch_pool_fold_kf(const uint8_t* pool, size_t pitch, const int32_t* slots, float* st, int first, int K,
+                               const double* dampen, bool finish, double inv, const AccWindow& w, int* d_status,
+                               uint8_t* merged, float* merged_f32, const PoolKd& kd, const float* lastg,
+                               float* avg_out, hipStream_t s) {
+  if (K <= 0 || K > kAccBurst || w.g_begin != 0 || w.g_end <= 0 || (finish && !avg_out) || avg_out == lastg)
+    return hipErrorInvalidValue;
+  if (!kd.slab || !kd.partials || !kd.sums || kd.vpitch < (size_t)(3 * w.g_end)) return hipErrorInvalidValue;
+  PoolPicks p;
+  PoolKdRows r;
+  PoolKdModes m;
+  if (!pool_kd_args(slots, K, kd, &p, &r, &m)) return hipErrorInvalidValue;
+  const unsigned grid = acc_grid(w.g_end - w.g_begin);
+  hipError_t e = acc_launch(finish ? k_pool_fold_kf<true> : k_pool_fold_kf<false>, w, s, pool, pitch, p, st, first, K,
+                            acc_dampen(dampen, K), inv, w.n_up, w.g_begin, w.g_end, w.d_hdr_block, w.d_hfirst,
+                            d_status, merged, merged_f32, r, m, kd.lr, kd.slab, kd.vpitch, kd.partials, lastg, avg_out);
+  if (e != hipSuccess) return e;
+  k_pool_kf_reduce<<<dim3((unsigned)K), dim3(kAccNT), 0, s>>>(kd.partials, (int64_t)grid * (kAccNT / 64), kd.sums);
+  return hipGetLastError();
+}
+
+hipError_t launch_acc_avg_row(const float* st, double inv, const AccWindow& w, float* avg_out, hipStream_t s) {
+  if (!st || !avg_out) return hipErrorInvalidValue;
+  return acc_launch(k_acc_avg_row, w, s, st, inv, w.g_end - w.g_begin, w.d_hdr_block, avg_out);
 }
 
 hipError_t launch_pool_fold_kd(const uint8_t* pool, size_t pitch, const int32_t* slots, float* st, int first, int K,

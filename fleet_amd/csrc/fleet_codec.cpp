@@ -2818,6 +2818,347 @@ int fleet_kledger_update_device(fleet_kledger* l, const int32_t* picks, int K, c
   return kledger_commit(l, picks, K, norm_g, norm_diff, set);
 }
 
+// ------------------------------------------------------ Kardam Byzantine filter
+
+// What Kardam.checkByz reads of an update's picks (Kardam.java:136-185; CppNNUpdater.java:
+// 488 without its `true ||`), beside a ledger: lastGrad as two fp32 rows in upload
+// coordinates (d_lg[lg] is read by the update's kernel, d_lg[lg ^ 1] receives the avg of
+// the update's result as lastGrad decodes it, Q(f32(f64(A) / accepted)); the two swap when
+// a resolve ends with an average), currModel / lastModel as two rows of a slab (d_m, rows mc and mc ^ 1), and the
+// optimistic result of the pending update (d_out, d_f32).
+struct fleet_kfilter {
+  fleet_kledger* l = nullptr;
+  size_t n_w = 0, n_b = 0, n_m = 0, mpitch = 0;
+  int edges = 0;
+  float* d_lg[2] = {nullptr, nullptr};
+  int lg = 0;
+  bool has_last = false;
+  uint8_t* d_out = nullptr;     // the merged bytes of the pending update
+  float* d_f32 = nullptr;       // and their decodeFloat
+  double* d_part = nullptr;     // one launch's per-wave partials (four sums a pick)
+  double* d_sums = nullptr;     // 4 sums per pick of an update
+  double* h_sums = nullptr;     // pinned
+  float* d_m = nullptr;         // two model rows
+  int mc = 0;
+  bool has_model = false, has_last_model = false;  // row mc was staged since the last resolve / row mc ^ 1 holds lastModel
+  float* d_w = nullptr;         // the host form's staging of a model
+  float* d_b = nullptr;
+  double* d_mpart = nullptr;    // kAccBurst * kMlMaxTiles partials
+  double* d_msq = nullptr;      // {row norm, pair norm}
+  double* h_msq = nullptr;      // pinned
+  // the pending update
+  bool pending = false;
+  std::vector<int32_t> picks;
+  std::vector<double> dampen;
+};
+
+namespace {
+
+static void release_kfilter(fleet_kfilter* f) {
+  for (void* d : {(void*)f->d_lg[0], (void*)f->d_lg[1], (void*)f->d_out, (void*)f->d_f32, (void*)f->d_part, (void*)f->d_sums, (void*)f->d_m,
+                  (void*)f->d_w, (void*)f->d_b, (void*)f->d_mpart, (void*)f->d_msq})
+    if (d) (void)hipFree(d);
+  for (void* h : {(void*)f->h_sums, (void*)f->h_msq})
+    if (h) (void)hipHostFree(h);
+  delete f;
+}
+
+// kledger_fold through the filter form: the merged bytes and their fp32 go to the filter's
+// own rows, the avg to the lastGrad row that is not read, the four sums of every pick to
+// d_sums[4 k ..)
+static int kfilter_fold(fleet_kfilter* f, const int32_t* picks, int K, const double* dampen, double lr, hipStream_t s) {
+  fleet_kledger* l = f->l;
+  fleet_pool* p = l->p;
+  fleet_ctx* c = p->c;
+  constexpr int B = fleet::kAccBurst;
+  HIP_TRY(c, hipMemsetAsync(p->d_status, 0, sizeof(int) * (size_t)p->slots, s));
+  for (int k0 = 0; k0 < K; k0 += B) {
+    const int kc = std::min(B, K - k0);
+    const fleet::PoolKd kd{lr, l->k_mode.data() + k0, l->k_prev.data() + k0, l->k_out.data() + k0, l->d_slab, l->vpitch,
+                           l->rows, f->d_part, f->d_sums + 4 * (size_t)k0};
+    HIP_TRY(c, fleet::launch_pool_fold_kf(p->d_rows, p->pitch, picks + k0, p->d_state, k0 == 0, kc, dampen + k0,
+                                          k0 + kc == K, (double)1 / K, p->w.launch(), p->d_status, f->d_out, f->d_f32,
+                                          kd, f->has_last ? f->d_lg[f->lg] : nullptr, f->d_lg[f->lg ^ 1], s));
+  }
+  HIP_TRY(c, hipMemcpyAsync(p->h_status, p->d_status, sizeof(int) * (size_t)p->slots, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(f->h_sums, f->d_sums, sizeof(double) * 4 * (size_t)K, hipMemcpyDeviceToHost, s));
+  return FLEET_OK;
+}
+
+// after the stream was synchronised: kledger_commit on the first two sums of every pick,
+// and on a clean verdict the filter's norms and the pending update
+static int kfilter_commit(fleet_kfilter* f, const int32_t* picks, int K, const double* dampen, double* norm_g,
+                          double* norm_diff, uint8_t* set, double* norm_p, double* norm_pdiff) {
+  fleet_kledger* l = f->l;
+  for (int k = 0; k < K; ++k) l->h_sums[2 * k] = f->h_sums[4 * k], l->h_sums[2 * k + 1] = f->h_sums[4 * k + 1];
+  const int rc = kledger_commit(l, picks, K, norm_g, norm_diff, set);
+  if (rc) return rc;
+  for (int k = 0; k < K; ++k) {
+    norm_p[k] = std::sqrt(f->h_sums[4 * k + 2]);
+    norm_pdiff[k] = f->has_last ? std::sqrt(f->h_sums[4 * k + 3]) : std::nan("");
+  }
+  f->picks.assign(picks, picks + K);
+  f->dampen.assign(dampen, dampen + K);
+  f->pending = true;
+  return FLEET_OK;
+}
+
+// the device outputs of an update or a resolve from the filter's rows, on s
+static int kfilter_copy_out(fleet_kfilter* f, void* d_merged, void* d_merged_f32, hipStream_t s) {
+  fleet_pool* p = f->l->p;
+  fleet_ctx* c = p->c;
+  HIP_TRY(c, hipMemcpyAsync(d_merged, f->d_out, 16 * p->w.ng, hipMemcpyDeviceToDevice, s));
+  if (d_merged_f32)
+    HIP_TRY(c, hipMemcpyAsync(d_merged_f32, f->d_f32, sizeof(float) * p->w.n, hipMemcpyDeviceToDevice, s));
+  return FLEET_OK;
+}
+
+// A resolve's checks (FLEET_ERR_ARG with everything untouched) and the count of accepted picks.
+static int kfilter_resolve_args(fleet_kfilter* f, const uint8_t* accept, int K, const char* what, int* accepted) {
+  fleet_pool* p = f->l->p;
+  fleet_ctx* c = p->c;
+  if (!f->pending) return fail(c, FLEET_ERR_ARG, "%s: no update is pending", what);
+  if (K != (int)f->picks.size())
+    return fail(c, FLEET_ERR_ARG, "%s: %d decisions for the pending update's %zu picks", what, K, f->picks.size());
+  for (int k = 0; k < K; ++k)
+    if (!p->occupied[f->picks[k]])
+      return fail(c, FLEET_ERR_ARG, "%s: pick %d's slot %d holds no upload any more", what, k, f->picks[k]);
+  int n = 0;
+  for (int k = 0; k < K; ++k) n += accept[k] ? 1 : 0;
+  *accepted = n;
+  return FLEET_OK;
+}
+
+// The refold of a proper subset (CppNNUpdater.java:490-508 over the accepted picks): the
+// pool's fold without its finish over the accepted slots in pick order, then the finish
+// with the last of all K picks' row, so the header and the unwalked slots are that pick's
+// whether it was accepted or not (:508, pickedG). Overwrites the filter's output rows.
+static int kfilter_refold(fleet_kfilter* f, const uint8_t* accept, int accepted, hipStream_t s) {
+  fleet_pool* p = f->l->p;
+  fleet_ctx* c = p->c;
+  constexpr int B = fleet::kAccBurst;
+  const int K = (int)f->picks.size();
+  std::vector<int32_t> slots;
+  std::vector<double> d;
+  for (int k = 0; k < K; ++k)
+    if (accept[k]) slots.push_back(f->picks[k]), d.push_back(f->dampen[k]);
+  HIP_TRY(c, hipMemsetAsync(p->d_status, 0, sizeof(int) * (size_t)p->slots, s));
+  for (int k0 = 0; k0 < accepted; k0 += B) {
+    const int kc = std::min(B, accepted - k0);
+    HIP_TRY(c, fleet::launch_pool_fold(p->d_rows, p->pitch, slots.data() + k0, p->d_state, k0 == 0, kc, d.data() + k0, false,
+                                       (double)1 / accepted, p->w.launch(), p->d_status, nullptr, nullptr, s));
+  }
+  HIP_TRY(c, fleet::launch_acc_finish(p->d_rows + (size_t)f->picks[K - 1] * p->pitch, p->d_state, (double)1 / accepted,
+                                      p->w.launch(), f->d_out, f->d_f32, s));
+  HIP_TRY(c, fleet::launch_acc_avg_row(p->d_state, (double)1 / accepted, p->w.launch(), f->d_lg[f->lg ^ 1], s));
+  HIP_TRY(c, hipMemcpyAsync(p->h_status, p->d_status, sizeof(int) * (size_t)p->slots, hipMemcpyDeviceToHost, s));
+  return FLEET_OK;
+}
+
+// a resolve that ended with an average: lastGrad and lastModel advance (CppNNUpdater.java:510-511)
+static void kfilter_advance(fleet_kfilter* f) {
+  f->lg ^= 1;
+  f->has_last = true;
+  if (f->has_model) {
+    f->mc ^= 1;
+    f->has_last_model = true;
+  }
+}
+
+// currModel from device vectors on s, its norm and the norm of its difference to lastModel
+static int kfilter_model_on(fleet_kfilter* f, const float* d_w, const float* d_b, hipStream_t s, double* norm_model,
+                            double* norm_model_diff) {
+  fleet_ctx* c = f->l->p->c;
+  HIP_TRY(c, fleet::launch_mrow_stage(d_w, (int64_t)f->n_w, d_b, (int64_t)f->n_b, f->n_b ? (int64_t)f->edges : 0,
+                                      f->d_m + (size_t)f->mc * f->mpitch, f->d_mpart, f->d_msq, s));
+  if (f->has_last_model) {
+    const int32_t cur = f->mc, prev = f->mc ^ 1;
+    HIP_TRY(c, fleet::launch_mrow_pair_norms(f->d_m, f->mpitch, 2, (int64_t)f->n_m, &cur, &prev, 1, f->d_mpart, f->d_msq + 1, s));
+  }
+  HIP_TRY(c, hipMemcpyAsync(f->h_msq, f->d_msq, sizeof(double) * 2, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  f->has_model = true;
+  *norm_model = std::sqrt(f->h_msq[0]);
+  *norm_model_diff = f->has_last_model ? std::sqrt(f->h_msq[1]) : std::nan("");
+  return FLEET_OK;
+}
+
+}  // namespace
+
+int fleet_kfilter_create(fleet_kledger* l, size_t n_weights, size_t n_biases, int graph_edges, fleet_kfilter** out) {
+  if (!l || !out) return FLEET_ERR_ARG;
+  *out = nullptr;
+  if (graph_edges < 0) return FLEET_ERR_ARG;
+  fleet_pool* p = l->p;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  if (n_weights >= (size_t)fleet::kMlMaxValues || n_biases >= (size_t)fleet::kMlMaxValues)
+    return fail(c, FLEET_ERR_ARG, "fleet_kfilter_create: %zu weights, %zu biases", n_weights, n_biases);
+  const size_t n = n_biases * (size_t)graph_edges + n_weights;
+  if (n == 0 || n >= (size_t)fleet::kMlMaxValues) return fail(c, FLEET_ERR_ARG, "fleet_kfilter_create: a model of %zu values", n);
+  fleet_kfilter* f = new fleet_kfilter();
+  f->l = l;
+  f->n_w = n_weights, f->n_b = n_biases, f->edges = graph_edges, f->n_m = n;
+  f->mpitch = (n + 3) / 4 * 4;
+  const size_t lg_bytes = p->w.state_bytes(), out_bytes = p->w.row_bytes();
+  const size_t part_bytes = sizeof(double) * (size_t)fleet::pool_kf_partial_doubles(p->w.launch());
+  const size_t sums_bytes = sizeof(double) * 4 * (size_t)p->slots, m_bytes = sizeof(float) * 2 * f->mpitch;
+  const bool ok =
+      hipMalloc((void**)&f->d_lg[0], lg_bytes) == hipSuccess && hipMemset(f->d_lg[0], 0, lg_bytes) == hipSuccess &&
+      hipMalloc((void**)&f->d_lg[1], lg_bytes) == hipSuccess && hipMemset(f->d_lg[1], 0, lg_bytes) == hipSuccess &&
+      hipMalloc((void**)&f->d_out, out_bytes) == hipSuccess && hipMemset(f->d_out, 0, out_bytes) == hipSuccess &&
+      hipMalloc((void**)&f->d_f32, lg_bytes) == hipSuccess && hipMemset(f->d_f32, 0, lg_bytes) == hipSuccess &&
+      hipMalloc((void**)&f->d_part, part_bytes) == hipSuccess && hipMalloc((void**)&f->d_sums, sums_bytes) == hipSuccess &&
+      hipHostMalloc((void**)&f->h_sums, sums_bytes, hipHostMallocDefault) == hipSuccess &&
+      hipMalloc((void**)&f->d_m, m_bytes) == hipSuccess && hipMemset(f->d_m, 0, m_bytes) == hipSuccess &&
+      hipMalloc((void**)&f->d_w, sizeof(float) * std::max<size_t>(1, n_weights)) == hipSuccess &&
+      hipMalloc((void**)&f->d_b, sizeof(float) * std::max<size_t>(1, n_biases)) == hipSuccess &&
+      hipMalloc((void**)&f->d_mpart, sizeof(double) * fleet::kAccBurst * fleet::kMlMaxTiles) == hipSuccess &&
+      hipMalloc((void**)&f->d_msq, sizeof(double) * 2) == hipSuccess &&
+      hipHostMalloc((void**)&f->h_msq, sizeof(double) * 2, hipHostMallocDefault) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    release_kfilter(f);
+    return fail(c, FLEET_ERR_NOMEM, "fleet_kfilter_create: allocating the rows of %zu groups and %zu model values failed", p->w.ng, n);
+  }
+  *out = f;
+  return FLEET_OK;
+}
+
+void fleet_kfilter_destroy(fleet_kfilter* f) {
+  if (!f) return;
+  fleet_ctx* c = f->l->p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard dg(c->device);
+  (void)hipStreamSynchronize(c->stream);
+  release_kfilter(f);
+}
+
+int fleet_kfilter_has_last(const fleet_kfilter* f) {
+  if (!f) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(f->l->p->c->mu);
+  return f->has_last ? 1 : 0;
+}
+
+int fleet_kfilter_set_model(fleet_kfilter* f, const float* weights, const float* biases, double* norm_model,
+                            double* norm_model_diff) {
+  if (!f || (f->n_w && !weights) || (f->n_b && !biases) || !norm_model || !norm_model_diff) return FLEET_ERR_ARG;
+  fleet_ctx* c = f->l->p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  if (f->n_w) HIP_TRY(c, hipMemcpyAsync(f->d_w, weights, sizeof(float) * f->n_w, hipMemcpyHostToDevice, c->stream));
+  if (f->n_b) HIP_TRY(c, hipMemcpyAsync(f->d_b, biases, sizeof(float) * f->n_b, hipMemcpyHostToDevice, c->stream));
+  return kfilter_model_on(f, f->d_w, f->d_b, c->stream, norm_model, norm_model_diff);
+}
+
+int fleet_kfilter_set_model_device(fleet_kfilter* f, const float* d_weights, const float* d_biases, double* norm_model,
+                                   double* norm_model_diff, void* stream) {
+  if (!f || (f->n_w && !d_weights) || (f->n_b && !d_biases) || !norm_model || !norm_model_diff) return FLEET_ERR_ARG;
+  fleet_ctx* c = f->l->p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  return kfilter_model_on(f, d_weights, d_biases, pick(c, stream), norm_model, norm_model_diff);
+}
+
+int fleet_kfilter_update(fleet_kfilter* f, const int32_t* picks, int K, const double* dampen, const int32_t* worker,
+                         const int32_t* epoch, double lr, char* merged, size_t cap, size_t* out_len, float* merged_f32,
+                         double* norm_g, double* norm_diff, uint8_t* set, double* norm_p, double* norm_pdiff) {
+  if (!f || !picks || !dampen || !merged || K <= 0 || !worker || !epoch || !norm_g || !norm_diff || !set || !norm_p ||
+      !norm_pdiff)
+    return FLEET_ERR_ARG;
+  fleet_kledger* l = f->l;
+  fleet_pool* p = l->p;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  f->pending = false;
+  if (!std::isfinite(lr)) return fail(c, FLEET_ERR_ARG, "fleet_kfilter_update: the learning rate is not finite");
+  int rc = pool_update_args(p, picks, K, "fleet_kfilter_update");
+  if (rc || (rc = kledger_resolve(l, K, worker, epoch, "fleet_kfilter_update"))) return rc;
+  if (out_len) *out_len = p->w.len;
+  if (cap < p->w.len) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu", cap, p->w.len);
+  if ((rc = settle(c, &p->fly, c->stream, true))) return rc;
+  if ((rc = kfilter_fold(f, picks, K, dampen, lr, c->stream))) return rc;
+  if ((rc = window_read_back(c, p->w, f->d_out, f->d_f32, merged, merged_f32, c->stream))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return kfilter_commit(f, picks, K, dampen, norm_g, norm_diff, set, norm_p, norm_pdiff);
+}
+
+int fleet_kfilter_update_device(fleet_kfilter* f, const int32_t* picks, int K, const double* dampen,
+                                const int32_t* worker, const int32_t* epoch, double lr, void* d_merged,
+                                void* d_merged_f32, double* norm_g, double* norm_diff, uint8_t* set, double* norm_p,
+                                double* norm_pdiff, void* stream) {
+  if (!f || !picks || !dampen || !d_merged || K <= 0 || !worker || !epoch || !norm_g || !norm_diff || !set || !norm_p ||
+      !norm_pdiff)
+    return FLEET_ERR_ARG;
+  fleet_kledger* l = f->l;
+  fleet_pool* p = l->p;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  f->pending = false;
+  if (!std::isfinite(lr)) return fail(c, FLEET_ERR_ARG, "fleet_kfilter_update_device: the learning rate is not finite");
+  int rc = pool_update_args(p, picks, K, "fleet_kfilter_update_device");
+  if (rc || (rc = kledger_resolve(l, K, worker, epoch, "fleet_kfilter_update_device"))) return rc;
+  hipStream_t s = pick(c, stream);
+  if ((rc = settle(c, &p->fly, s, false))) return rc;
+  if ((rc = kfilter_fold(f, picks, K, dampen, lr, s))) return rc;
+  if ((rc = kfilter_copy_out(f, d_merged, d_merged_f32, s))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(s));
+  p->fly.done();
+  return kfilter_commit(f, picks, K, dampen, norm_g, norm_diff, set, norm_p, norm_pdiff);
+}
+
+int fleet_kfilter_resolve(fleet_kfilter* f, const uint8_t* accept, int K, char* merged, size_t cap, size_t* out_len,
+                          float* merged_f32) {
+  if (!f || !accept || !merged || !out_len || K <= 0) return FLEET_ERR_ARG;
+  fleet_pool* p = f->l->p;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  int accepted = 0;
+  int rc = kfilter_resolve_args(f, accept, K, "fleet_kfilter_resolve", &accepted);
+  if (rc) return rc;
+  if (accepted && cap < p->w.len) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu", cap, p->w.len);
+  f->pending = false;
+  *out_len = 0;
+  if (!accepted) return FLEET_OK;  // no average: lastGrad and lastModel stay (CppNNUpdater.java:506)
+  if ((rc = settle(c, &p->fly, c->stream, true))) return rc;
+  if (accepted < K && (rc = kfilter_refold(f, accept, accepted, c->stream))) return rc;
+  if ((rc = window_read_back(c, p->w, f->d_out, f->d_f32, merged, merged_f32, c->stream))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (accepted < K && (rc = pool_verdict(p, f->picks.data(), K))) return rc;
+  *out_len = p->w.len;
+  kfilter_advance(f);
+  return FLEET_OK;
+}
+
+int fleet_kfilter_resolve_device(fleet_kfilter* f, const uint8_t* accept, int K, void* d_merged, void* d_merged_f32,
+                                 size_t* out_len, void* stream) {
+  if (!f || !accept || !d_merged || !out_len || K <= 0) return FLEET_ERR_ARG;
+  fleet_pool* p = f->l->p;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  int accepted = 0;
+  int rc = kfilter_resolve_args(f, accept, K, "fleet_kfilter_resolve_device", &accepted);
+  if (rc) return rc;
+  f->pending = false;
+  *out_len = 0;
+  if (!accepted) return FLEET_OK;
+  hipStream_t s = pick(c, stream);
+  if ((rc = settle(c, &p->fly, s, false))) return rc;
+  if (accepted < K && (rc = kfilter_refold(f, accept, accepted, s))) return rc;
+  if ((rc = kfilter_copy_out(f, d_merged, d_merged_f32, s))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(s));
+  p->fly.done();
+  if (accepted < K && (rc = pool_verdict(p, f->picks.data(), K))) return rc;
+  *out_len = p->w.len;
+  kfilter_advance(f);
+  return FLEET_OK;
+}
+
 // --------------------------------------------------------- Kardam model ledger
 
 // Kardam.java's `models` map (worker -> model, Kardam.java:114-125) over a slab of fp32

@@ -126,6 +126,21 @@ int64_t pool_kd_partial_doubles(const AccWindow& w);
 hipError_t launch_pool_fold_kd(const uint8_t* pool, size_t pitch, const int32_t* slots, float* st, int first, int K,
                                const double* dampen, bool finish, double inv, const AccWindow& w, int* d_status,
                                uint8_t* merged, float* merged_f32, const PoolKd& kd, hipStream_t s);
+// launch_pool_fold_kd's filter form (k_pool_fold_kf, then k_pool_kf_reduce): beside the
+// ledger's sums, per pick the squared norm of its dampened value p over the flat slots and,
+// with `lastg` (one fp32 row of >= 3 groups floats in upload coordinates; nullptr: none),
+// that of Q(p - lastg), whatever the pick's mode. With `finish` the launch also leaves the
+// update's avg, Q(f32(f64(A) * inv)) per slot -- what the next update's lastGrad decodes to,
+// which decodeFloat(merged) is not where Q is not idempotent --, in avg_out (another row).
+// launch_acc_avg_row gives the same row from a state that a fold without finish left. sums[4 k + {0, 1, 2, 3}] = pick k's sg,
+// sd, sp, se, the first two bit for bit launch_pool_fold_kd's; partials holds
+// pool_kf_partial_doubles(w) doubles.
+int64_t pool_kf_partial_doubles(const AccWindow& w);
+hipError_t launch_pool_fold_kf(const uint8_t* pool, size_t pitch, const int32_t* slots, float* st, int first, int K,
+                               const double* dampen, bool finish, double inv, const AccWindow& w, int* d_status,
+                               uint8_t* merged, float* merged_f32, const PoolKd& kd, const float* lastg,
+                               float* avg_out, hipStream_t s);
+hipError_t launch_acc_avg_row(const float* st, double inv, const AccWindow& w, float* avg_out, hipStream_t s);
 // The Kardam model ledger (mledger_kernels.hip). A model version is one fp32 row of
 // 4 * ceil(n / 4) floats, n = n_b * reps + n_w < kMlMaxValues values in getModelParams'
 // order, row[i] = Q(param(i)), the padding 0. A row or a pair runs on mrow_tiles(n) <=

@@ -78,14 +78,53 @@ def similarity(x: Sequence[int], y: Sequence[int]) -> float:
     return b
 
 
+def percentile(values: Sequence[float], p: float) -> float:
+    """Helpers.percentile (commonLib/utils/Helpers.java:52-59): commons-math3 3.6.1's
+    ``new Percentile().evaluate(sorted values, p)`` with its default estimation type
+    (``Percentile.EstimationType.LEGACY``, the algorithm of the class's Javadoc): with n
+    values, n = 1 gives that value; otherwise ``pos = p * (n + 1) / 100``, ``pos < 1`` gives
+    the minimum, ``pos >= n`` the maximum, and anything between
+    ``lower + (pos - floor(pos)) * (upper - lower)`` with ``lower`` and ``upper`` the sorted
+    values at ranks ``floor(pos)`` and ``floor(pos) + 1`` counted from 1. As there, no value
+    gives NaN and a ``p`` outside (0, 100] is an error. Non-finite values are outside what
+    is pinned here: Java's sort and the library's NaN strategy order them their own way."""
+    if not (0 < p <= 100):
+        raise ValueError(f"out of bounds quantile value: {p}, must be in (0, 100]")
+    v = sorted(float(x) for x in values)
+    n = len(v)
+    if n == 0:
+        return float("nan")
+    if n == 1:
+        return v[0]
+    pos = p * (n + 1) / 100
+    fpos = math.floor(pos)
+    if pos < 1:
+        return v[0]
+    if pos >= n:
+        return v[n - 1]
+    lower, upper = v[int(fpos) - 1], v[int(fpos)]
+    return lower + (pos - fpos) * (upper - lower)
+
+
+def _java_div(a: float, b: float) -> float:
+    """a / b in IEEE double arithmetic, as Java divides: x/0 is an infinity, 0/0 NaN."""
+    try:
+        return a / b
+    except ZeroDivisionError:
+        if a != a or a == 0:
+            return float("nan")
+        return math.copysign(math.inf, a) * math.copysign(1.0, b)
+
+
 class Kardam:
     """utils/Kardam.java's bookkeeping (setGrad :48-62, setModel :93-106, updateLip
     :190-203) with its O(N) vector work on the GPU: the gradient texts and norms of
     all picked uploads come from one ``Codec.kardam_grads`` call,
     the model-difference norm from ``subtractNative`` + ``getNorm`` over two texts, or,
     with a model ledger (``apply_model``), from one device pass over the picked versions'
-    resident rows. ``checkByz`` is not rebuilt: CppNNUpdater bypasses it (``if (true ||
-    ...)``, :488)."""
+    resident rows. ``check_byz`` is ``checkByz`` (:136-185) on the norms a
+    ``fleet_amd.KardamFilter`` computes: CppNNUpdater bypasses it (``if (true || ...)``,
+    :488), ``FleetUpdater(kardam_filter=True)`` runs it."""
 
     def __init__(self, codec, workers: int = 10, ledger=None, model_ledger=None):
         self.codec = codec
@@ -102,6 +141,36 @@ class Kardam:
         self.model_diff_norm = {}
         self.grad_diff_norm = {}
         self.lips = {}
+        self.subsequent_rejects = 0
+
+    def check_byz(self, worker: int, norm_p: float, norm_pdiff: float, norm_model: float, norm_model_diff: float,
+                  has_last: bool) -> bool:
+        """checkByz (Kardam.java:136-185) for one pick from its norms: ``norm_p`` =
+        getNorm(g), ``norm_pdiff`` = getNorm(g.subtract(lastGrad)), ``norm_model`` =
+        getNorm(currModel), ``norm_model_diff`` = getNorm(currModel.subtract(lastModel));
+        ``has_last``: lastGrad != null. ``worker`` is not read, as there. Every worker's lips
+        are sorted in place on the way (:149), which changes the value a later ``update_lip``
+        drops."""
+        if not self.lips:  # :138-141
+            self.subsequent_rejects = 0
+            return True
+        top = []
+        for w in self.lips:  # :142-151
+            top.append(max(self.lips[w]))
+            self.lips[w].sort()
+        high = percentile(top, 200 / 3.0)  # :156
+        if not has_last:  # :159-162
+            check_norm = _java_div(norm_p, norm_model)
+        else:  # :163-169
+            check_norm = _java_div(norm_pdiff, norm_model_diff)
+        if check_norm <= high:  # :170-173 (NaN compares false: rejected below)
+            self.subsequent_rejects = 0
+            return True
+        if self.subsequent_rejects == self.workers:  # :174-178
+            self.subsequent_rejects = 0
+            return True
+        self.subsequent_rejects += 1  # :179-182
+        return False
 
     def set_grads(self, worker_ids, uploads, dampen, lr: float, epochs):
         """setGrad for each picked upload: one device pass computes every g_c and its
@@ -185,7 +254,7 @@ class FleetUpdater:
     def __init__(self, codec, layout, M: int, lrates: Sequence[float], weights, fc_bias, policy: int = 0,
                  alpha: float = 0.0, stale_size: int = 0, num_labels: int = 10, has_outlier: bool = False,
                  streaming: bool = False, picker=None, pool_slots: Optional[int] = None, kardam=None,
-                 kardam_model=None, kardam_models=None, model=None):
+                 kardam_model=None, kardam_models=None, model=None, kardam_filter: bool = False):
         if model is None and (weights is None or fc_bias is None):
             raise ValueError("weights and fc_bias are the model the updater steps: give them, or model= (a "
                              "fleet_amd.ResidentModel that holds them in HBM)")
@@ -195,6 +264,9 @@ class FleetUpdater:
         if kardam is not None and (picker is None or (kardam_model is None and kardam_models is None)):
             raise ValueError("Kardam's bookkeeping runs in the staleSize > 0 branch: kardam needs a picker and a "
                              "kardam_model or kardam_models")
+        if kardam_filter and (kardam is None or kardam_models is None):
+            raise ValueError("kardam_filter runs checkByz on the picks of the pooled branch: it needs a picker, kardam "
+                             "and kardam_models (the model whose newest version is currModel)")
         if stale_size != 0 and picker is None:
             raise NotImplementedError("staleness simulation (StalenessSimulator) is not rebuilt: staleSize != 0 needs a "
                                       "picker")
@@ -257,6 +329,14 @@ class FleetUpdater:
         self.kardam_models = kardam_models
         self._ledger = None
         self._mledger = None
+        # kardam_filter: the filter CppNNUpdater bypasses (`true ||`, :488). An update then asks a
+        # fleet_amd.KardamFilter for every pick's checkByz norms in the pass that folds the picks,
+        # decides per pick in the Kardam loop (modelsSize() < staleSize or Kardam.check_byz) and
+        # resolves: the average is over the accepted picks, and an update none of whose picks was
+        # accepted has no average -- no model step, the epoch stays, update returns None (:506).
+        self.kardam_filter = bool(kardam_filter)
+        self._filter = None
+        self.last_accept: Optional[List[bool]] = None
 
     def _dampen_of(self, p: "Pending") -> float:
         """getDampen for one pick (:463-464) from the current epoch and label vector."""
@@ -338,6 +418,8 @@ class FleetUpdater:
         versions = None
         if self.kardam is not None and self.kardam_models is not None:
             versions = self._kardam_versions(picked)  # before anything changes
+        if self.kardam_filter:
+            return self._update_filtered(pool, picked, dampen, versions)
         try:
             if self.model is not None:
                 mu8, mf32 = self._device_out(pool.length)
@@ -362,11 +444,7 @@ class FleetUpdater:
                         want_f32=True)
                 kd = (models, diff, was_set)
         except Exception as e:
-            bad = set(getattr(e, "slots", ()))  # Base64Error / LayoutError: the slots at fault leave, the model stays
-            for q in self.acc:
-                if q.slot in bad:
-                    pool.drop(q.slot)
-            self.acc = [q for q in self.acc if q.slot not in bad]
+            self._drop_at_fault(pool, e)
             raise
         if kd is not None and versions is not None:
             self._kardam_models_loop(picked, *kd)
@@ -397,6 +475,78 @@ class FleetUpdater:
         self.last_merged = merged
         return merged
 
+    def _drop_at_fault(self, pool, e) -> None:
+        """Base64Error / LayoutError of an update: the slots at fault leave, the model stays."""
+        bad = set(getattr(e, "slots", ()))
+        for q in self.acc:
+            if q.slot in bad:
+                pool.drop(q.slot)
+        self.acc = [q for q in self.acc if q.slot not in bad]
+
+    def _update_filtered(self, pool, picked, dampen, versions) -> Optional[bytes]:
+        """The update over the picked uploads with Kardam's filter (:417-516, :488 without its
+        `true ||`): currModel's norms, one KardamFilter.update for every pick's norms and the
+        optimistic result, the Kardam loop with the decision after each pick's updateLip, the
+        resolve over what was accepted."""
+        from . import ResidentModel
+        km = self.kardam_models
+        n_models = km.modelsSize()
+        if self._ledger is None:
+            self._ledger = self.kardam.ledger = pool.ledger(self.kardam.workers)
+        if self._filter is None:
+            nw, nb, ge, _ = km.shape()
+            self._filter = self._ledger.filter(nw, nb, ge)
+        f = self._filter
+        slots, epochs = [q.slot for q in picked], [q.epoch for q in picked]
+        workers = [-1 if v is None else q.client_id for q, v in zip(picked, versions)]
+        try:
+            if isinstance(km, ResidentModel):  # currModel (:417)
+                norm_model, norm_model_diff = f.set_model_device(*km.version_tensors(n_models - 1))
+            else:
+                norm_model, norm_model_diff = f.set_model(*km.export(n_models - 1))
+            has_last = f.has_last
+            if self.model is not None:
+                mu8, mf32 = self._device_out(pool.length)
+                _, diff, was_set, norm_p, norm_pdiff = f.update_device(
+                    slots, dampen, workers, epochs, float(self.model.getLrate()), mu8, mf32)
+            else:
+                _, _, _, diff, was_set, norm_p, norm_pdiff = f.update(slots, dampen, workers, epochs, float(self.lr))
+        except Exception as e:
+            self._drop_at_fault(pool, e)
+            raise
+        accept: List[bool] = []
+
+        def decide(k: int) -> None:  # :488
+            accept.append(n_models < self.stale_size or self.kardam.check_byz(
+                picked[k].client_id, float(norm_p[k]), float(norm_pdiff[k]), norm_model, norm_model_diff, has_last))
+        self._kardam_models_loop(picked, versions, diff, was_set, decide)
+        self.last_accept = list(accept)
+        window = [0] * len(self.global_labels)
+        for q in picked:
+            for j, v in enumerate(q.labels[: len(window)]):
+                window[j] += v
+        for j, v in enumerate(window):
+            self.global_labels[j] += v
+        merged = None
+        if self.model is not None:
+            if f.resolve_device(accept, mu8, mf32):
+                merged = self._step_resident(pool.length)
+        else:
+            r = f.resolve(accept, want_f32=True)
+            if r is not None:
+                merged, grad = r
+                if self.curr_epoch < len(self.lrates):
+                    self.lr = np.float32(self.lrates[self.curr_epoch])
+                self.weights, self.fc_bias = self.codec.descent(self.weights, self.fc_bias, grad, self.layout, self.lr)
+        if merged is not None:  # avg != null (:506-512)
+            self.curr_epoch += 1
+            self.last_merged = merged
+        for q in picked:  # the picked uploads leave `acc` whatever was decided (:421, :516)
+            pool.drop(q.slot)
+        gone = {q.slot for q in picked}
+        self.acc = [q for q in self.acc if q.slot not in gone]
+        return merged
+
     def _kardam_versions(self, picked) -> List[Optional[int]]:
         """The gate of :472-474 for each pick, on ``kardam_models``: the index of the picked
         model in ``models`` (modelsSize()-1-tau), or None when Kardam does not run for the pick
@@ -410,9 +560,10 @@ class FleetUpdater:
             out.append(v if v >= 0 and n == self.stale_size else None)
         return out
 
-    def _kardam_models_loop(self, picked, versions, diff, was_set) -> None:
+    def _kardam_models_loop(self, picked, versions, diff, was_set, decide=None) -> None:
         """setModel for every pick from one model-ledger update, then the loop's host part in
-        pick order (:476-480): apply_model, apply, update_lip."""
+        pick order (:476-480): apply_model, apply, update_lip. ``decide(k)``, when given, runs
+        after pick k's part, for every pick (:488)."""
         m = self._mledger
         if m is None:
             m = self.kardam.model_ledger
@@ -426,12 +577,13 @@ class FleetUpdater:
                 ids[v] = m.stage_model(self.kardam_models, v)
         _, mdiff, status = m.update([-1 if v is None else ids[v] for v in versions],
                                     [-1 if v is None else q.client_id for q, v in zip(picked, versions)])
-        for q, v, md, ms, dn, st in zip(picked, versions, mdiff, status, diff, was_set):
-            if v is None:
-                continue
-            self.kardam.apply_model(q.client_id, int(ms), float(md))
-            if self.kardam.apply(q.client_id, bool(st), float(dn)):
-                self.kardam.update_lip(q.client_id)
+        for k, (q, v, md, ms, dn, st) in enumerate(zip(picked, versions, mdiff, status, diff, was_set)):
+            if v is not None:
+                self.kardam.apply_model(q.client_id, int(ms), float(md))
+                if self.kardam.apply(q.client_id, bool(st), float(dn)):
+                    self.kardam.update_lip(q.client_id)
+            if decide is not None:
+                decide(k)
 
     def _finish_batch(self, fused=None) -> bytes:
         """The M-th call's part after the arrival (:420-421, :463-464, :490-516): picks the

@@ -511,6 +511,83 @@ int fleet_kledger_update_device(fleet_kledger* ledger, const int32_t* picks, int
                                 const int32_t* worker, const int32_t* epoch, double lr, void* d_merged,
                                 void* d_merged_f32, double* norm_g, double* norm_diff, uint8_t* set, void* stream);
 
+/* Kardam Byzantine filter: what checkByz reads of an update's picks -------------
+ * With the `true ||` of CppNNUpdater.java:488 removed a pick enters `avg` only if
+ *   modelsSize() < staleSize || kardam.checkByz(id, pickedGrad, lastGrad, currModel, lastModel, tau)
+ * and checkByz (Kardam.java:136-185) compares checkNorm -- getNorm(pickedGrad) /
+ * getNorm(currModel) while lastGrad == null, else getNorm(pickedGrad.subtract(lastGrad)) /
+ * getNorm(currModel.subtract(lastModel)) -- with a percentile of the workers' Lipschitz
+ * coefficients. pickedGrad is the pick's dampened flat gradient p before the learning rate,
+ * lastGrad the `avg` of the last update that had one (:510), currModel
+ * getModelParametersNative(modelsSize()-1) at the start of the update (:417), lastModel the
+ * currModel of the last update that had an `avg` (:511). None of the norms depends on a
+ * decision of the same update, so one pass over the picks (k_pool_fold_kf, the filter form
+ * of the ledger's fold) gives every pick's two norms beside everything fleet_kledger_update
+ * gives, the host decides (percentile, counters: scalars), and fleet_kfilter_resolve folds
+ * what was accepted.
+ *
+ * A filter belongs to one ledger (same pool, context, mutex and device; destroy it before
+ * fleet_kledger_destroy). It owns lastGrad as two fp32 rows in upload coordinates -- one
+ * read by the update, one that receives the avg of its result as lastGrad.subtract decodes
+ * it, Q(f32(f64(sum) / accepted)) per flat slot (decodeFloat(merged) is that value decoded
+ * and encoded once more, and differs from it where Q is not idempotent); they swap when a
+ * resolve ends with an average --, one row of merged bytes and one of their fp32, two model rows of n =
+ * n_biases * graph_edges + n_weights floats (current and last, fleet_mledger's row format),
+ * and four sums per pick where the ledger has two. FLEET_ERR_ARG from create: NULLs,
+ * graph_edges < 0, n = 0 or n >= 2^31 - 4096. */
+typedef struct fleet_kfilter fleet_kfilter;
+int fleet_kfilter_create(fleet_kledger* ledger, size_t n_weights, size_t n_biases, int graph_edges,
+                         fleet_kfilter** out);
+void fleet_kfilter_destroy(fleet_kfilter* filter);
+/* lastGrad != null (Kardam.java:157): 1 / 0; FLEET_ERR_ARG for NULL. */
+int fleet_kfilter_has_last(const fleet_kfilter* filter);
+/* currModel = getModelParametersNative(modelsSize()-1) (CppNNUpdater.java:417) from the
+ * vectors fleet_mledger_stage(_device) takes: the row a[i] = Q(param(i)), *norm_model =
+ * getNorm(currModel) (Kardam.java:158) and, when a last model exists, *norm_model_diff =
+ * getNorm(currModel.subtract(lastModel)) (:161), else NaN. Synchronous (the norms are host
+ * outputs). The staged row becomes lastModel when the next resolve ends with an average
+ * (:511); staging again before that replaces it. */
+int fleet_kfilter_set_model(fleet_kfilter* filter, const float* weights, const float* biases, double* norm_model,
+                            double* norm_model_diff);
+int fleet_kfilter_set_model_device(fleet_kfilter* filter, const float* d_weights, const float* d_biases,
+                                   double* norm_model, double* norm_model_diff, void* stream);
+/* fleet_kledger_update(_device) plus, for every pick k (worker[k] < 0 included: the filter's
+ * norm does not depend on the Kardam gate), norm_p[k] = getNorm(pickedGrad) (Kardam.java:158)
+ * and norm_pdiff[k] = getNorm(pickedGrad.subtract(lastGrad)) (:160; E = Q(p - L) per flat
+ * slot), NaN while there is no lastGrad. merged, merged_f32, norm_g, norm_diff, set, the slot
+ * status, the ledger's rows and tables and every error with its transactional guarantee are
+ * fleet_kledger_update's, bit for bit; on an error the filter's lastGrad and models are as
+ * before too. The pass is optimistic: the outputs are the result with every pick accepted.
+ * After FLEET_OK the update is pending until fleet_kfilter_resolve; until then the caller
+ * must not fleet_pool_put(_device) into or fleet_pool_drop a picked slot. A new
+ * fleet_kfilter_update discards a pending one (so does a failed one). Not for graph capture. */
+int fleet_kfilter_update(fleet_kfilter* filter, const int32_t* picks, int K, const double* dampen,
+                         const int32_t* worker, const int32_t* epoch, double lr, char* merged, size_t cap,
+                         size_t* out_len, float* merged_f32, double* norm_g, double* norm_diff, uint8_t* set,
+                         double* norm_p, double* norm_pdiff);
+int fleet_kfilter_update_device(fleet_kfilter* filter, const int32_t* picks, int K, const double* dampen,
+                                const int32_t* worker, const int32_t* epoch, double lr, void* d_merged,
+                                void* d_merged_f32, double* norm_g, double* norm_diff, uint8_t* set, double* norm_p,
+                                double* norm_pdiff, void* stream);
+/* The pending update's result for the decisions accept[k] != 0 of its K picks
+ * (CppNNUpdater.java:488-508):
+ *   all accepted: the optimistic result, no fold is launched;
+ *   a proper subset: avg over the accepted picks in pick order (the pool's fold without its
+ *     finish, then the finish with inv = 1 / accepted) merged into the LAST of the K picks'
+ *     upload, accepted or not (:508, pickedG), which overwrites the outputs;
+ *   none: no average (:506), *out_len = 0, no output written.
+ * With an average *out_len is the upload's length, lastGrad becomes this result's avg
+ * (:510) and the model staged since the last resolve becomes lastModel (:511);
+ * without one both stay. The update is then no longer pending. FLEET_ERR_ARG with
+ * everything untouched (the update stays pending): a NULL filter, accept, merged or
+ * out_len, no pending update, K other than the pending update's, a picked slot that is no
+ * longer occupied. FLEET_ERR_CAPACITY as fleet_pool_update. Synchronous; not for graph
+ * capture. The device form uses fleet_pool_update_device's addressing. */
+int fleet_kfilter_resolve(fleet_kfilter* filter, const uint8_t* accept, int K, char* merged, size_t cap,
+                          size_t* out_len, float* merged_f32);
+int fleet_kfilter_resolve_device(fleet_kfilter* filter, const uint8_t* accept, int K, void* d_merged,
+                                 void* d_merged_f32, size_t* out_len, void* stream);
+
 /* Kardam model ledger: Kardam's `models` map kept in HBM -----------------------
  * kardam.setModel(pickedId, pickedModel) (CppNNUpdater.java:472-476) with pickedModel =
  * T_v = getModelParametersNative(v) (cppNN_backend.cpp:227-242: Base64::encode of
