@@ -128,6 +128,12 @@ def lib() -> C.CDLL:
         "fleet_pool_update": (i32, [vp, vp, i32, vp, vp, sz, szp, vp]),
         "fleet_pool_update_device": (i32, [vp, vp, i32, vp, vp, vp, vp]),
         "fleet_pool_slot_status": (i32, [vp, i32]),
+        "fleet_gate_header_codes": (i32, [vp, i32, vp]),
+        "fleet_gate_create": (i32, [vp, vp, i32, C.POINTER(vp)]),
+        "fleet_gate_destroy": (None, [vp]),
+        "fleet_gate_vet": (i32, [vp, vp, i32, vp, vp, vp]),
+        "fleet_gate_vet_device": (i32, [vp, vp, i32, vp, vp, vp, vp]),
+        "fleet_gate_put": (i32, [vp, i32, vp, sz, vp, vp, vp]),
         "fleet_kledger_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
         "fleet_kledger_destroy": (None, [vp]),
         "fleet_kledger_workers": (i32, [vp]),
@@ -1181,6 +1187,124 @@ class Pool:
         """A Kardam ledger (fleet_kledger) over this pool: ``workers`` worker ids, at most
         ``max_store`` (default: the pool's slots) picks of one update that store a row."""
         return Ledger(self, workers, self.slots if max_store is None else max_store)
+
+    def gate(self, header_values=None) -> "Gate":
+        """An arrival gate (fleet_gate) beside this pool. ``header_values``: the value every
+        header slot of a good upload decodes to, in position order (``Layout.header_values()``);
+        None: the header slots are not checked."""
+        return Gate(self, header_values)
+
+
+def header_codes(values) -> np.ndarray:
+    """``float2int`` of each value (fleet_gate_header_codes; Base64.cpp:60-73): the codes a
+    client's ``Base64::encode(cnn.gradients())`` puts in the header slots when ``values`` are
+    the layout's block counts and sizes (``Layout.header_values()``). Runs on the host."""
+    v = np.ascontiguousarray(values, dtype=np.float32)
+    out = np.zeros(len(v), np.int32)
+    rc = lib().fleet_gate_header_codes(v.ctypes.data, len(v), out.ctypes.data)
+    if rc != FLEET_OK:
+        raise FleetError(rc, "fleet_gate_header_codes")
+    return out
+
+
+class Vet:
+    """One slot's verdict from a :class:`Gate`: ``status`` (0 good, 1 not Base64::encode
+    output, 2 a header slot's code is not the model's), ``sumsq`` (the squared norm of the
+    flat gradient over the pool's window) and ``max_abs`` (its largest magnitude there)."""
+
+    __slots__ = ("status", "sumsq", "max_abs")
+
+    def __init__(self, status: int, sumsq: float, max_abs: float):
+        self.status, self.sumsq, self.max_abs = int(status), float(sumsq), float(max_abs)
+
+    @property
+    def norm(self) -> float:
+        """``new ByteVec(getFlatGradient(g)).getNorm()`` when the pool holds the whole upload."""
+        return float(np.sqrt(self.sumsq))
+
+    def __iter__(self):
+        return iter((self.status, self.sumsq, self.max_abs))
+
+    def __eq__(self, other):
+        return isinstance(other, Vet) and tuple(self) == tuple(other)
+
+    def __repr__(self):
+        return f"Vet(status={self.status}, sumsq={self.sumsq!r}, max_abs={self.max_abs!r})"
+
+
+class Gate:
+    """An upload vetted when it arrives, beside an upload pool (fleet_gate,
+    include/fleet_codec.h): one device pass over resident slots that folds nothing and gives
+    per slot the Base64 verdict an update would reach, the header codes against the model's,
+    and the flat gradient's squared norm and largest magnitude (``new
+    ByteVec(getFlatGradient(g)).getNorm()``, cppNN_backend.cpp:701-720, 779-795). ``put`` is
+    the pool's ``put`` into a free slot that keeps the upload only when it is good. The gate
+    never writes the pool's ``slot_status``. Close it before its pool."""
+
+    def __init__(self, pool: Pool, header_values=None):
+        self.pool = pool
+        self._L = pool._L
+        self._h = None
+        self.codes = None if header_values is None else header_codes(header_values)
+        h = C.c_void_p()
+        pool.codec._check(self._L.fleet_gate_create(
+            pool._h, None if self.codes is None else self.codes.ctypes.data, 0 if self.codes is None else len(self.codes),
+            C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.pool, "_h", None) and getattr(self.pool.codec, "_h", None):
+            self._L.fleet_gate_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _live(self):
+        """The handle, while the gate and its pool are open."""
+        if not getattr(self, "_h", None) or not getattr(self.pool, "_h", None):
+            raise ValueError("the gate or its pool is closed")
+        return self._h
+
+    def vet(self, slots):
+        """A list of :class:`Vet`, one per slot of ``slots`` (occupied, distinct), in that order."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        K = len(sl)
+        st, ss, mx = np.zeros(K, np.int32), np.zeros(K, np.float64), np.zeros(K, np.float32)
+        self.pool.codec._check(self._L.fleet_gate_vet(self._live(), sl.ctypes.data, K, st.ctypes.data, ss.ctypes.data,
+                                                      mx.ctypes.data))
+        return [Vet(a, b, c) for a, b, c in zip(st, ss, mx)]
+
+    def vet_device(self, slots, status_i32, sumsq_f64, max_abs_f32, stream=None) -> None:
+        """The device form: int32, float64 and float32 CUDA tensors of at least ``len(slots)``
+        entries receive the results on ``stream``; nothing is synchronised."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        for t, dt in ((status_i32, "int32"), (sumsq_f64, "float64"), (max_abs_f32, "float32")):
+            if str(t.dtype) != "torch." + dt or not t.is_cuda or not t.is_contiguous() or t.numel() < len(sl):
+                raise ValueError(f"a contiguous {dt} CUDA tensor of at least {len(sl)} entries per output")
+        self.pool.codec._check(self._L.fleet_gate_vet_device(self._live(), sl.ctypes.data, len(sl), status_i32.data_ptr(),
+                                                             sumsq_f64.data_ptr(), max_abs_f32.data_ptr(),
+                                                             _stream(stream)))
+
+    def put(self, slot: int, upload) -> Vet:
+        """``Pool.put`` into the free slot ``slot`` (an occupied one raises), then its vet. The
+        upload stays in the slot only when the returned ``status`` is 0; a refused upload
+        leaves the slot free and the pool as it was."""
+        s = _as_bytes(upload)
+        st, ss, mx = C.c_int32(0), C.c_double(0.0), C.c_float(0.0)
+        rc = self._L.fleet_gate_put(self._live(), int(slot), s, len(s), C.byref(st), C.byref(ss), C.byref(mx))
+        if rc not in (FLEET_OK, FLEET_ERR_BASE64, FLEET_ERR_LAYOUT):
+            self.pool.codec._check(rc)
+        return Vet(st.value, ss.value, mx.value)
 
 
 class Ledger:

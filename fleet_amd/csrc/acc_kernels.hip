@@ -2,7 +2,8 @@
 // resident sum per launch (k_acc_push), the merged gradient from the sum (k_acc_finish),
 // a burst of uploads per launch (k_acc_push_many), the upload pool's fold over picked
 // resident rows (k_pool_fold), and that fold with Kardam's side outputs of the picks
-// (k_pool_fold_kd, k_pool_kd_reduce: the Kardam ledger).
+// (k_pool_fold_kd, k_pool_kd_reduce: the Kardam ledger), and the arrival gate's pass over
+// resident rows that folds nothing (k_pool_vet, k_pool_vet_reduce).
 //
 // CppNNUpdater.update is entered once per upload and only buffers it until M have
 // arrived (CppNNUpdater.java:383-391); the chain it then runs over the picked uploads
@@ -803,6 +804,169 @@ __global__ void __launch_bounds__(kAccNT) k_acc_avg_row(const float* __restrict_
   }
 }
 
+// The largest of v >= 0 over the wave, valid in lane 63: group_sum_f64<64>'s DPP lane moves
+// with a maximum for the add (a row the move leaves out reads 0, which no maximum of
+// magnitudes notices). Every lane of the wave active.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_move_f32(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false));
+}
+__device__ __forceinline__ float wave_max_f32(float v) {
+  v = fmaxf(v, dpp_move_f32<0x141, 0xf>(v));  // row_half_mirror
+  v = fmaxf(v, dpp_move_f32<0x4e, 0xf>(v));   // quad_perm [2,3,0,1]
+  v = fmaxf(v, dpp_move_f32<0xb1, 0xf>(v));   // quad_perm [1,0,3,2]
+  v = fmaxf(v, dpp_move_f32<0x140, 0xf>(v));  // row_mirror
+  v = fmaxf(v, dpp_move_f32<0x142, 0xa>(v));  // row_bcast15 into rows 1, 3
+  v = fmaxf(v, dpp_move_f32<0x143, 0x8>(v));  // row_bcast31 into row 3
+  return v;
+}
+
+// The arrival gate's pass over K <= kAccBurst resident rows of a pool (fleet_gate_vet*): per
+// slot what an update would find wrong with the upload, and what the reference can say of
+// it on arrival -- new ByteVec(getFlatGradient(g)).getNorm() (cppNN_backend.cpp:701-720,
+// 779-795) -- without folding anything. Per slot k and group, in k_pool_fold's order: the
+// lane's 16 bytes of the row, the Base64 check under acc_lane_step's `need` mask (so the
+// verdict is the fold's, character for character), with `expected` (n_hdr codes, indexed
+// by the header's index in the whole upload; nullptr: no header check) every header slot's
+// code against expected[h0 + i], the code of every slot with a kbit taken as 0, y =
+// Q(dec(code)) by the fold's first two stages, and over the flat slots of live lanes
+// ss += (double)(y * y) -- getNorm's fp32 product, widened -- and m = max(m, |y|).
+// The wave's ss and m of a slot are reduced over the wave (group_sum_f64<64>,
+// wave_max_f32) and folded into the wave's own LDS cells across the grid-stride
+// iterations; after them the wave stores {ss, m} once per slot, partials[(k * waves + w)
+// * 2 + {0, 1}], and k_pool_vet_reduce adds the waves in a fixed order. No floating-point
+// atomics, and nothing of slot k's path reads another slot's values or its position in
+// the launch: the same bits for a slot vetted alone or in any burst.
+// Errors per slot as k_pool_fold attributes them, ORed into status[k] -- the gate's own
+// words, one per slot of the launch, not the pool's per-slot status. The kernel reads the
+// rows and the header block and writes status[] and partials[] alone.
+__global__ void __launch_bounds__(kAccNT) k_pool_vet(const uint8_t* __restrict__ pool, size_t pitch, PoolPicks picks,
+                                                     int K, int64_t n_up, int64_t g_begin, int64_t g_end,
+                                                     const int32_t* __restrict__ hdr_block,
+                                                     const int32_t* __restrict__ expected, int* __restrict__ status,
+                                                     double* __restrict__ partials) {
+  __shared__ AccShared sh;
+  __shared__ double vss[kAccNT / 64][kAccBurst];
+  __shared__ float vmx[kAccNT / 64][kAccBurst];
+  for (int i = threadIdx.x; i < (kAccNT / 64) * kAccBurst; i += kAccNT) {
+    (&vss[0][0])[i] = 0.0;
+    (&vmx[0][0])[i] = 0.0f;
+  }
+  const AccHdr H = acc_block_open(sh, hdr_block);  // (its barrier covers the zeroes)
+  const int64_t ng = g_end - g_begin;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool check = expected != nullptr;
+  uint64_t bad_picks = 0, layout_picks = 0;
+  for (int64_t base = (int64_t)blockIdx.x * kAccNT; base < ng; base += (int64_t)gridDim.x * kAccNT) {
+    const int64_t gl = base + threadIdx.x;
+    const bool live = gl < ng;
+    const int64_t gs = live ? gl : 0, g = g_begin + gs;
+    const uint32_t need = needed_chars_mask((int)min<int64_t>(3, max<int64_t>(0, n_up - 3 * g)));
+    int h0;
+    const uint32_t hbits = acc_header_bits(sh, H.hdr, H.n_hdr, 3 * g, &h0);
+    const uint32_t kbits = keep_bits<3>(hbits, true, 3 * g, H.walk_end);
+    const bool wave_keep = __ballot(kbits != 0) != 0;
+    const uint32_t flat = live ? ~kbits & 7u : 0u;
+    int32_t want[3] = {0, 0, 0};
+    if (wave_keep && check) {
+      int hi = h0;
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        if ((hbits >> i) & 1u) want[i] = expected[hi++];
+    }
+    for (int k = 0; k < K; ++k) {
+      const uint8_t* src = pool + (size_t)picks.slot[k] * pitch + 16 * gs;
+      uint4 w = uint4{0u, 0u, 0u, 0u};
+      if (live) w = *reinterpret_cast<const uint4*>(src);
+      int32_t codes[3];
+      uint32_t bad = 0, layout_bad = 0;
+      if (need == 0xffffu) bad = live ? b64_decode_group_full(w, &sh.tab, codes) : 0u;
+      else bad = live ? (b64_decode_group(w, &sh.tab, codes) & need) : 0u;
+      if (!live) codes[0] = codes[1] = codes[2] = 0;
+      if (wave_keep) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          if (((hbits >> i) & 1u) && check && live) layout_bad |= (uint32_t)(codes[i] != want[i]);
+          if ((kbits >> i) & 1u) codes[i] = 0;
+        }
+      }
+      bad_picks |= (uint64_t)(bad != 0) << k;
+      layout_picks |= (uint64_t)(layout_bad != 0) << k;
+      float y0[3], y[3];
+      dec_stage_d16<3>(y0, codes, &sh.dtab);
+      q_stage_d16x<3>(y, y0, &sh.dtab, sh.tab.var);
+      double ss = 0.0;
+      float m = 0.0f;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const float yf = ((flat >> i) & 1u) ? y[i] : 0.0f;
+        ss += (double)(yf * yf);
+        m = fmaxf(m, fabsf(yf));
+      }
+      const double s = group_sum_f64<64>(ss);
+      const float mm = wave_max_f32(m);
+      if (lane == 63) {
+        vss[wave][k] += s;
+        vmx[wave][k] = fmaxf(vmx[wave][k], mm);
+      }
+    }
+  }
+  if (bad_picks | layout_picks) {
+    for (int k = 0; k < K; ++k) {
+      const int e = (((bad_picks >> k) & 1) ? FLEET_ERRBIT_BASE64 : 0) | (((layout_picks >> k) & 1) ? FLEET_ERRBIT_LAYOUT : 0);
+      if (e) atomicOr(status + k, e);
+    }
+  }
+  __syncthreads();  // the wave's cells were written by its last lane
+  if (lane < K) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    const size_t w = (size_t)blockIdx.x * (kAccNT / 64) + wave, waves = (size_t)gridDim.x * (kAccNT / 64);
+    reinterpret_cast<d2*>(partials)[(size_t)lane * waves + w] = d2{vss[wave][lane], (double)vmx[wave][lane]};
+  }
+}
+
+// Slot k's results from the waves' partials of one k_pool_vet launch: a lane adds every
+// 256th wave's ss in turn and keeps the largest m, the wave folds by DPP lane moves, lane 0
+// adds the block's four waves in order. The slot's status word travels with them, so the
+// three outputs of a launch land in the caller's arrays (device or the gate's own) at k.
+// waves = 0 (an empty window, nothing launched before): 0, 0 and the cleared status.
+__global__ void __launch_bounds__(kAccNT) k_pool_vet_reduce(const double* __restrict__ partials, int64_t waves,
+                                                            const int* __restrict__ status,
+                                                            int32_t* __restrict__ out_status,
+                                                            double* __restrict__ out_sumsq,
+                                                            float* __restrict__ out_max) {
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  __shared__ double red[kAccNT / 64];
+  __shared__ float redm[kAccNT / 64];
+  const int k = blockIdx.x;
+  const d2* p = reinterpret_cast<const d2*>(partials) + (size_t)k * waves;
+  double v = 0.0;
+  float m = 0.0f;
+  for (int64_t w = threadIdx.x; w < waves; w += kAccNT) {
+    const d2 t = p[w];
+    v += t.x;
+    m = fmaxf(m, (float)t.y);
+  }
+  const double a = group_sum_f64<64>(v);  // valid in lane 63
+  const float b = wave_max_f32(m);
+  if ((threadIdx.x & 63) == 63) {
+    red[threadIdx.x / 64] = a;
+    redm[threadIdx.x / 64] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double sa = 0.0;
+    float sm = 0.0f;
+    for (int i = 0; i < kAccNT / 64; ++i) {
+      sa += red[i];
+      sm = fmaxf(sm, redm[i]);
+    }
+    out_status[k] = status[k];
+    out_sumsq[k] = sa;
+    out_max[k] = sm;
+  }
+}
+
 // Element-wise kernels: a grid of whole blocks per CU (8 x 256 lanes fill a CU's wave
 // slots), striding over the groups, so the tables are copied into LDS once per block.
 static unsigned acc_grid(int64_t groups) {
@@ -909,6 +1073,27 @@ hipError_t launch_pool_fold_kf(const uint8_t* pool, size_t pitch, const int32_t*
                             d_status, merged, merged_f32, r, m, kd.lr, kd.slab, kd.vpitch, kd.partials, lastg, avg_out);
   if (e != hipSuccess) return e;
   k_pool_kf_reduce<<<dim3((unsigned)K), dim3(kAccNT), 0, s>>>(kd.partials, (int64_t)grid * (kAccNT / 64), kd.sums);
+  return hipGetLastError();
+}
+
+int64_t pool_vet_partial_doubles(const AccWindow& w) { return pool_kd_partial_doubles(w); }
+
+hipError_t launch_pool_vet(const uint8_t* pool, size_t pitch, const int32_t* slots, int K, const AccWindow& w,
+                           const int32_t* d_expected, int* d_work_status, double* partials, int32_t* out_status,
+                           double* out_sumsq, float* out_max, hipStream_t s) {
+  if (K <= 0 || K > kAccBurst || !pool || !slots || !d_work_status || !partials || !out_status || !out_sumsq || !out_max)
+    return hipErrorInvalidValue;
+  PoolPicks p;
+  for (int k = 0; k < kAccBurst; ++k) p.slot[k] = k < K ? slots[k] : 0;
+  hipError_t e = hipMemsetAsync(d_work_status, 0, sizeof(int) * (size_t)K, s);
+  if (e != hipSuccess) return e;
+  const bool empty = w.g_end <= w.g_begin;
+  const unsigned grid = acc_grid(std::max<int64_t>(1, w.g_end - w.g_begin));
+  e = acc_launch(k_pool_vet, w, s, pool, pitch, p, K, w.n_up, w.g_begin, w.g_end, w.d_hdr_block, d_expected,
+                 d_work_status, partials);
+  if (e != hipSuccess) return e;
+  k_pool_vet_reduce<<<dim3((unsigned)K), dim3(kAccNT), 0, s>>>(partials, empty ? 0 : (int64_t)grid * (kAccNT / 64),
+                                                               d_work_status, out_status, out_sumsq, out_max);
   return hipGetLastError();
 }
 

@@ -2582,6 +2582,168 @@ int fleet_pool_update_device(fleet_pool* p, const int32_t* picks, int K, const d
   return pool_verdict(p, picks, K);
 }
 
+// ---------------------------------------------------------------- arrival gate
+
+// What can be said of an upload when it arrives, beside a pool (k_pool_vet): the fold's
+// Base64 verdict, the header codes against the model's, and the flat gradient's squared
+// norm and largest magnitude -- new ByteVec(getFlatGradient(g)).getNorm(),
+// cppNN_backend.cpp:701-720, 779-795. One launch's status words and per-wave partials
+// (kAccBurst slots), and the results of a host vet of up to the pool's slots in HBM and
+// pinned. The gate writes nothing of the pool's but, in fleet_gate_put, the row of a free slot.
+struct fleet_gate {
+  fleet_pool* p = nullptr;
+  int cap = 0;                    // result entries: max(the pool's slots, kAccBurst)
+  int32_t* d_expected = nullptr;  // the header codes an upload must carry (nullptr: not checked)
+  int* d_work = nullptr;          // one launch's status words
+  double* d_part = nullptr;       // one launch's per-wave partials
+  int32_t* d_status = nullptr;
+  double* d_sumsq = nullptr;
+  float* d_max = nullptr;
+  int32_t* h_status = nullptr;    // pinned
+  double* h_sumsq = nullptr;
+  float* h_max = nullptr;
+};
+
+namespace {
+
+static void release_gate(fleet_gate* g) {
+  for (void* d : {(void*)g->d_expected, (void*)g->d_work, (void*)g->d_part, (void*)g->d_status, (void*)g->d_sumsq, (void*)g->d_max})
+    if (d) (void)hipFree(d);
+  for (void* h : {(void*)g->h_status, (void*)g->h_sumsq, (void*)g->h_max})
+    if (h) (void)hipHostFree(h);
+  delete g;
+}
+
+// the launches of a vet of K checked slots on `s`, kAccBurst slots each, into device arrays of K
+static int gate_launch(fleet_gate* g, const int32_t* slots, int K, int32_t* d_status, double* d_sumsq, float* d_max,
+                       hipStream_t s) {
+  fleet_pool* p = g->p;
+  constexpr int B = fleet::kAccBurst;
+  for (int k0 = 0; k0 < K; k0 += B)
+    HIP_TRY(p->c, fleet::launch_pool_vet(p->d_rows, p->pitch, slots + k0, std::min(B, K - k0), p->w.launch(), g->d_expected,
+                                         g->d_work, g->d_part, d_status + k0, d_sumsq + k0, d_max + k0, s));
+  return FLEET_OK;
+}
+
+// gate_launch into the gate's own arrays on the context's stream, read back and waited for
+static int gate_vet_host(fleet_gate* g, const int32_t* slots, int K, int32_t* status, double* sumsq, float* max_abs) {
+  fleet_ctx* c = g->p->c;
+  const int rc = gate_launch(g, slots, K, g->d_status, g->d_sumsq, g->d_max, c->stream);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(g->h_status, g->d_status, sizeof(int32_t) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(g->h_sumsq, g->d_sumsq, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(g->h_max, g->d_max, sizeof(float) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  std::copy(g->h_status, g->h_status + K, status);
+  std::copy(g->h_sumsq, g->h_sumsq + K, sumsq);
+  std::copy(g->h_max, g->h_max + K, max_abs);
+  return FLEET_OK;
+}
+
+}  // namespace
+
+int fleet_gate_header_codes(const float* values, int n, int32_t* codes) {
+  if (n < 0 || (n && (!values || !codes))) return FLEET_ERR_ARG;
+  for (int i = 0; i < n; ++i) codes[i] = fleet::enc(values[i]);  // Base64::float2int (Base64.cpp:60-73)
+  return FLEET_OK;
+}
+
+int fleet_gate_create(fleet_pool* p, const int32_t* header_codes, int n_headers, fleet_gate** out) {
+  if (!p || !out) return FLEET_ERR_ARG;
+  *out = nullptr;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  if (header_codes && n_headers != p->w.n_hdr)
+    return fail(c, FLEET_ERR_ARG, "fleet_gate_create: %d header codes for the pool's %d headers", n_headers, p->w.n_hdr);
+  fleet_gate* g = new fleet_gate();
+  g->p = p;
+  g->cap = std::max(p->slots, fleet::kAccBurst);
+  const size_t n = (size_t)g->cap;
+  const size_t part_bytes = sizeof(double) * (size_t)fleet::pool_vet_partial_doubles(p->w.launch());
+  const size_t exp_bytes = sizeof(int32_t) * ((size_t)p->w.n_hdr + 16);
+  bool ok = hipMalloc((void**)&g->d_work, sizeof(int) * fleet::kAccBurst) == hipSuccess &&
+            hipMalloc((void**)&g->d_part, part_bytes) == hipSuccess &&
+            hipMalloc((void**)&g->d_status, sizeof(int32_t) * n) == hipSuccess &&
+            hipMalloc((void**)&g->d_sumsq, sizeof(double) * n) == hipSuccess &&
+            hipMalloc((void**)&g->d_max, sizeof(float) * n) == hipSuccess &&
+            hipHostMalloc((void**)&g->h_status, sizeof(int32_t) * n, hipHostMallocDefault) == hipSuccess &&
+            hipHostMalloc((void**)&g->h_sumsq, sizeof(double) * n, hipHostMallocDefault) == hipSuccess &&
+            hipHostMalloc((void**)&g->h_max, sizeof(float) * n, hipHostMallocDefault) == hipSuccess;
+  if (ok && header_codes)
+    ok = hipMalloc((void**)&g->d_expected, exp_bytes) == hipSuccess && hipMemset(g->d_expected, 0, exp_bytes) == hipSuccess &&
+         (!n_headers || hipMemcpy(g->d_expected, header_codes, sizeof(int32_t) * (size_t)n_headers, hipMemcpyHostToDevice) == hipSuccess);
+  if (!ok) {
+    (void)hipGetLastError();
+    release_gate(g);
+    return fail(c, FLEET_ERR_NOMEM, "fleet_gate_create: allocating the gate of a pool of %d slots failed", p->slots);
+  }
+  *out = g;
+  return FLEET_OK;
+}
+
+void fleet_gate_destroy(fleet_gate* g) {
+  if (!g) return;
+  fleet_ctx* c = g->p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard dg(c->device);
+  (void)settle(c, &g->p->fly, nullptr, true);  // a device vet in flight reads the gate's buffers
+  (void)hipStreamSynchronize(c->stream);
+  release_gate(g);
+}
+
+int fleet_gate_vet(fleet_gate* g, const int32_t* slots, int K, int32_t* status, double* sumsq, float* max_abs) {
+  if (!g || !slots || !status || !sumsq || !max_abs || K <= 0) return FLEET_ERR_ARG;
+  fleet_pool* p = g->p;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  int rc = pool_update_args(p, slots, K, "fleet_gate_vet");
+  if (rc) return rc;
+  if ((rc = settle(c, &p->fly, c->stream, true))) return rc;
+  return gate_vet_host(g, slots, K, status, sumsq, max_abs);
+}
+
+int fleet_gate_vet_device(fleet_gate* g, const int32_t* slots, int K, void* d_status, void* d_sumsq, void* d_max_abs,
+                          void* stream) {
+  if (!g || !slots || !d_status || !d_sumsq || !d_max_abs || K <= 0) return FLEET_ERR_ARG;
+  fleet_pool* p = g->p;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  int rc = pool_update_args(p, slots, K, "fleet_gate_vet_device");
+  if (rc) return rc;
+  hipStream_t s = pick(c, stream);
+  if ((rc = settle(c, &p->fly, s, false))) return rc;
+  if ((rc = gate_launch(g, slots, K, (int32_t*)d_status, (double*)d_sumsq, (float*)d_max_abs, s))) return rc;
+  p->fly.on(s);  // the launch's words and partials are in use until `s` has run it
+  return FLEET_OK;
+}
+
+int fleet_gate_put(fleet_gate* g, int slot, const char* upload, size_t len, int32_t* status, double* sumsq,
+                   float* max_abs) {
+  if (!g || !upload || !status || !sumsq || !max_abs) return FLEET_ERR_ARG;
+  fleet_pool* p = g->p;
+  fleet_ctx* c = p->c;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  int rc = pool_slot_arg(p, slot, "fleet_gate_put");
+  if (rc) return rc;
+  if (p->occupied[slot]) return fail(c, FLEET_ERR_ARG, "fleet_gate_put: slot %d holds an upload", slot);
+  if ((rc = window_len_arg(c, p->w, len, "the pool's"))) return rc;
+  if ((rc = settle(c, &p->fly, c->stream, true))) return rc;
+  if ((rc = window_copy_in(c, p->w, upload, p->h_row, p->d_rows + (size_t)slot * p->pitch, c->stream))) return rc;
+  const int32_t one = slot;
+  if ((rc = gate_vet_host(g, &one, 1, status, sumsq, max_abs))) return rc;
+  // a refused upload's slot stays free: its bytes are what a dropped slot's are, gone with the next put
+  if (*status & FLEET_ERRBIT_BASE64)
+    return fail(c, FLEET_ERR_BASE64, "slot %d: input is not Base64::encode output (alphabet/padding)", slot);
+  if (*status & FLEET_ERRBIT_LAYOUT)
+    return fail(c, FLEET_ERR_LAYOUT, "slot %d: upload's layout header slots differ from the model's", slot);
+  p->occupied[slot] = 1;
+  return FLEET_OK;
+}
+
 // --------------------------------------------------------------- Kardam ledger
 
 // Kardam.java's `grads` map (worker -> (g, epoch), Kardam.java:40, 56-71) with every g

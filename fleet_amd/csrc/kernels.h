@@ -141,6 +141,19 @@ hipError_t launch_pool_fold_kf(const uint8_t* pool, size_t pitch, const int32_t*
                                uint8_t* merged, float* merged_f32, const PoolKd& kd, const float* lastg,
                                float* avg_out, hipStream_t s);
 hipError_t launch_acc_avg_row(const float* st, double inv, const AccWindow& w, float* avg_out, hipStream_t s);
+// The arrival gate's pass (k_pool_vet, then k_pool_vet_reduce on the same stream) over K <=
+// kAccBurst rows of a pool (slots: a host array of K), folding nothing: per slot k
+// out_status[k] = FLEET_ERRBIT_BASE64 where the row is not Base64::encode output (the
+// fold's verdict) | FLEET_ERRBIT_LAYOUT where a header slot's code differs from d_expected
+// (the window's n_headers codes by header index; nullptr: not checked), out_sumsq[k] = sum
+// (double)(y * y) and out_max[k] = max |y| over the window's flat slots, y = Q(dec(code)).
+// d_work_status (kAccBurst words) and partials (pool_vet_partial_doubles(w) doubles) are
+// the launch's own; the three outputs are device arrays of K. The pool's rows, state,
+// hfirst[] and status are not written.
+int64_t pool_vet_partial_doubles(const AccWindow& w);
+hipError_t launch_pool_vet(const uint8_t* pool, size_t pitch, const int32_t* slots, int K, const AccWindow& w,
+                           const int32_t* d_expected, int* d_work_status, double* partials, int32_t* out_status,
+                           double* out_sumsq, float* out_max, hipStream_t s);
 // The Kardam model ledger (mledger_kernels.hip). A model version is one fp32 row of
 // 4 * ceil(n / 4) floats, n = n_b * reps + n_w < kMlMaxValues values in getModelParams'
 // order, row[i] = Q(param(i)), the padding 0. A row or a pair runs on mrow_tiles(n) <=

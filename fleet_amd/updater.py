@@ -24,7 +24,8 @@ subtract) are on :class:`Codec`. Kardam's bookkeeping of the picked uploads (:47
 is opt-in in the picker mode (``kardam=``): its gradients live in a ledger beside the
 pool, and the pool's fold computes their norms as side outputs; with ``kardam_models=`` its
 models live in a model ledger too, and one pass over the picked versions' rows gives every
-pick's setModel result.
+pick's setModel result. With ``vet=True`` an arrival enters the pool through an arrival gate
+(``Pool.gate``), which refuses a malformed or wrong-model upload on the request that brought it.
 """
 from __future__ import annotations
 
@@ -254,7 +255,8 @@ class FleetUpdater:
     def __init__(self, codec, layout, M: int, lrates: Sequence[float], weights, fc_bias, policy: int = 0,
                  alpha: float = 0.0, stale_size: int = 0, num_labels: int = 10, has_outlier: bool = False,
                  streaming: bool = False, picker=None, pool_slots: Optional[int] = None, kardam=None,
-                 kardam_model=None, kardam_models=None, model=None, kardam_filter: bool = False):
+                 kardam_model=None, kardam_models=None, model=None, kardam_filter: bool = False, vet: bool = False,
+                 vet_max_norm: Optional[float] = None):
         if model is None and (weights is None or fc_bias is None):
             raise ValueError("weights and fc_bias are the model the updater steps: give them, or model= (a "
                              "fleet_amd.ResidentModel that holds them in HBM)")
@@ -272,6 +274,10 @@ class FleetUpdater:
                                       "picker")
         if picker is not None and streaming:
             raise ValueError("a picker chooses among buffered uploads; streaming folds them on arrival")
+        if (vet or vet_max_norm is not None) and picker is None:
+            raise ValueError("vet checks an upload on its way into the upload pool: it needs a picker")
+        if vet_max_norm is not None and not vet:
+            raise ValueError("vet_max_norm is a threshold on the norm the vet computes: it needs vet=True")
         self.codec = codec
         self.layout = layout
         self.M = M
@@ -337,6 +343,19 @@ class FleetUpdater:
         self.kardam_filter = bool(kardam_filter)
         self._filter = None
         self.last_accept: Optional[List[bool]] = None
+        # vet: an arrival goes into the pool through an arrival gate (``Pool.gate`` with the
+        # layout's header codes, ``Gate.put``) instead of ``Pool.put``. An upload that is not
+        # Base64::encode output, or whose header slots are not this model's, is refused on the
+        # request that brought it: it never joins `acc`, does not count toward M, and update
+        # returns None for it, as for the reference's hash mismatch (:350-353). With
+        # ``vet_max_norm`` an upload whose flat gradient's norm (new
+        # ByteVec(getFlatGradient(g)).getNorm()) exceeds it is refused too, its slot dropped.
+        # ``refused`` lists (client_id, status, norm) of every refused arrival. Without vet the
+        # updater makes the calls it made before.
+        self.vet = bool(vet)
+        self.vet_max_norm = None if vet_max_norm is None else float(vet_max_norm)
+        self._gate = None
+        self.refused: List[tuple] = []
 
     def _dampen_of(self, p: "Pending") -> float:
         """getDampen for one pick (:463-464) from the current epoch and label vector."""
@@ -395,7 +414,18 @@ class FleetUpdater:
         slot = pool.free_slot()
         if slot is None:  # before anything changes
             raise RuntimeError(f"the upload pool's {pool.slots} slots are all occupied")
-        pool.put(slot, p.upload)
+        if self.vet:
+            if self._gate is None:
+                self._gate = pool.gate(self.layout.header_values())
+            v = self._gate.put(slot, p.upload)
+            over = self.vet_max_norm is not None and not v.norm <= self.vet_max_norm
+            if v.status != 0 or over:
+                if v.status == 0:  # a good text that is kept out: the slot it took is freed
+                    pool.drop(slot)
+                self.refused.append((p.client_id, v.status, v.norm))
+                return None
+        else:
+            pool.put(slot, p.upload)
         p.slot, p.upload = slot, b""
         self.acc.append(p)
         if len(self.acc) < self.M:  # M-softsync (:388-391)

@@ -406,7 +406,7 @@ int fleet_pool_occupied(const fleet_pool* pool, int slot);
  * slot, in pieces whose copy to the device overlaps the next piece's host copy;
  * synchronous. A put into an occupied slot replaces the upload. FLEET_ERR_ARG: a NULL
  * argument, a slot outside [0, slots), a length other than `len`. The text is checked
- * when it is picked, not here. */
+ * when it is picked, not here (fleet_gate_put, below, checks it on arrival). */
 int fleet_pool_put(fleet_pool* pool, int slot, const char* upload, size_t len);
 /* The same for an upload already in HBM (d_upload: the whole row, of which only the
  * window's bytes are read): copied device-to-device on the caller's stream, no
@@ -437,6 +437,72 @@ int fleet_pool_update_device(fleet_pool* pool, const int32_t* picks, int K, cons
 /* The error bits the last update saw in the slot's upload: 1 = Base64, 2 = layout
  * header; 0 for a clean or unpicked slot. FLEET_ERR_ARG for NULL or a bad slot. */
 int fleet_pool_slot_status(const fleet_pool* pool, int slot);
+
+/* Arrival gate: an upload vetted when it arrives, beside an upload pool ----------
+ * fleet_pool_put does not look at the text, so a malformed upload waits in its slot until
+ * an update picks it, and that update pays its whole fold to fail. The reference does at
+ * arrival what it can -- a gradient for the wrong model is dropped there
+ * (CppNNUpdater.java:350-353) --, and fleet_acc_push checks an upload as it folds it. A
+ * fleet_gate is that check for a pool: one device pass over one or more resident slots
+ * (k_pool_vet) that folds nothing and says, per slot,
+ *   status   FLEET_ERRBIT_BASE64 (1): the text is not Base64::encode output -- the verdict
+ *            an update's fold would reach, character for character (a bad character in a
+ *            position a ragged last group does not need passes, as there);
+ *            FLEET_ERRBIT_LAYOUT (2): a header slot's code differs from the code this
+ *            model's gradients carry there (below); 0: the upload is good;
+ *   sumsq    sum (double)(y * y) over the flat gradient, y = Q(dec(code)): the square of
+ *            new ByteVec(getFlatGradient(g)).getNorm() (cppNN_backend.cpp:701-720, 779-795;
+ *            getNorm's fp32 products summed in double, per wave and then the waves in a
+ *            fixed order: no floating-point atomics, the same bits for the same upload
+ *            whatever else is vetted beside it);
+ *   max_abs  max |y| over the flat gradient.
+ * With a windowed pool the results cover the window's slots alone, which is why the sum of
+ * squares is returned and not its root: the windows of an upload add (and max_abs is the
+ * largest of theirs).
+ *
+ * A gate belongs to one pool (same context, mutex and device; destroy it before
+ * fleet_pool_destroy; errors through fleet_last_error(ctx)). It owns the expected header
+ * codes, one launch's status words (fleet_acc_burst()) and per-wave partials (grid x 4 waves
+ * x fleet_acc_burst() slots x 2 doubles), and status, sumsq and max_abs of max(slots,
+ * fleet_acc_burst()) slots in HBM and pinned: nothing is allocated after create. A failed
+ * allocation is FLEET_ERR_NOMEM and leaves nothing behind. The gate reads the pool's rows
+ * and writes none of the pool's rows, state, first-pick header codes or slot status:
+ * fleet_pool_slot_status keeps meaning "what the last update saw".
+ *
+ * Not built: JNI natives (the shim has no pool), a multi-GPU form, any change to
+ * fleet_pool_put itself, and overlapping the vet with the put's copy pieces. */
+typedef struct fleet_gate fleet_gate;
+/* float2int of each value (Base64.cpp:60-73), on the host: the codes a client's
+ * Base64::encode(cnn.gradients()) puts in the header slots (network.h:1038-1056: the block
+ * counts and sizes) when `values` are those counts and sizes. FLEET_ERR_ARG: n < 0, or a
+ * NULL array with n > 0. */
+int fleet_gate_header_codes(const float* values, int n, int32_t* codes);
+/* header_codes: one code per header position of the pool, in position order, or NULL: no
+ * header check, and FLEET_ERRBIT_LAYOUT is never set. FLEET_ERR_ARG: a NULL pool or out;
+ * codes given and n_headers other than the pool's header count. */
+int fleet_gate_create(fleet_pool* pool, const int32_t* header_codes, int n_headers, fleet_gate** out);
+void fleet_gate_destroy(fleet_gate* gate);
+/* Vets the uploads in slots[0..K): the launches (fleet_acc_burst() slots each, the slots in
+ * the kernel arguments) on the context's stream, one synchronisation, and status[k],
+ * sumsq[k], max_abs[k] for slot slots[k]. FLEET_OK whenever the pass ran: a bad upload is a
+ * result, not a failure of the call. FLEET_ERR_ARG, before anything is launched and with
+ * the outputs untouched: K <= 0, a NULL argument, a slot outside [0, slots), an unoccupied
+ * slot, a slot named twice. Waits for device puts in flight, as the pool's host forms do. */
+int fleet_gate_vet(fleet_gate* gate, const int32_t* slots, int K, int32_t* status, double* sumsq, float* max_abs);
+/* The same on the caller's stream into device arrays of K entries (int32, double, float),
+ * without synchronisation; `slots` is still a host array. The gate's launch buffers are in
+ * use until the stream has run the call: a later call of the pool or the gate on another
+ * stream waits for it, as for a device put. */
+int fleet_gate_vet_device(fleet_gate* gate, const int32_t* slots, int K, void* d_status, void* d_sumsq,
+                          void* d_max_abs, void* stream);
+/* One arrival, vetted on the request that brought it: fleet_pool_put's ingress into a FREE
+ * slot (an occupied slot is FLEET_ERR_ARG; the other argument checks are fleet_pool_put's),
+ * then the vet of that slot; synchronous. With a zero status the slot is occupied and the
+ * call returns FLEET_OK. Otherwise the slot stays free -- the pool is as it was -- and the
+ * call returns FLEET_ERR_BASE64 or FLEET_ERR_LAYOUT, BASE64 first, with the three outputs
+ * filled. */
+int fleet_gate_put(fleet_gate* gate, int slot, const char* upload, size_t len, int32_t* status, double* sumsq,
+                   float* max_abs);
 
 /* Kardam ledger: Kardam's `grads` map kept in HBM beside an upload pool --------
  * Kardam's bookkeeping runs in the staleSize > 0 branch alone (kardam.setModel /
