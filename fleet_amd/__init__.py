@@ -40,6 +40,10 @@ FLEET_ERR_CAPACITY = -6
 FLEET_MAX_HEADERS = 4096
 
 
+# new_solver's names (commonLib/cppNN/solver.h:198-208) in FLEET_SOLVER_* order
+SOLVERS = ("sgd", "adagrad", "rmsprop", "adam")
+
+
 class FleetError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"[{code}] {msg}")
@@ -185,6 +189,15 @@ def lib() -> C.CDLL:
         "fleet_selftest_digest": (i32, [vp, i32, C.POINTER(C.c_uint64)]),
         "fleet_descent_device": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, C.c_float, vp]),
         "fleet_descent": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp, i32, vp, vp, i32, C.c_float]),
+        "fleet_solver_from_name": (i32, [C.c_char_p]),
+        "fleet_descent_solver_device": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, C.c_float, vp]),
+        "fleet_descent_solver": (i32, [vp, i32, vp, sz, vp, vp, vp, sz, vp, sz, vp, vp, i32, vp, vp, i32, C.c_float]),
+        "fleet_model_set_solver": (i32, [vp, C.c_char_p]),
+        "fleet_model_solver": (i32, [vp]),
+        "fleet_model_solver_state": (i32, [vp, i32, vp, sz]),
+        "fleet_rmodel_set_solver": (i32, [vp, C.c_char_p]),
+        "fleet_rmodel_solver": (i32, [vp]),
+        "fleet_rmodel_solver_state": (i32, [vp, i32, vp, sz]),
         "fleet_model_params": (i32, [vp, vp, sz, vp, sz, i32, vp, sz, szp]),
         "fleet_model_version": (i32, [vp, vp, vp, i32, vp, sz, vp, vp]),
         "fleet_model_params_device": (i32, [vp, vp, sz, vp, sz, i32, vp, vp]),
@@ -915,6 +928,54 @@ class Codec:
                                                  grad_f32.data_ptr(), ws.ctypes.data, wp.ctypes.data, len(ws),
                                                  bs.ctypes.data, fc.ctypes.data, len(bs), float(lr),
                                                  _stream(stream)))
+
+
+    @staticmethod
+    def _solver_number(solver) -> int:
+        if isinstance(solver, str):
+            n = lib().fleet_solver_from_name(solver.encode())
+            if n < 0:
+                raise ValueError(f"no solver {solver!r}: one of {', '.join(SOLVERS)}")
+            return n
+        return int(solver)
+
+    def descent_solver(self, solver, weights, g1, g2, fc_bias, grad, layout, lr: float):
+        """:meth:`descent` under ``solver`` ("sgd", "adagrad", "rmsprop", "adam" or its
+        FLEET_SOLVER_* number; commonLib/cppNN/solver.h:97-195): returns the updated
+        (weights, g1, g2, fc_bias). ``g1`` / ``g2``: the solver's state, one float per weight
+        (``g2``: adam only, None otherwise and returned as None; both None for sgd)."""
+        sv = self._solver_number(solver)
+        w = np.array(weights, dtype=np.float32, copy=True).reshape(-1)
+        s1 = None if g1 is None else np.array(g1, dtype=np.float32, copy=True).reshape(-1)
+        s2 = None if g2 is None else np.array(g2, dtype=np.float32, copy=True).reshape(-1)
+        if any(s is not None and len(s) != len(w) for s in (s1, s2)):
+            raise ValueError("a state row holds one float per weight")
+        b = np.array(fc_bias, dtype=np.float32, copy=True).reshape(-1)
+        g = np.ascontiguousarray(grad, dtype=np.float32).reshape(-1)
+        ws, wp, bs, fc = self._layout_args(layout)
+        self._check(self._L.fleet_descent_solver(self._h, sv, w.ctypes.data, len(w),
+                                                 None if s1 is None else s1.ctypes.data,
+                                                 None if s2 is None else s2.ctypes.data, b.ctypes.data, len(b),
+                                                 g.ctypes.data, len(g), ws.ctypes.data, wp.ctypes.data, len(ws),
+                                                 bs.ctypes.data, fc.ctypes.data, len(bs), float(lr)))
+        return w, s1, s2, b
+
+    def descent_solver_device(self, solver, weights_f32, g1_f32, g2_f32, fc_bias_f32, grad_f32, layout, lr: float,
+                              stream=None):
+        """:meth:`descent_device` under ``solver``: weights and state rows (float32 CUDA
+        tensors of one size) updated in place."""
+        sv = self._solver_number(solver)
+        for t in (g1_f32, g2_f32):
+            if t is not None and t.numel() != weights_f32.numel():
+                raise ValueError("a state row holds one float per weight")
+        ws, wp, bs, fc = self._layout_args(layout)
+        self._check(self._L.fleet_descent_solver_device(self._h, sv, weights_f32.data_ptr(),
+                                                        g1_f32.data_ptr() if g1_f32 is not None else None,
+                                                        g2_f32.data_ptr() if g2_f32 is not None else None,
+                                                        fc_bias_f32.data_ptr() if fc_bias_f32 is not None else None,
+                                                        grad_f32.data_ptr(), ws.ctypes.data, wp.ctypes.data, len(ws),
+                                                        bs.ctypes.data, fc.ctypes.data, len(bs), float(lr),
+                                                        _stream(stream)))
 
 
 class Accumulator:
@@ -1746,14 +1807,33 @@ class Model:
     natives keep in libnative.so (cppNN_backend.cpp: cnn, models, lrates_vec,
     currEpoch, priority), with the natives' names as methods."""
 
-    def __init__(self, codec: "Codec", params_text, distillation_mode: int = 1):
-        """fetchParamsNative (cppNN_backend.cpp:282-301): network::read of a getParams text."""
+    def __init__(self, codec: "Codec", params_text, distillation_mode: int = 1, solver: str = "sgd"):
+        """fetchParamsNative (cppNN_backend.cpp:282-301): network::read of a getParams text.
+        ``solver``: what the server's ``mojo::network cnn(solver.c_str())`` (:40-42) is built
+        with, one of :data:`SOLVERS`; its state belongs to ``cnn`` alone and starts at zero."""
         t = _as_bytes(params_text)
         h = C.c_void_p()
         rc = codec._L.fleet_model_load(codec._h, t, len(t), int(distillation_mode), C.byref(h))
         if rc != FLEET_OK:
             raise FleetError(rc, "fleet_model_load failed (see stderr): not a supported getParams text")
         self._h, self._L, self.codec = h, codec._L, codec
+        if solver != "sgd":
+            self.set_solver(solver)
+
+    def set_solver(self, name: str) -> None:
+        """After the load and before the first descent (FleetError otherwise, and for a name
+        that is none of :data:`SOLVERS`): allocates the zeroed state."""
+        self._check(self._L.fleet_model_set_solver(self._h, str(name).encode()))
+
+    @property
+    def solver(self) -> str:
+        return SOLVERS[self._L.fleet_model_solver(self._h)]
+
+    def solver_state(self, which: int) -> np.ndarray:
+        """State row ``which`` (0: g1, 1: adam's g2) of ``cnn``, one float per weight."""
+        out = np.empty(self.shape()[0], np.float32)
+        self._check(self._L.fleet_model_solver_state(self._h, int(which), out.ctypes.data, len(out)))
+        return out
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1847,10 +1927,12 @@ class ResidentModel:
 
     HBM: ``stats()['resident_bytes'] = 4 * roundup64(n_weights + n_biases) *
     (max_versions + 2)`` -- cnn and a ring of ``max_versions + 1`` version rows (descentNative
-    pushes before it pops) -- plus ``stats()['workspace_bytes']`` allocated once at load.
+    pushes before it pops) -- plus ``stats()['workspace_bytes']`` allocated once at load, plus
+    ``4 * n_weights`` per state row of a ``solver`` other than sgd (one; two for adam).
     ``stale_size`` of a step may not exceed ``max_versions``."""
 
-    def __init__(self, codec: "Codec", params_text, distillation_mode: int = 1, max_versions: int = 8):
+    def __init__(self, codec: "Codec", params_text, distillation_mode: int = 1, max_versions: int = 8,
+                 solver: str = "sgd"):
         t = _as_bytes(params_text)
         h = C.c_void_p()
         rc = codec._L.fleet_rmodel_load(codec._h, t, len(t), int(distillation_mode), int(max_versions), C.byref(h))
@@ -1858,6 +1940,22 @@ class ResidentModel:
             raise FleetError(rc, "fleet_rmodel_load failed (see stderr): not a supported getParams text")
         self._h, self._L, self.codec = h, codec._L, codec
         self.max_versions = int(max_versions)
+        if solver != "sgd":
+            self.set_solver(solver)
+
+    def set_solver(self, name: str) -> None:
+        """:meth:`Model.set_solver`; the state rows (``n_weights`` floats each) live in HBM and
+        count in ``stats()['resident_bytes']``."""
+        self._check(self._L.fleet_rmodel_set_solver(self._h, str(name).encode()))
+
+    @property
+    def solver(self) -> str:
+        return SOLVERS[self._L.fleet_rmodel_solver(self._h)]
+
+    def solver_state(self, which: int) -> np.ndarray:
+        out = np.empty(self.shape()[0], np.float32)
+        self._check(self._L.fleet_rmodel_solver_state(self._h, int(which), out.ctypes.data, len(out)))
+        return out
 
     def close(self):
         if getattr(self, "_h", None):

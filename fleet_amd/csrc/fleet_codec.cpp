@@ -25,6 +25,8 @@
 
 #include "../../include/fleet_codec.h"
 #include "kernels.h"
+#include "solver_host.h"
+#include "solver_math.h"
 
 static_assert(FLEET_MAX_HEADERS == fleet::kMaxHeaderSlots, "the kernels size their LDS header lists by it");
 #include "model_codec.h"
@@ -1789,6 +1791,125 @@ int fleet_descent(fleet_ctx* c, float* weights, size_t n_weights, float* fc_bias
   }
   return FLEET_OK;
 }
+
+// The same step under the reference's other solvers (solver_kernels.hip, solver_math.h)
+
+int fleet_solver_from_name(const char* name) {
+  if (!name) return -1;
+  static const char* const names[] = {"sgd", "adagrad", "rmsprop", "adam"};  // new_solver (solver.h:198-208)
+  for (int i = 0; i < 4; ++i)
+    if (!std::strcmp(name, names[i])) return i;
+  return -1;
+}
+
+namespace {
+static int solver_args(fleet_ctx* c, int solver, const void* g1, const void* g2, size_t nw) {
+  if (solver < FLEET_SOLVER_SGD || solver > FLEET_SOLVER_ADAM) return fail(c, FLEET_ERR_ARG, "no solver %d", solver);
+  if (nw && ((solver != FLEET_SOLVER_SGD && !g1) || (solver == FLEET_SOLVER_ADAM && !g2)))
+    return fail(c, FLEET_ERR_ARG, "descent: solver %d needs its state row%s", solver,
+                solver == FLEET_SOLVER_ADAM ? "s g1 and g2" : " g1");
+  return FLEET_OK;
+}
+}  // namespace
+
+int fleet_descent_solver_device(fleet_ctx* c, int solver, float* d_weights, float* d_g1, float* d_g2,
+                                float* d_fc_bias, const float* d_grad, const int32_t* w_sizes,
+                                const uint8_t* w_present, int n_w, const int32_t* b_sizes, const uint8_t* fc_layer,
+                                int n_b, float lr, void* stream) {
+  if (!c || !d_grad) return FLEET_ERR_ARG;
+  if (solver == FLEET_SOLVER_SGD)
+    return fleet_descent_device(c, d_weights, d_fc_bias, d_grad, w_sizes, w_present, n_w, b_sizes, fc_layer, n_b, lr,
+                                stream);
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  size_t n_up = 0, nw = 0, nf = 0;
+  std::vector<fleet::DescentSegs> segs;
+  int rc = descent_segments(c, w_sizes, w_present, n_w, b_sizes, fc_layer, n_b, &n_up, &nw, &nf, &segs);
+  if (rc) return rc;
+  if ((nw && !d_weights) || (nf && !d_fc_bias)) return FLEET_ERR_ARG;
+  if ((rc = solver_args(c, solver, d_g1, d_g2, nw))) return rc;
+  float b1_t, b2_t;  // a fresh solver's
+  fleet::adam_bias_terms(0, &b1_t, &b2_t);
+  for (const auto& sg : segs)
+    HIP_TRY(c, fleet::launch_descent_solver(solver, d_weights, d_g1, d_g2, d_fc_bias, d_grad, sg, lr, b1_t, b2_t,
+                                            pick(c, stream)));
+  return FLEET_OK;
+}
+
+int fleet_descent_solver(fleet_ctx* c, int solver, float* weights, size_t n_weights, float* g1, float* g2,
+                         float* fc_bias, size_t n_fc_bias, const float* grad, size_t n_grad, const int32_t* w_sizes,
+                         const uint8_t* w_present, int n_w, const int32_t* b_sizes, const uint8_t* fc_layer, int n_b,
+                         float lr) {
+  return fleet::descent_solver_host(c, solver, 0, weights, n_weights, g1, g2, fc_bias, n_fc_bias, grad, n_grad, w_sizes,
+                                    w_present, n_w, b_sizes, fc_layer, n_b, lr);
+}
+
+}  // extern "C"
+
+// fleet_descent_solver with adam's b1_t, b2_t after `adam_resets` resets (solver_host.h)
+int fleet::descent_solver_host(fleet_ctx* c, int solver, int adam_resets, float* weights, size_t n_weights, float* g1,
+                               float* g2, float* fc_bias, size_t n_fc_bias, const float* grad, size_t n_grad,
+                               const int32_t* w_sizes, const uint8_t* w_present, int n_w, const int32_t* b_sizes,
+                               const uint8_t* fc_layer, int n_b, float lr) {
+  if (!c || !grad) return FLEET_ERR_ARG;
+  if (solver == FLEET_SOLVER_SGD)
+    return fleet_descent(c, weights, n_weights, fc_bias, n_fc_bias, grad, n_grad, w_sizes, w_present, n_w, b_sizes,
+                         fc_layer, n_b, lr);
+  size_t n_up = 0, nw = 0, nf = 0;
+  std::vector<fleet::DescentSegs> segs;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    rc = descent_segments(c, w_sizes, w_present, n_w, b_sizes, fc_layer, n_b, &n_up, &nw, &nf, &segs);
+  }
+  if (rc) return rc;
+  if (n_grad != n_up || n_weights != nw || n_fc_bias != nf || (nw && !weights) || (nf && !fc_bias))
+    return fail(c, FLEET_ERR_ARG, "descent: sizes do not match the layout (grad %zu/%zu, weights %zu/%zu, bias %zu/%zu)",
+                n_grad, n_up, n_weights, nw, n_fc_bias, nf);
+  if ((rc = solver_args(c, solver, g1, g2, nw))) return rc;
+  size_t idx = 0;  // fleet_descent's header check
+  bool ok = grad[idx++] == (float)n_w;
+  for (int i = 0; i < n_w && ok; ++i) {
+    ok = grad[idx++] == (float)w_sizes[i];
+    idx += (size_t)w_sizes[i];
+  }
+  ok = ok && grad[idx++] == (float)n_b;
+  for (int k = 0; k < n_b && ok; ++k) {
+    ok = grad[idx++] == (float)b_sizes[k];
+    idx += (size_t)b_sizes[k];
+  }
+  if (!ok) return fail(c, FLEET_ERR_LAYOUT, "descent: gradient header does not match the model layout");
+  const bool two = solver == FLEET_SOLVER_ADAM;
+  float b1_t, b2_t;
+  fleet::adam_bias_terms(adam_resets, &b1_t, &b2_t);
+  DevMem dw, d1, d2, db, dg;
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    DEVICE_SCOPE(c);
+    const size_t wb = nw * sizeof(float);
+    if (nw) HIP_TRY(c, hipMalloc(&dw.p, wb));
+    if (nw) HIP_TRY(c, hipMalloc(&d1.p, wb));
+    if (nw && two) HIP_TRY(c, hipMalloc(&d2.p, wb));
+    if (nf) HIP_TRY(c, hipMalloc(&db.p, nf * sizeof(float)));
+    HIP_TRY(c, hipMalloc(&dg.p, n_grad * sizeof(float)));
+    if (nw) HIP_TRY(c, hipMemcpyAsync(dw.p, weights, wb, hipMemcpyHostToDevice, c->stream));
+    if (nw) HIP_TRY(c, hipMemcpyAsync(d1.p, g1, wb, hipMemcpyHostToDevice, c->stream));
+    if (nw && two) HIP_TRY(c, hipMemcpyAsync(d2.p, g2, wb, hipMemcpyHostToDevice, c->stream));
+    if (nf) HIP_TRY(c, hipMemcpyAsync(db.p, fc_bias, nf * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dg.p, grad, n_grad * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    for (const auto& sg : segs)
+      HIP_TRY(c, fleet::launch_descent_solver(solver, (float*)dw.p, (float*)d1.p, (float*)d2.p, (float*)db.p,
+                                              (const float*)dg.p, sg, lr, b1_t, b2_t, c->stream));
+    if (nw) HIP_TRY(c, hipMemcpyAsync(weights, dw.p, wb, hipMemcpyDeviceToHost, c->stream));
+    if (nw) HIP_TRY(c, hipMemcpyAsync(g1, d1.p, wb, hipMemcpyDeviceToHost, c->stream));
+    if (nw && two) HIP_TRY(c, hipMemcpyAsync(g2, d2.p, wb, hipMemcpyDeviceToHost, c->stream));
+    if (nf) HIP_TRY(c, hipMemcpyAsync(fc_bias, db.p, nf * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return FLEET_OK;
+}
+
+extern "C" {
 
 // descentNative's model copy in DISTILLATION_MODE=1 (cppNN_backend.cpp:355-372):
 // cnnNew->read(cnn.getParams()) of the unquantised model. getParams prints the
@@ -3633,13 +3754,13 @@ const char* fleet_plan(void) {
 
 int fleet_selftest_digest(fleet_ctx* c, int fn, uint64_t* out) {
   if (!c || !out) return FLEET_ERR_ARG;
-  if (fn < 0 || fn > 24) return fail(c, FLEET_ERR_ARG, "no self-test function %d", fn);
+  if (fn < 0 || fn > 30) return fail(c, FLEET_ERR_ARG, "no self-test function %d", fn);
   std::lock_guard<std::mutex> lk(c->mu);
   DEVICE_SCOPE(c);
   unsigned long long* d = nullptr;
   HIP_TRY(c, hipMalloc((void**)&d, sizeof(unsigned long long)));
   HIP_TRY(c, hipMemsetAsync(d, 0, sizeof(unsigned long long), c->stream));
-  HIP_TRY(c, fleet::launch_digest(fn, d, c->stream));
+  HIP_TRY(c, fn >= 25 ? fleet::launch_digest_solver(fn, d, c->stream) : fleet::launch_digest(fn, d, c->stream));
   unsigned long long h = 0;
   HIP_TRY(c, hipMemcpyAsync(&h, d, sizeof h, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));

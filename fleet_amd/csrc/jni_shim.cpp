@@ -45,6 +45,8 @@
 //
 // Environment: FLEET_GPUS = devices the batched natives spread one update over
 // (element sharding, fleet_update_multi; default 1, "all" = every visible GPU);
+// FLEET_SOLVER = the reference's `solver` global (sgd, adagrad, rmsprop, adam; default sgd),
+// read at fetchParamsNative;
 // FLEET_DISTILLATION_MODE = the reference's compile-time DISTILLATION_MODE (default 1);
 // FLEET_SAMPLER_IID / FLEET_SAMPLER_OUTLIER / FLEET_SAMPLER_CLIENTS = the
 // reference's source-edited sampler globals iid / outlier / numClients
@@ -613,6 +615,16 @@ JNIEXPORT void JNICALL Java_apps_cppNN_CppNNUpdater_fetchParamsNative(JNIEnv* en
   if (rc != FLEET_OK) {
     fail(c, "fetchParamsNative", rc);
     return;
+  }
+  // the reference's `solver` global (:40-42), edited in its source like DISTILLATION_MODE
+  const char* sv = std::getenv("FLEET_SOLVER");
+  if (sv && *sv) {
+    const int rc2 = fleet_model_set_solver(m, sv);
+    if (rc2 != FLEET_OK) {
+      std::fprintf(stderr, "[fleet] fetchParamsNative failed (%d): FLEET_SOLVER: %s\n", rc2, fleet_model_last_error(m));
+      fleet_model_destroy(m);
+      return;
+    }
   }
   std::lock_guard<std::mutex> lk(g_model_mu);
   if (g_model) fleet_model_destroy(g_model);

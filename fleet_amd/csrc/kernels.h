@@ -30,6 +30,13 @@ struct DescentSegs {
 };
 hipError_t launch_descent(float* weights, float* fc_bias, const float* grad, const DescentSegs& segs, float lr,
                           hipStream_t s);
+// the same segments under FLEET_SOLVER_ADAGRAD / _RMSPROP / _ADAM (solver_kernels.hip,
+// k_descent_solver<S>): g1, g2 = state rows indexed like the weights (g2: adam only);
+// b1_t, b2_t = adam's bias-correction terms (solver_math.h adam_bias_terms)
+hipError_t launch_descent_solver(int solver, float* weights, float* g1, float* g2, float* fc_bias, const float* grad,
+                                 const DescentSegs& segs, float lr, float b1_t, float b2_t, hipStream_t s);
+// self-test digests fn 25..30 of the solvers' arithmetic (solver_kernels.hip)
+hipError_t launch_digest_solver(int fn, unsigned long long* out, hipStream_t s);
 hipError_t launch_update(const uint8_t* uploads, size_t pitch, int M, const double* d_dampen, double inv_avg,
                          int64_t n_up, int64_t g_begin, int64_t g_end, const int32_t* d_hdr_block,
                          uint8_t* merged, float* merged_f32, int* d_err, hipStream_t s);

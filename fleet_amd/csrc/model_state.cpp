@@ -35,6 +35,8 @@
 
 #include "../../include/fleet_codec.h"
 #include "model_state.h"
+#include "solver_host.h"
+#include "solver_math.h"
 
 using fleet::Layer;
 using fleet::Version;
@@ -311,9 +313,15 @@ int fleet_model_descent(fleet_model* m, const char* merged, size_t len, int clie
     if (L.use_bias && L.fc) fcb.insert(fcb.end(), m->cnn.b.begin() + (long)o, m->cnn.b.begin() + (long)(o + L.bias_size));
     o += L.use_bias ? L.bias_size : 0;
   }
-  rc = fleet_descent(m->ctx, m->cnn.w.data(), m->cnn.w.size(), fcb.data(), fcb.size(), g.data(), n, w_sizes.data(),
-                     w_present.data(), nw, b_sizes.data(), m->fc.data(), nb, m->lr);
+  if (m->solver == FLEET_SOLVER_SGD)
+    rc = fleet_descent(m->ctx, m->cnn.w.data(), m->cnn.w.size(), fcb.data(), fcb.size(), g.data(), n, w_sizes.data(),
+                       w_present.data(), nw, b_sizes.data(), m->fc.data(), nb, m->lr);
+  else
+    rc = fleet::descent_solver_host(m->ctx, m->solver, fleet::kServerResets, m->cnn.w.data(), m->cnn.w.size(), m->g1.data(), m->g2.data(),
+                                    fcb.data(), fcb.size(), g.data(), n, w_sizes.data(), w_present.data(), nw,
+                                    b_sizes.data(), m->fc.data(), nb, m->lr);
   if (rc) return mfail(m, rc, "descent: %s", fleet_last_error(m->ctx));
+  m->stepped = true;
   o = 0;
   size_t f = 0;
   for (const Layer& L : m->layers) {
@@ -329,6 +337,35 @@ int fleet_model_descent(fleet_model* m, const char* merged, size_t len, int clie
   m->models.push_back(std::move(v));
   m->pushed++;
   if (m->models.size() > (size_t)std::max(0, stale_size)) m->models.pop_front();
+  return FLEET_OK;
+}
+
+int fleet_model_set_solver(fleet_model* m, const char* name) {
+  if (!m) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  const int sv = fleet_solver_from_name(name);
+  if (sv < 0) return mfail(m, FLEET_ERR_ARG, "set_solver: no solver \"%s\" (sgd, adagrad, rmsprop, adam)", name ? name : "(null)");
+  if (m->stepped) return mfail(m, FLEET_ERR_ARG, "set_solver: the model has been stepped");
+  m->solver = sv;
+  m->g1.assign(sv != FLEET_SOLVER_SGD ? m->cnn.w.size() : 0, 0.0f);
+  m->g2.assign(sv == FLEET_SOLVER_ADAM ? m->cnn.w.size() : 0, 0.0f);
+  return FLEET_OK;
+}
+
+int fleet_model_solver(fleet_model* m) {
+  if (!m) return 0;
+  std::lock_guard<std::mutex> lk(m->mu);
+  return m->solver;
+}
+
+int fleet_model_solver_state(fleet_model* m, int which, float* out, size_t cap) {
+  if (!m) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (which < 0 || which > 1 || m->solver == FLEET_SOLVER_SGD || (which == 1 && m->solver != FLEET_SOLVER_ADAM))
+    return mfail(m, FLEET_ERR_ARG, "solver_state: solver %d keeps no state row %d", m->solver, which);
+  const std::vector<float>& g = which ? m->g2 : m->g1;
+  if (cap < g.size() || (g.size() && !out)) return mfail(m, FLEET_ERR_CAPACITY, "output capacity %zu < %zu", cap, g.size());
+  if (!g.empty()) std::memcpy(out, g.data(), sizeof(float) * g.size());
   return FLEET_OK;
 }
 

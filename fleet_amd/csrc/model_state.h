@@ -43,5 +43,8 @@ struct fleet_model {
   std::vector<double> lrates;        // `lrates_vec`
   float lr = 0.0f;                   // cnn's learning rate (set_learning_rate(double) -> float)
   int epoch = 0, priority = 0;
+  int solver = 0;                    // FLEET_SOLVER_*: what `cnn` was constructed with
+  bool stepped = false;              // a descent has run: the solver can no longer be set
+  std::vector<float> g1, g2;         // the solver's state (G1, G2), laid out like cnn.w
   std::string err;
 };

@@ -38,6 +38,11 @@ hipError_t launch_rm_check(const float* d_grad, int64_t n_values, const RmLayout
 // segment covers included.
 hipError_t launch_rm_step(float* cnn_w, float* cnn_b, const float* d_grad, const RmLayout& L, float lr, float* row_w,
                           float* row_b, const int* d_err, hipStream_t s);
+// The same step under FLEET_SOLVER_ADAGRAD / _RMSPROP / _ADAM (solver_math.h): g1, g2 = the
+// model's state rows of n_w floats (g2: adam only), advanced in place in the weight leg; b1_t, b2_t = adam's bias-correction terms.
+hipError_t launch_rm_step_solver(int solver, float* cnn_w, float* cnn_b, float* g1, float* g2, const float* d_grad,
+                                 const RmLayout& L, float lr, float b1_t, float b2_t, float* row_w, float* row_b,
+                                 const int* d_err, hipStream_t s);
 // out[i] = strtof(sprintf("%g", in[i])): finite values through g6_roundtrip, inf kept,
 // NaN to the default quiet NaN with its sign (what strtof gives for "nan" / "-nan")
 hipError_t launch_rm_roundtrip(const float* in, float* out, int64_t n, hipStream_t s);

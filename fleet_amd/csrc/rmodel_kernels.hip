@@ -4,11 +4,14 @@
 // here in k_rm_check before any weight is written; k_rm_step applies
 // descent_math.h's two update bodies and, in DISTILLATION_MODE=0, leaves the
 // model copy's `%g` / strtof round trip of every value in the new version's row.
+// k_rm_step_solver<S> is the same step under adagrad, rmsprop or adam (solver_math.h),
+// with the solver's state rows beside cnn.
 #include <hip/hip_runtime.h>
 
 #include "decimal6.h"
 #include "descent_math.h"
 #include "rmodel_kernels.h"
+#include "solver_math.h"
 
 namespace fleet {
 namespace {
@@ -134,6 +137,45 @@ __global__ void __launch_bounds__(256) k_rm_step(float* __restrict__ cnn_w, floa
   }
 }
 
+// k_rm_step under adagrad, rmsprop or adam (solver_math.h): the solver body and its state
+// rows (indexed like the weights, read and written in place) in the weight leg only; the
+// bias legs, the header check's word and the mode-0 version row are k_rm_step's.
+template <int S>
+__global__ void __launch_bounds__(256) k_rm_step_solver(float* __restrict__ cnn_w, float* __restrict__ cnn_b,
+                                                        float* __restrict__ g1, float* __restrict__ g2,
+                                                        const float* __restrict__ g, RmLayout L, float lr,
+                                                        float b1_t, float b2_t, float* __restrict__ row_w,
+                                                        float* __restrict__ row_b, const int* __restrict__ err) {
+  if (*err) return;
+  int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e < L.n_w) {
+    const int k = seg_of(L.w_start, L.counts[0], e);
+    const SolverStep y = solver_step<S>(cnn_w[e], g[L.w_grad[k] + (e - L.w_start[k])], g1[e],
+                                        S == kSolverAdam ? g2[e] : 0.0f, lr, b1_t, b2_t);
+    cnn_w[e] = y.w;
+    g1[e] = y.g1;
+    if (S == kSolverAdam) g2[e] = y.g2;
+    if (row_w) row_w[e] = rt_text(y.w);
+    return;
+  }
+  e -= L.n_w;
+  if (e < L.n_fc) {
+    const int k = seg_of(L.b_start, L.counts[1], e);
+    const int j = seg_of(L.fcl_start, L.n_fcl, e);
+    const int64_t q = L.fcl_boff[j] + (e - L.fcl_start[j]);
+    const float y = descent_bias(cnn_b[q], g[L.b_grad[k] + (e - L.b_start[k])], lr);
+    cnn_b[q] = y;
+    if (row_b) row_b[q] = rt_text(y);
+    return;
+  }
+  e -= L.n_fc;
+  if (e < L.n_b && row_b) {
+    for (int j = 0; j < L.n_fcl; ++j)  // an fc layer's bias: written above
+      if (e >= L.fcl_boff[j] && e < L.fcl_boff[j] + (L.fcl_start[j + 1] - L.fcl_start[j])) return;
+    row_b[e] = rt_text(cnn_b[e]);
+  }
+}
+
 __global__ void __launch_bounds__(256) k_rm_roundtrip(const float* __restrict__ in, float* __restrict__ out,
                                                       int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -153,6 +195,31 @@ hipError_t launch_rm_step(float* cnn_w, float* cnn_b, const float* d_grad, const
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_rm_step, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, cnn_w, cnn_b, d_grad, L, lr,
                      row_w, row_b, d_err);
+  return hipGetLastError();
+}
+
+hipError_t launch_rm_step_solver(int solver, float* cnn_w, float* cnn_b, float* g1, float* g2, const float* d_grad,
+                                 const RmLayout& L, float lr, float b1_t, float b2_t, float* row_w, float* row_b,
+                                 const int* d_err, hipStream_t s) {
+  const int64_t n = L.n_w + L.n_fc + L.n_b;
+  if (n == 0) return hipSuccess;
+  const dim3 grid((unsigned)((n + 255) / 256));
+  switch (solver) {
+    case kSolverAdagrad:
+      hipLaunchKernelGGL(k_rm_step_solver<kSolverAdagrad>, grid, dim3(256), 0, s, cnn_w, cnn_b, g1, g2, d_grad, L, lr,
+                         b1_t, b2_t, row_w, row_b, d_err);
+      break;
+    case kSolverRmsprop:
+      hipLaunchKernelGGL(k_rm_step_solver<kSolverRmsprop>, grid, dim3(256), 0, s, cnn_w, cnn_b, g1, g2, d_grad, L, lr,
+                         b1_t, b2_t, row_w, row_b, d_err);
+      break;
+    case kSolverAdam:
+      hipLaunchKernelGGL(k_rm_step_solver<kSolverAdam>, grid, dim3(256), 0, s, cnn_w, cnn_b, g1, g2, d_grad, L, lr,
+                         b1_t, b2_t, row_w, row_b, d_err);
+      break;
+    default:
+      return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 

@@ -33,6 +33,7 @@
 #include "model_codec.h"
 #include "model_state.h"
 #include "rmodel_kernels.h"
+#include "solver_math.h"
 
 struct fleet_rmodel {
   fleet_ctx* ctx = nullptr;
@@ -50,6 +51,9 @@ struct fleet_rmodel {
   uint8_t* a20 = nullptr;
   uint8_t* gtext = nullptr;  // a host gradient text, staged (grown on first use)
   float* grad = nullptr;
+  float* sstate = nullptr;  // the solver's state rows g1 | g2, nw floats each (fleet_rmodel_set_solver)
+  int solver = 0;
+  bool stepped = false;
   size_t gtext_cap = 0, grad_cap = 0;
   int* h_pin = nullptr;  // pinned: [0] the error word's copy, [4..] the counts line
   // carved from tab / work
@@ -189,7 +193,7 @@ void release(fleet_rmodel* m) {
     DeviceScope sc(m->device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
     for (void* p : {(void*)m->state, (void*)m->tab, (void*)m->work, (void*)m->text, (void*)m->a20, (void*)m->gtext,
-                    (void*)m->grad})
+                    (void*)m->grad, (void*)m->sstate})
       if (p) (void)hipFree(p);
     if (m->h_pin) (void)hipHostFree(m->h_pin);
     if (m->stream) (void)hipStreamDestroy(m->stream);
@@ -333,8 +337,16 @@ int step(fleet_rmodel* m, const float* d_grad, size_t n_values, int stale_size, 
   if (m->epoch < (int)m->lrates.size()) m->lr = (float)m->lrates[(size_t)m->epoch];
   const int row = m->free_rows.back();
   RM_HIP(m, fleet::launch_rm_check(d_grad, (int64_t)n_values, m->lay, m->d_err, s));
-  RM_HIP(m, fleet::launch_rm_step(row_w(m, 0), row_b(m, 0), d_grad, m->lay, m->lr, m->mode ? nullptr : row_w(m, row),
-                                  m->mode ? nullptr : row_b(m, row), m->d_err, s));
+  float b1_t, b2_t;  // adam's, as fetchParamsNative's start_epoch leaves them
+  fleet::adam_bias_terms(fleet::kServerResets, &b1_t, &b2_t);
+  if (m->solver == FLEET_SOLVER_SGD)
+    RM_HIP(m, fleet::launch_rm_step(row_w(m, 0), row_b(m, 0), d_grad, m->lay, m->lr, m->mode ? nullptr : row_w(m, row),
+                                    m->mode ? nullptr : row_b(m, row), m->d_err, s));
+  else
+    RM_HIP(m, fleet::launch_rm_step_solver(m->solver, row_w(m, 0), row_b(m, 0), m->sstate,
+                                           m->solver == FLEET_SOLVER_ADAM ? m->sstate + m->nw : nullptr, d_grad, m->lay,
+                                           m->lr, b1_t, b2_t, m->mode ? nullptr : row_w(m, row), m->mode ? nullptr : row_b(m, row),
+                                           m->d_err, s));
   int word = 0, rc;
   if ((rc = read_word(m, s, &word))) return rc;
   if (word == fleet::kRmErrSizes)
@@ -342,6 +354,7 @@ int step(fleet_rmodel* m, const float* d_grad, size_t n_values, int stale_size, 
                  n_values, m->nw, m->nfc);
   if (word) return rfail(m, FLEET_ERR_LAYOUT, "descent: the gradient header does not match the model layout");
   m->epoch++;
+  m->stepped = true;
   if (m->mode && (rc = make_version(m, row, s))) return rc;
   push_version(m, row, stale_size);
   return FLEET_OK;
@@ -448,6 +461,48 @@ int fleet_rmodel_descent_device(fleet_rmodel* m, const void* d_merged_f32, size_
   if (n_values < least || n_values > (size_t)INT64_MAX / 8)
     return rfail(m, FLEET_ERR_ARG, "descent: %zu values, a gradient of this model holds at least %zu", n_values, least);
   return step(m, (const float*)d_merged_f32, n_values, stale_size, caller_stream(stream));
+}
+
+int fleet_rmodel_set_solver(fleet_rmodel* m, const char* name) {
+  if (!m) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  RM_SCOPE(m);
+  const int sv = fleet_solver_from_name(name);
+  if (sv < 0) return rfail(m, FLEET_ERR_ARG, "set_solver: no solver \"%s\" (sgd, adagrad, rmsprop, adam)", name ? name : "(null)");
+  if (m->stepped) return rfail(m, FLEET_ERR_ARG, "set_solver: the model has been stepped");
+  const auto rows_of = [](int v) { return (size_t)(v == FLEET_SOLVER_SGD ? 0 : v == FLEET_SOLVER_ADAM ? 2 : 1); };
+  // (a second call before the first step starts over: state rows are small beside the versions)
+  if (m->sstate) (void)hipFree(m->sstate);
+  m->sstate = nullptr;
+  m->resident_bytes -= sizeof(float) * m->nw * rows_of(m->solver);
+  m->solver = FLEET_SOLVER_SGD;
+  const size_t bytes = sizeof(float) * m->nw * rows_of(sv);
+  if (rows_of(sv)) {
+    int rc;
+    if ((rc = dev_alloc(m, &m->sstate, bytes))) return rc;
+    m->resident_bytes += bytes;
+    RM_HIP(m, hipMemsetAsync(m->sstate, 0, bytes, m->stream));
+    RM_HIP(m, hipStreamSynchronize(m->stream));
+  }
+  m->solver = sv;
+  return FLEET_OK;
+}
+
+int fleet_rmodel_solver(fleet_rmodel* m) {
+  if (!m) return 0;
+  std::lock_guard<std::mutex> lk(m->mu);
+  return m->solver;
+}
+
+int fleet_rmodel_solver_state(fleet_rmodel* m, int which, float* out, size_t cap) {
+  if (!m) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  RM_SCOPE(m);
+  if (which < 0 || which > 1 || m->solver == FLEET_SOLVER_SGD || (which == 1 && m->solver != FLEET_SOLVER_ADAM))
+    return rfail(m, FLEET_ERR_ARG, "solver_state: solver %d keeps no state row %d", m->solver, which);
+  if (cap < m->nw || (m->nw && !out)) return rfail(m, FLEET_ERR_CAPACITY, "output capacity %zu < %zu", cap, m->nw);
+  if (m->nw) RM_HIP(m, hipMemcpy(out, m->sstate + (size_t)which * m->nw, sizeof(float) * m->nw, hipMemcpyDeviceToHost));
+  return FLEET_OK;
 }
 
 int fleet_rmodel_count(fleet_rmodel* m) {

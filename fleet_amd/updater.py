@@ -250,7 +250,9 @@ class FleetUpdater:
     (cppNN_backend.cpp:161-172). With ``model=`` (a ``fleet_amd.ResidentModel``) the model lives in
     HBM instead: ``weights`` and ``fc_bias`` may be None, every path runs the device form of its
     update into tensors the updater keeps and steps the model there (``descent_device``), and
-    only the merged text comes back to the host. ``kardam_models=`` may be that same model."""
+    only the merged text comes back to the host. ``kardam_models=`` may be that same model.
+    The model steps under the solver it was made with (``ResidentModel(..., solver=)``); the
+    ``weights=`` / ``fc_bias=`` path keeps no solver state and is always sgd."""
 
     def __init__(self, codec, layout, M: int, lrates: Sequence[float], weights, fc_bias, policy: int = 0,
                  alpha: float = 0.0, stale_size: int = 0, num_labels: int = 10, has_outlier: bool = False,

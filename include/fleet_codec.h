@@ -756,6 +756,14 @@ int fleet_mledger_read_version(fleet_mledger* ledger, int64_t id, float* params,
  *   fn 24: the text of `ostream << float` (decimal6.h g6_text) over all 2^32 bit
  *          patterns: sum_i g6_text_term(i, text) against libc's snprintf("%g")
  *          (tests/native/check_g6text.cpp, tests/golden/g6text_digest.json)
+ *   fn 25..28: the solvers' arithmetic (solver_math.h, x86 NaN rule applied) against
+ *          tests/native/check_solver.cpp on the CPU (tests/golden/solver_digests.json):
+ *          fn 25 sqrtf(x), fn 26 adam's denominator (float)sqrt((double)x / (1. - .999f)) +
+ *          1e-8f, fn 27 x / (1.f - .9f), each over all 2^32 x with fn 0's term; fn 28 a / b
+ *          over 2^32 pairs (a, b) = (low, high word of splitmix64(i)) and every pair of
+ *          {+-0, the smallest and largest denormal, FLT_MIN, 1, FLT_MAX, +-inf, +-NaN},
+ *          term splitmix64(splitmix64(a << 32 | b) + bits(a / b));
+ *          fn 29, 30 = fn 26, 27 with a server session's b2_t = .999f*.999f, b1_t = .9f*.9f
  * computed on the GPU; compare with the oracle's digests. */
 int fleet_selftest_digest(fleet_ctx* ctx, int fn, uint64_t* out);
 
@@ -914,6 +922,39 @@ int fleet_descent(fleet_ctx* ctx, float* weights, size_t n_weights, float* fc_bi
                   const float* grad, size_t n_grad, const int32_t* w_sizes, const uint8_t* w_present, int n_w,
                   const int32_t* b_sizes, const uint8_t* fc_layer, int n_b, float lr);
 
+/* The model step under the reference's other solvers ---------
+ * `mojo::network cnn(solver.c_str())` (cppNN_backend.cpp:40-42) runs the named
+ * solver's increment_w in network::descent() (commonLib/cppNN/solver.h:97-195):
+ *   adagrad  g1 += d*d;                       w -= (lr*d) / (sqrt(g1) + 1e-8f)
+ *   rmsprop  g1 = .999f*g1 + ((1-.999f)*d)*d; w -= (lr*d) / (sqrt(g1) + 1e-8f), lr = .01f*L
+ *   adam     g1 = .9f*g1 + (1-.9f)*d; g2 = .999f*g2 + ((1-.999f)*d)*d;          lr = .1f*L
+ *            w -= (lr*(g1/(1.f-.9f))) / ((float)sqrt((double)g2/(1.-.999f)) + 1e-8f)
+ * one IEEE rounding per operation in the type shown (solver_math.h). adam's .9f and
+ * .999f in the last line are its b1_t and b2_t, which adam::reset multiplies by b1 and
+ * b2: the two entry points below use a fresh solver's values, as written above; the
+ * models use a server session's (see fleet_model_set_solver). The state g1 (and g2, adam) is one
+ * float per weight, laid out like `weights`, zero before the first step, advanced
+ * in place; biases step by update_bias with the plain L whatever the solver. */
+#define FLEET_SOLVER_SGD 0
+#define FLEET_SOLVER_ADAGRAD 1
+#define FLEET_SOLVER_RMSPROP 2
+#define FLEET_SOLVER_ADAM 3
+/* new_solver's names ("sgd", "adagrad", "rmsprop", "adam"); -1 for any other, NULL included */
+int fleet_solver_from_name(const char* name);
+/* fleet_descent_device under `solver`. g1 / g2: n_weights floats each on the device;
+ * g2 may be NULL unless solver is adam, g1 may be NULL for sgd (FLEET_ERR_ARG
+ * otherwise, and for an unknown solver). FLEET_SOLVER_SGD is fleet_descent_device's
+ * step exactly. */
+int fleet_descent_solver_device(fleet_ctx* ctx, int solver, float* d_weights, float* d_g1, float* d_g2,
+                                float* d_fc_bias, const float* d_grad, const int32_t* w_sizes,
+                                const uint8_t* w_present, int n_w, const int32_t* b_sizes, const uint8_t* fc_layer,
+                                int n_b, float lr, void* stream);
+/* fleet_descent under `solver`: host buffers updated in place, the same header check */
+int fleet_descent_solver(fleet_ctx* ctx, int solver, float* weights, size_t n_weights, float* g1, float* g2,
+                         float* fc_bias, size_t n_fc_bias, const float* grad, size_t n_grad, const int32_t* w_sizes,
+                         const uint8_t* w_present, int n_w, const int32_t* b_sizes, const uint8_t* fc_layer, int n_b,
+                         float lr);
+
 /* The server's resident model -----------------------
  * The state the reference's updater natives keep in libnative.so globals
  * (Server/src/main/c++/cppNN_backend.cpp: cnn, models, lrates_vec, currEpoch,
@@ -937,6 +978,22 @@ int fleet_model_init_updater(fleet_model* m, const double* lrates, int n_lrates)
  * oldest dropped beyond stale_size. The merged gradient's header must describe
  * the model (FLEET_ERR_LAYOUT otherwise; the reference overruns). */
 int fleet_model_descent(fleet_model* m, const char* merged, size_t len, int client_batch_size, int stale_size);
+/* The solver `cnn` is constructed with (new_solver's names; the default is "sgd"). To be
+ * called after load and before the first descent: it allocates the zeroed state, which
+ * belongs to cnn alone (versions carry none, getParams prints none). FLEET_ERR_ARG for an
+ * unknown name (the reference dereferences NULL there) and after a descent, with
+ * nothing changed. A refused gradient leaves the state as it was; the mode-1
+ * non-finite-weight case leaves it advanced, as it leaves cnn.
+ * adam in a session: fetchParamsNative's start_epoch resets the solver once
+ * (network.h:1442; before the model is read, so no state is cleared), which leaves
+ * b1_t = .9f*.9f and b2_t = .999f*.999f for every descent of the session; nothing decays
+ * them further. adagrad's state starts at zero like the others' (the reference leaves
+ * it as the heap gave it: its fill(0) is commented out, solver.h:105-107). */
+int fleet_model_set_solver(fleet_model* m, const char* name);
+int fleet_model_solver(fleet_model* m); /* FLEET_SOLVER_* */
+/* state row `which` (0: g1, 1: g2) of n_weights floats; FLEET_ERR_ARG for a row the
+ * solver does not keep, FLEET_ERR_CAPACITY for cap < n_weights */
+int fleet_model_solver_state(fleet_model* m, int which, float* out, size_t cap);
 /* modelsSize (:324-327) */
 int fleet_model_count(fleet_model* m);
 /* getParametersNative(version) (:244-280): the full getParams text of
@@ -1011,6 +1068,13 @@ int fleet_rmodel_descent(fleet_rmodel* m, const char* merged, size_t len, int cl
  * Synchronous: one 4-byte error word is read back per step. */
 int fleet_rmodel_descent_device(fleet_rmodel* m, const void* d_merged_f32, size_t n_values, int stale_size,
                                 void* stream);
+/* fleet_model_set_solver / _solver / _solver_state on the resident model: the state rows
+ * are n_weights floats each in HBM, allocated zeroed by the call and counted in
+ * fleet_rmodel_stats; the check kernel refuses a gradient before any weight or state
+ * float is written. */
+int fleet_rmodel_set_solver(fleet_rmodel* m, const char* name);
+int fleet_rmodel_solver(fleet_rmodel* m);
+int fleet_rmodel_solver_state(fleet_rmodel* m, int which, float* out, size_t cap);
 int fleet_rmodel_count(fleet_rmodel* m);
 /* getParametersNative: the header is constant; the bias lines, the mode-0 weight lines,
  * the mode-1 dictionary lines and the index section are formatted on the device from
@@ -1037,7 +1101,8 @@ int fleet_rmodel_version_device(fleet_rmodel* m, int version, const float** d_we
 /* fleet_mledger_stage_model from the resident row, device to device, same ids; FLEET_ERR_ARG
  * for a ledger of another context than the model's */
 int fleet_rmodel_stage_mledger(fleet_mledger* ledger, fleet_rmodel* m, int version, int64_t* id);
-/* resident_bytes: the rows, 4 * roundup64(n_weights + n_biases) * (max_versions + 2);
+/* resident_bytes: the rows, 4 * roundup64(n_weights + n_biases) * (max_versions + 2), plus
+ * 4 * n_weights per state row of the solver (fleet_rmodel_set_solver);
  * device_allocs: every hipMalloc / hipHostMalloc made on the model's behalf so far */
 int fleet_rmodel_stats(fleet_rmodel* m, size_t* resident_bytes, int* device_allocs);
 size_t fleet_rmodel_workspace_bytes(const fleet_rmodel* m);
