@@ -211,6 +211,13 @@ def lib() -> C.CDLL:
         "fleet_teacher_bias_count": (sz, []),
         "fleet_teacher_forward_device": (i32, [vp, vp, vp, vp, sz, i32, vp, i32, C.c_float, vp, vp]),
         "fleet_teacher_forward": (i32, [vp, vp, sz, vp, sz, vp, sz, i32, vp, i32, C.c_float, vp]),
+        "fleet_evaluate_block_images": (sz, []),
+        "fleet_evaluate_set_grid": (i32, [i32]),
+        "fleet_evaluate_device": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "fleet_evaluate": (i32, [vp, vp, sz, vp, sz, vp, sz, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "fleet_model_evaluate": (i32, [vp, i32, vp, sz, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "fleet_rmodel_evaluate": (i32, [vp, i32, vp, sz, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "fleet_rmodel_evaluate_device": (i32, [vp, i32, vp, sz, i32, vp, vp, i32, vp, vp, vp, vp]),
         "fleet_model_load": (i32, [vp, vp, sz, i32, C.POINTER(vp)]),
         "fleet_model_destroy": (None, [vp]),
         "fleet_model_last_error": (C.c_char_p, [vp]),
@@ -365,6 +372,102 @@ class plan_override:
     def __exit__(self, *exc):
         set_plan(self.prev)
         return False
+
+
+class Evaluation:
+    """What the Driver's ``test()`` returns for a model (Driver/src/main/c++/cppNN_backend.cpp:53-75)
+    -- ``error`` and ``accuracy``, the ``valE, valA`` of FLeet's CSV lines -- with the count of
+    correct images and, per image, the predicted class and its probability. Unpacks as
+    ``error, accuracy``, the tuple the reference returns."""
+
+    __slots__ = ("error", "accuracy", "correct", "predictions", "probabilities")
+
+    def __init__(self, error, accuracy, correct, predictions, probabilities):
+        self.error, self.accuracy, self.correct = error, accuracy, correct
+        self.predictions, self.probabilities = predictions, probabilities
+
+    def __iter__(self):
+        return iter((self.error, self.accuracy))
+
+    def __repr__(self):
+        return f"Evaluation(error={self.error!r}, accuracy={self.accuracy!r}, correct={self.correct!r})"
+
+
+def evaluate_block_images() -> int:
+    """Images a block of the evaluation's forward kernel takes at a time."""
+    return int(lib().fleet_evaluate_block_images())
+
+
+class evaluate_grid_override:
+    """``with evaluate_grid_override(2): ...`` caps the evaluation kernel's grid at that many
+    blocks, so that a small set walks more than one grid-stride pass (tests; process-wide, as
+    :class:`plan_override`)."""
+
+    def __init__(self, max_blocks: int):
+        self.max_blocks = int(max_blocks)
+
+    def __enter__(self):
+        self.prev = lib().fleet_evaluate_set_grid(self.max_blocks)
+        return self
+
+    def __exit__(self, *exc):
+        lib().fleet_evaluate_set_grid(self.prev)
+        return False
+
+
+def _eval_host_args(images, labels, idx):
+    x = np.ascontiguousarray(images, dtype=np.float32)
+    if x.ndim == 1:
+        x = x.reshape(1, -1)
+    lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+    if x.ndim != 2 or len(lab) != x.shape[0]:
+        raise ValueError("images [N, F] and one label per image")
+    ix = None if idx is None else np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+    return x, lab, ix, (x.shape[0] if ix is None else len(ix))
+
+
+def _eval_host_call(fn, head, images, labels, idx):
+    """one of the host-buffer evaluate entry points: fn(*head, images .., outputs ..) -> (rc, Evaluation)"""
+    x, lab, ix, B = _eval_host_args(images, labels, idx)
+    err, acc, cor = C.c_float(0), C.c_float(0), C.c_int32(0)
+    pred, prob = np.empty(max(B, 1), np.int32), np.empty(max(B, 1), np.float32)
+    rc = fn(*head, x.ctypes.data, x.shape[0], x.shape[1], lab.ctypes.data, None if ix is None else ix.ctypes.data, B,
+            C.byref(err), C.byref(acc), C.byref(cor), pred.ctypes.data, prob.ctypes.data)
+    return rc, Evaluation(np.float32(err.value), np.float32(acc.value), int(cor.value), pred[:B], prob[:B])
+
+
+def _eval_device_out(images_f32, labels_i32, idx, out):
+    """shapes and output tensors of a device evaluation: (n_images, F, B, out dict)"""
+    import torch
+    if images_f32.dim() != 2 or labels_i32.numel() != images_f32.shape[0]:
+        raise ValueError("images [N, F] and one label per image")
+    for t, dt, name in ((images_f32, torch.float32, "images"), (labels_i32, torch.int32, "labels"), (idx, torch.int32, "idx")):
+        if t is not None and (t.dtype != dt or not t.is_cuda or not t.is_contiguous()):
+            raise ValueError(f"{name}: a contiguous {dt} CUDA tensor")
+    B = images_f32.shape[0] if idx is None else idx.numel()
+    dev = images_f32.device
+    o = dict(out) if out else {}
+    o.setdefault("predictions", torch.empty(B, dtype=torch.int32, device=dev))
+    o.setdefault("probabilities", torch.empty(B, dtype=torch.float32, device=dev))
+    o.setdefault("result", torch.empty(3, dtype=torch.float32, device=dev))
+    for k, n, dt in (("predictions", B, torch.int32), ("probabilities", B, torch.float32), ("result", 3, torch.float32),
+                     ("costs", B, torch.float32), ("probs10", 10 * B, torch.float32)):
+        t = o.get(k)
+        if t is not None and (t.dtype != dt or t.numel() < n or not t.is_cuda or not t.is_contiguous()):
+            raise ValueError(f"out[{k!r}]: a contiguous {dt} CUDA tensor of at least {n} elements")
+    return images_f32.shape[0], images_f32.shape[1], B, o
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def evaluation_from_device(out) -> Evaluation:
+    """The :class:`Evaluation` of a device evaluation's output tensors (synchronises on the copy)."""
+    r = out["result"].cpu().numpy()
+    pred, prob = out.get("predictions"), out.get("probabilities")
+    return Evaluation(r[0], r[1], int(r[2:3].view(np.int32)[0]),
+                      None if pred is None else pred.cpu().numpy(), None if prob is None else prob.cpu().numpy())
 
 
 def layout_from_sizes(w_sizes: Sequence[int], b_sizes: Sequence[int]):
@@ -887,6 +990,37 @@ class Codec:
                                                          images_f32.data_ptr(), n_img, F,
                                                          idx_i32.data_ptr() if idx_i32 is not None else None, B,
                                                          float(temperature), probs_f32.data_ptr(), _stream(stream)))
+
+    # -- the Driver's evaluation ---------------------------------
+    def evaluate(self, w, b, images, labels, idx=None) -> "Evaluation":
+        """The Driver's ``test()`` (Driver/src/main/c++/cppNN_backend.cpp:53-75) of the MNIST
+        network with weights ``w`` and biases ``b`` (``teacher_forward``'s layout) over
+        ``images[idx]`` (every image in order when ``idx`` is None): bit for bit the
+        reference's error, accuracy, predictions and their probabilities."""
+        wv = np.ascontiguousarray(w, dtype=np.float32).reshape(-1)
+        bv = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+        rc, ev = _eval_host_call(self._L.fleet_evaluate, (self._h, wv.ctypes.data, len(wv), bv.ctypes.data, len(bv)),
+                                 images, labels, idx)
+        self._check(rc)
+        return ev
+
+    def evaluate_device(self, w_f32, b_f32, images_f32, labels_i32, idx_i32=None, out=None, stream=None) -> dict:
+        """Device-resident :meth:`evaluate`: CUDA tensors w [21448], b [82], images [N, F >= 784]
+        float32, labels [N] int32, idx int32 or None. Runs on ``stream`` (default: torch's
+        current) and does not synchronise. ``out`` may hold tensors to write -- ``predictions``
+        [B] int32, ``probabilities`` [B], ``result`` [3] (float error, float accuracy, the bits of
+        int32 correct), and optionally ``costs`` [B], ``probs10`` [B, 10]; ``predictions`` or
+        ``probabilities`` given as None are not written. Returns the dict of tensors written
+        (:func:`evaluation_from_device` reads it). Index errors at check()."""
+        if w_f32.numel() != self._L.fleet_teacher_weight_count() or b_f32.numel() != self._L.fleet_teacher_bias_count():
+            raise ValueError("weights / biases of the wrong size")
+        n_img, F, B, o = _eval_device_out(images_f32, labels_i32, idx_i32, out)
+        self._check(self._L.fleet_evaluate_device(self._h, w_f32.data_ptr(), b_f32.data_ptr(), images_f32.data_ptr(),
+                                                  n_img, F, labels_i32.data_ptr(), _ptr(idx_i32), B,
+                                                  _ptr(o.get("predictions")), _ptr(o.get("probabilities")),
+                                                  _ptr(o.get("costs")), _ptr(o.get("probs10")), o["result"].data_ptr(),
+                                                  _stream(stream)))
+        return o
 
     # -- descentNative's model step (SURVEY.md §8 f1) ----------------------------
     @staticmethod
@@ -1910,6 +2044,23 @@ class Model:
         nw, nb, ge, _ = self.shape()
         return self.codec.model_ledger(nw, nb, ge, workers, max_versions)
 
+    def evaluate(self, images, labels, version=None, idx=None) -> "Evaluation":
+        """What the Driver reports for a version of this model: fetchParamsNative + evaluateNative
+        (Driver/src/main/c++/cppNN_backend.cpp:179-205) over ``images[idx]``. ``version``: None =
+        the newest of ``models`` (what Evaluator.crossValidation asks for), ``-1`` = ``cnn``, else
+        ``models[version]``. The model must be the MNIST network (FleetError otherwise).
+
+        The Driver's view in mode 1: the Driver evaluates the broadcast text, whose weights are
+        the quantised dictionary values printed with 6 digits, not the stored version. That is
+        ``Model(codec, rm.getParametersNative(v), mode).evaluate(images, labels, version=-1)``:
+        the text is read by this project's own network::read and what it read is evaluated."""
+        v = self.modelsSize() - 1 if version is None else int(version)
+        if version is None and v < 0:
+            raise ValueError("the model holds no version yet (initUpdater); version=-1 evaluates cnn")
+        rc, ev = _eval_host_call(self._L.fleet_model_evaluate, (self._h, v), images, labels, idx)
+        self._check(rc)
+        return ev
+
     def export(self, version: int = -1):
         """(weights, biases) of models[version]; version -1 = the current model."""
         nw, nb, _, _ = self.shape()
@@ -2081,6 +2232,34 @@ class ResidentModel:
         w, b = np.empty(nw, np.float32), np.empty(nb, np.float32)
         self._check(self._L.fleet_rmodel_export(self._h, int(version), w.ctypes.data, nw, b.ctypes.data, nb))
         return w, b
+
+    def _eval_version(self, version):
+        v = self.modelsSize() - 1 if version is None else int(version)
+        if version is None and v < 0:
+            raise ValueError("the model holds no version yet (initUpdater); version=-1 evaluates cnn")
+        return v
+
+    def evaluate(self, images, labels, version=None, idx=None) -> "Evaluation":
+        """:meth:`Model.evaluate` from the resident row: host images, labels and indices are
+        uploaded, no weight crosses PCIe; returns synchronised."""
+        rc, ev = _eval_host_call(self._L.fleet_rmodel_evaluate, (self._h, self._eval_version(version)), images, labels, idx)
+        self._check(rc)
+        return ev
+
+    def evaluate_device(self, images_f32, labels_i32, version=None, idx=None, out=None, stream=None) -> dict:
+        """:meth:`evaluate` on tensors where they live: images [N, F >= 784] float32, labels [N]
+        int32, idx int32 or None, on this model's device. Runs on ``stream`` (default: torch's
+        current) and does not synchronise; returns device tensors ``predictions`` [B] int32,
+        ``probabilities`` [B] and ``result`` [3] (float error, float accuracy, the bits of int32
+        correct), written into ``out``'s tensors where it has them (``predictions`` /
+        ``probabilities`` given as None are not written). :func:`evaluation_from_device` reads
+        them. Index errors at ``codec.check()``."""
+        n_img, F, B, o = _eval_device_out(images_f32, labels_i32, idx, out)
+        self._check(self._L.fleet_rmodel_evaluate_device(self._h, self._eval_version(version), images_f32.data_ptr(),
+                                                         n_img, F, labels_i32.data_ptr(), _ptr(idx), B,
+                                                         _ptr(o.get("predictions")), _ptr(o.get("probabilities")),
+                                                         o["result"].data_ptr(), _stream(stream)))
+        return o
 
     def stats(self) -> dict:
         rb, na = C.c_size_t(0), C.c_int(0)

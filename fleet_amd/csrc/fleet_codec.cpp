@@ -142,6 +142,10 @@ struct fleet_ctx {
   size_t d_kflags_cap = 0;
   uint32_t kflag_epoch = 0;
   uint32_t kflag_test_skew = 0;       // fleet_test_kardam_skew: reduce blocks wait for a later epoch
+  // fleet_evaluate_device: the costs and predictions a caller does not take, [B floats | B int32]
+  // (a grown buffer is retired, not freed: an evaluation on another stream may still write it)
+  uint8_t* d_eval = nullptr;
+  int d_eval_cap = 0;  // the B it holds
 };
 
 namespace {
@@ -476,7 +480,7 @@ void fleet_destroy(fleet_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (void* p : {(void*)c->d_a, (void*)c->d_b, (void*)c->d_out, (void*)c->d_f32, (void*)c->d_dampen,
                   (void*)c->d_hdr, (void*)c->d_err, (void*)c->d_partials, (void*)c->d_dev_dampen,
-                  (void*)c->d_dev_hdr, (void*)c->d_dev_err, (void*)c->d_kflags})
+                  (void*)c->d_dev_hdr, (void*)c->d_dev_err, (void*)c->d_kflags, (void*)c->d_eval})
     if (p) (void)hipFree(p);
   for (void* p : c->retired) (void)hipFree(p);
   for (void* p : {(void*)c->h_stage, (void*)c->h_hdr, (void*)c->h_err})
@@ -1626,6 +1630,79 @@ int fleet_teacher_forward(fleet_ctx* c, const float* w, size_t n_w, const float*
   HIP_TRY(c, hipMemcpyAsync(h + o_p, d + o_p, sizeof(float) * (size_t)B * 10, hipMemcpyDeviceToHost, c->stream));
   if ((rc = read_err(c, c->stream))) return rc;
   std::memcpy(probs, h + o_p, sizeof(float) * (size_t)B * 10);
+  return FLEET_OK;
+}
+
+size_t fleet_evaluate_block_images(void) { return (size_t)fleet::eval_block_images(); }
+int fleet_evaluate_set_grid(int max_blocks) { return fleet::eval_set_grid(max_blocks); }
+
+int fleet_evaluate_device(fleet_ctx* c, const void* d_w, const void* d_b, const void* d_images, size_t n_images, int F,
+                          const void* d_labels, const void* d_idx, int B, void* d_pred, void* d_prob, void* d_cost,
+                          void* d_probs10, void* d_result, void* stream) {
+  if (!c || !d_w || !d_b || !d_images || !d_labels || !d_result || B <= 0 || F < 28 * 28 || n_images == 0 ||
+      (!d_idx && (size_t)B > n_images))
+    return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  if ((!d_cost || !d_pred) && B > c->d_eval_cap) {
+    if (c->d_eval) c->retired.push_back(c->d_eval);
+    c->d_eval = nullptr;
+    c->d_eval_cap = 0;
+    const hipError_t e = hipMalloc((void**)&c->d_eval, 8 * (size_t)B + 64);
+    if (e != hipSuccess) return fail(c, FLEET_ERR_NOMEM, "hipMalloc(%zu): %s", 8 * (size_t)B, hipGetErrorString(e));
+    c->d_eval_cap = B;
+  }
+  float* cost = d_cost ? (float*)d_cost : (float*)c->d_eval;
+  int32_t* pred = d_pred ? (int32_t*)d_pred : (int32_t*)(c->d_eval + 4 * (size_t)c->d_eval_cap);
+  HIP_TRY(c, fleet::launch_eval((const float*)d_w, (const float*)d_b, (const float*)d_images, (int64_t)n_images, F,
+                                (const int32_t*)d_labels, (const int32_t*)d_idx, B, pred, (float*)d_prob, cost,
+                                (float*)d_probs10, (float*)d_result, c->d_dev_err, pick(c, stream)));
+  return FLEET_OK;
+}
+
+int fleet_evaluate(fleet_ctx* c, const float* w, size_t n_w, const float* b, size_t n_b, const float* images,
+                   size_t n_images, int F, const int32_t* labels, const int32_t* idx, int B, float* error,
+                   float* accuracy, int32_t* correct, int32_t* pred, float* prob) {
+  if (!c || !w || !b || !images || !labels || B <= 0 || F < 28 * 28 || n_images == 0) return FLEET_ERR_ARG;
+  if (n_w != fleet_teacher_weight_count() || n_b != fleet_teacher_bias_count())
+    return fail(c, FLEET_ERR_ARG, "evaluate: %zu weights and %zu biases, expected %zu and %zu", n_w, n_b,
+                fleet_teacher_weight_count(), fleet_teacher_bias_count());
+  if (!idx && (size_t)B > n_images) return fail(c, FLEET_ERR_ARG, "evaluate: %d images asked of %zu", B, n_images);
+  for (int i = 0; idx && i < B; ++i)
+    if (idx[i] < 0 || (size_t)idx[i] >= n_images)
+      return fail(c, FLEET_ERR_ARG, "image %d: index %d outside the %zu images", i, idx[i], n_images);
+  // the images the evaluation reads: all of them with idx, the first B without
+  const size_t rows = idx ? n_images : (size_t)B;
+  const size_t o_b = round16(sizeof(float) * n_w), o_x = o_b + round16(sizeof(float) * n_b);
+  const size_t o_l = o_x + round16(sizeof(float) * rows * (size_t)F), o_i = o_l + round16(4 * rows);
+  const size_t o_pred = o_i + round16(4 * (size_t)B), o_prob = o_pred + round16(4 * (size_t)B);
+  const size_t o_cost = o_prob + round16(4 * (size_t)B), o_res = o_cost + round16(4 * (size_t)B), o_end = o_res + 16;
+  uint8_t* d = nullptr;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    DEVICE_SCOPE(c);
+    if ((rc = grow_dev(c, &c->d_a, &c->d_a_cap, o_end))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    d = c->d_a;
+    HIP_TRY(c, hipMemcpyAsync(d, w, sizeof(float) * n_w, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d + o_b, b, sizeof(float) * n_b, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d + o_x, images, sizeof(float) * rows * (size_t)F, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d + o_l, labels, 4 * rows, hipMemcpyHostToDevice, c->stream));
+    if (idx) HIP_TRY(c, hipMemcpyAsync(d + o_i, idx, 4 * (size_t)B, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, fleet::launch_eval((const float*)d, (const float*)(d + o_b), (const float*)(d + o_x), (int64_t)rows, F,
+                                  (const int32_t*)(d + o_l), idx ? (const int32_t*)(d + o_i) : nullptr, B,
+                                  (int32_t*)(d + o_pred), (float*)(d + o_prob), (float*)(d + o_cost), nullptr,
+                                  (float*)(d + o_res), c->d_err, c->stream));
+    float res[4] = {0, 0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(res, d + o_res, 12, hipMemcpyDeviceToHost, c->stream));
+    if (pred) HIP_TRY(c, hipMemcpyAsync(pred, d + o_pred, 4 * (size_t)B, hipMemcpyDeviceToHost, c->stream));
+    if (prob) HIP_TRY(c, hipMemcpyAsync(prob, d + o_prob, 4 * (size_t)B, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = read_err(c, c->stream))) return rc;
+    if (error) *error = res[0];
+    if (accuracy) *accuracy = res[1];
+    if (correct) std::memcpy(correct, &res[2], 4);
+  }
   return FLEET_OK;
 }
 

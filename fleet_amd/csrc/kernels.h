@@ -189,6 +189,16 @@ hipError_t launch_teacher_forward(const float* w, const float* b, const float* i
                                   hipStream_t s);
 int64_t teacher_weight_count();
 int64_t teacher_bias_count();
+// the Driver's test() (eval_kernels.hip): k_eval_forward over images idx[0..B) (idx == nullptr:
+// images 0..B-1) of the n_images x F rows, then k_eval_reduce. pred[B], cost[B] and
+// result (float error, float accuracy, int32 correct) are written; prob[B] and
+// probs10[B][10] when not nullptr. hipErrorInvalidValue for B <= 0, F < 784 or a missing
+// pred / cost / result.
+hipError_t launch_eval(const float* w, const float* b, const float* images, int64_t n_images, int F,
+                       const int32_t* labels, const int32_t* idx, int B, int32_t* pred, float* prob, float* cost,
+                       float* probs10, float* result, int* err, hipStream_t s);
+int eval_block_images();
+int eval_set_grid(int max_blocks);  // 0: three blocks per CU; returns the previous value
 hipError_t launch_encode_model_params(const float* weights, int64_t n_w, const float* biases, int64_t n_b, int64_t reps,
                                       uint8_t* out, hipStream_t s);
 hipError_t launch_encode_i32(const int32_t* codes, int64_t n, uint8_t* out, hipStream_t s);

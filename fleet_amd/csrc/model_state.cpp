@@ -102,6 +102,7 @@ int parse(fleet_model* m, const std::string& t, std::vector<float>* w, std::vect
     for (size_t i = 1; i < tk.size(); ++i) {
       long v;
       if (to_long(tk[i], &v)) L.args.push_back(v);
+      else L.act = tk[i];
     }
     auto need = [&](size_t k) { return L.args.size() >= k; };
     if (L.type == "input") {
@@ -195,6 +196,63 @@ int parse(fleet_model* m, const std::string& t, std::vector<float>* w, std::vect
   }
   return FLEET_OK;
 }
+
+}  // namespace
+
+int fleet::eval_check_mnist(const fleet_model* m, std::string* why) {
+  struct Want {
+    const char *name, *type, *act;
+    long args[3];
+    int n_args;
+  };
+  static const Want want[] = {{"I1", "input", "identity", {28, 28, 1}, 3},
+                              {"C1", "convolution", "elu", {5, 8, 1}, 3},
+                              {"P1", "semi_stochastic_pool", "", {3, 3, 0}, 2},
+                              {"C2i", "convolution", "elu", {1, 16, 1}, 3},
+                              {"C2", "convolution", "elu", {5, 48, 1}, 3},
+                              {"P2", "semi_stochastic_pool", "", {2, 2, 0}, 2},
+                              {"FC2", "fully_connected", "softmax", {10, 0, 0}, 1}};
+  const size_t n = sizeof want / sizeof want[0];
+  auto config = [](const std::string& type, const std::vector<long>& args, const std::string& act) {
+    std::string s = type;
+    for (long a : args) s += " " + std::to_string(a);
+    return act.empty() ? s : s + " " + act;
+  };
+  for (size_t k = 0; k < n; ++k) {
+    const Want& W = want[k];
+    const std::string expect = config(W.type, std::vector<long>(W.args, W.args + W.n_args), W.act);
+    if (k >= m->layers.size()) {
+      *why = std::string("layer ") + std::to_string(k) + " (" + W.name + " " + expect + ") is missing";
+      return FLEET_ERR_ARG;
+    }
+    const Layer& L = m->layers[k];
+    // (an input layer's "identity" is what getParams prints for it; a text without the word reads the same)
+    const bool act_ok = L.act == W.act || (k == 0 && L.act.empty());
+    if (L.type != W.type || !act_ok || L.args != std::vector<long>(W.args, W.args + W.n_args)) {
+      *why = "layer " + std::to_string(k) + " is " + L.name + " " + config(L.type, L.args, L.act) + ", the MNIST network has " +
+             W.name + " " + expect;
+      return FLEET_ERR_ARG;
+    }
+  }
+  if (m->layers.size() != n) {
+    *why = "layer " + std::to_string(n) + " (" + m->layers[n].name + ") follows FC2, the MNIST network ends there";
+    return FLEET_ERR_ARG;
+  }
+  // a chain: every layer feeds the next and nothing else
+  if (m->edge_w_size.size() != n - 1 || m->dims.size() != 12) {
+    *why = "the layer graph is not the chain I1 - C1 - P1 - C2i - C2 - P2 - FC2";
+    return FLEET_ERR_ARG;
+  }
+  static const int32_t dims[12] = {5, 5, 8, 1, 1, 128, 5, 5, 768, 192, 10, 1};
+  for (int i = 0; i < 12; ++i)
+    if (m->dims[(size_t)i] != dims[i]) {
+      *why = "the layer graph is not the chain I1 - C1 - P1 - C2i - C2 - P2 - FC2";
+      return FLEET_ERR_ARG;
+    }
+  return FLEET_OK;
+}
+
+namespace {
 
 size_t n_weights(const fleet_model* m) {
   size_t n = 0;
@@ -454,6 +512,26 @@ double fleet_model_get_lrate(fleet_model* m) {
   if (!m) return 0.0;
   std::lock_guard<std::mutex> lk(m->mu);
   return (double)m->lr;
+}
+
+int fleet_model_evaluate(fleet_model* m, int version, const float* images, size_t n_images, int F,
+                         const int32_t* labels, const int32_t* idx, int B, float* error, float* accuracy,
+                         int32_t* correct, int32_t* pred, float* prob) {
+  if (!m) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (!images || !labels || B <= 0 || F < 28 * 28 || n_images == 0)
+    return mfail(m, FLEET_ERR_ARG, "evaluate: images and labels, B >= 1, F >= 784");
+  std::string why;
+  if (fleet::eval_check_mnist(m, &why)) return mfail(m, FLEET_ERR_ARG, "evaluate: %s", why.c_str());
+  const Version* v = &m->cnn;
+  if (version >= 0) {
+    if ((size_t)version >= m->models.size()) return mfail(m, FLEET_ERR_ARG, "model version %d of %zu", version, m->models.size());
+    v = &m->models[(size_t)version];
+  }
+  const int rc = fleet_evaluate(m->ctx, v->w.data(), v->w.size(), v->b.data(), v->b.size(), images, n_images, F, labels, idx,
+                                B, error, accuracy, correct, pred, prob);
+  if (rc) return mfail(m, rc, "evaluate: %s", m->ctx ? fleet_last_error(m->ctx) : "the model has no device context");
+  return FLEET_OK;
 }
 
 int fleet_model_export(fleet_model* m, int version, float* weights, size_t n_weights, float* biases, size_t n_biases) {

@@ -13,7 +13,7 @@
 namespace fleet {
 
 struct Layer {
-  std::string name, type;
+  std::string name, type, act;  // act: the config's activation word ("elu", "softmax", ...), if any
   std::vector<long> args;
   bool use_bias = false, fc = false;
   int cols = 1, rows = 1, chans = 1;  // node dims after the graph is connected
@@ -26,6 +26,13 @@ struct Version {
   std::vector<float> b;  // biases of the use_bias() layers, layer order
 };
 
+}  // namespace fleet
+
+struct fleet_model;
+namespace fleet {
+// FLEET_OK when m is the Driver's MNIST network (Driver/src/main/c++/cppNN_backend.cpp:109-115),
+// the only one the evaluation kernels run; otherwise *why names the first layer that differs
+int eval_check_mnist(const fleet_model* m, std::string* why);
 }  // namespace fleet
 
 struct fleet_model {

@@ -55,6 +55,8 @@ struct fleet_rmodel {
   int solver = 0;
   bool stepped = false;
   size_t gtext_cap = 0, grad_cap = 0;
+  uint8_t* eval_ws = nullptr;  // evaluation: [B costs | B predictions | B p | result | staged images, labels, indices]
+  size_t eval_cap = 0;
   int* h_pin = nullptr;  // pinned: [0] the error word's copy, [4..] the counts line
   // carved from tab / work
   fleet::RmLayout lay{};
@@ -193,7 +195,7 @@ void release(fleet_rmodel* m) {
     DeviceScope sc(m->device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
     for (void* p : {(void*)m->state, (void*)m->tab, (void*)m->work, (void*)m->text, (void*)m->a20, (void*)m->gtext,
-                    (void*)m->grad, (void*)m->sstate})
+                    (void*)m->grad, (void*)m->sstate, (void*)m->eval_ws})
       if (p) (void)hipFree(p);
     if (m->h_pin) (void)hipHostFree(m->h_pin);
     if (m->stream) (void)hipStreamDestroy(m->stream);
@@ -364,6 +366,39 @@ int version_row(fleet_rmodel* m, int version, int* row) {
   if (version < 0 || (size_t)version >= m->models.size())
     return rfail(m, FLEET_ERR_ARG, "model version %d of %zu", version, m->models.size());
   *row = m->models[(size_t)version];
+  return FLEET_OK;
+}
+
+// the evaluation workspace: allocated on first use, grown only for a larger need
+int eval_workspace(fleet_rmodel* m, size_t bytes) {
+  if (bytes <= m->eval_cap) return FLEET_OK;
+  if (m->eval_ws) {  // (an evaluation on a caller's stream may still write the old one)
+    RM_HIP(m, hipDeviceSynchronize());
+    (void)hipFree(m->eval_ws);
+  }
+  m->eval_ws = nullptr;
+  m->eval_cap = 0;
+  const int rc = dev_alloc(m, &m->eval_ws, bytes);
+  if (rc) return rc;
+  m->eval_cap = bytes;
+  return FLEET_OK;
+}
+
+inline size_t r256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// both evaluate forms, the lock held: `staged` bytes follow the per-image part of the workspace
+int evaluate_on(fleet_rmodel* m, int version, const void* d_images, size_t n_images, int F, const void* d_labels,
+                const void* d_idx, int B, void* d_pred, void* d_prob, void* d_result, size_t staged, hipStream_t s) {
+  std::string why;
+  if (fleet::eval_check_mnist(m->host, &why)) return rfail(m, FLEET_ERR_ARG, "evaluate: %s", why.c_str());
+  int row = 0, rc;
+  if (version >= 0 && (rc = version_row(m, version, &row))) return rc;
+  if ((rc = eval_workspace(m, 3 * r256(4 * (size_t)B) + 256 + staged))) return rc;
+  uint8_t* ws = m->eval_ws;
+  if ((rc = fleet_evaluate_device(m->ctx, row_w(m, row), row_b(m, row), d_images, n_images, F, d_labels, d_idx, B,
+                                  d_pred ? d_pred : ws + r256(4 * (size_t)B), d_prob, ws, nullptr, d_result, (void*)s)))
+    return rfail(m, rc, "evaluate: %s", rc == FLEET_ERR_ARG ? "images, labels and a result, B >= 1 (and <= n_images without indices), F >= 784"
+                                                            : fleet_last_error(m->ctx));
   return FLEET_OK;
 }
 
@@ -688,6 +723,59 @@ int fleet_rmodel_stage_mledger(fleet_mledger* ledger, fleet_rmodel* m, int versi
   RM_SCOPE(m);
   RM_HIP(m, hipStreamSynchronize(m->stream));
   if (id) *id = vid;
+  return FLEET_OK;
+}
+
+int fleet_rmodel_evaluate_device(fleet_rmodel* m, int version, const void* d_images, size_t n_images, int F,
+                                 const void* d_labels, const void* d_idx, int B, void* d_pred, void* d_prob,
+                                 void* d_result, void* stream) {
+  if (!m) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  RM_SCOPE(m);
+  if (!d_images || !d_labels || !d_result || B <= 0 || F < 28 * 28 || n_images == 0 || (!d_idx && (size_t)B > n_images))
+    return rfail(m, FLEET_ERR_ARG, "evaluate: images, labels and a result, B >= 1 (and <= n_images without indices), F >= 784");
+  return evaluate_on(m, version, d_images, n_images, F, d_labels, d_idx, B, d_pred, d_prob, d_result, 0,
+                     caller_stream(stream));
+}
+
+int fleet_rmodel_evaluate(fleet_rmodel* m, int version, const float* images, size_t n_images, int F,
+                          const int32_t* labels, const int32_t* idx, int B, float* error, float* accuracy,
+                          int32_t* correct, int32_t* pred, float* prob) {
+  if (!m) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  RM_SCOPE(m);
+  if (!images || !labels || B <= 0 || F < 28 * 28 || n_images == 0 || (!idx && (size_t)B > n_images))
+    return rfail(m, FLEET_ERR_ARG, "evaluate: images and labels, B >= 1 (and <= n_images without indices), F >= 784");
+  for (int i = 0; idx && i < B; ++i)
+    if (idx[i] < 0 || (size_t)idx[i] >= n_images)
+      return rfail(m, FLEET_ERR_ARG, "image %d: index %d outside the %zu images", i, idx[i], n_images);
+  std::string why;
+  if (fleet::eval_check_mnist(m->host, &why)) return rfail(m, FLEET_ERR_ARG, "evaluate: %s", why.c_str());
+  int row = 0, rc;
+  if (version >= 0 && (rc = version_row(m, version, &row))) return rc;
+  const size_t rows = idx ? n_images : (size_t)B;  // the images the evaluation reads
+  const size_t per = 3 * r256(4 * (size_t)B) + 256;
+  const size_t o_x = per, o_l = o_x + r256(sizeof(float) * rows * (size_t)F), o_i = o_l + r256(4 * rows);
+  const size_t staged = o_i + r256(4 * (size_t)B) - per;
+  if ((rc = eval_workspace(m, per + staged))) return rc;
+  uint8_t* ws = m->eval_ws;
+  hipStream_t s = m->stream;
+  RM_HIP(m, hipMemcpyAsync(ws + o_x, images, sizeof(float) * rows * (size_t)F, hipMemcpyHostToDevice, s));
+  RM_HIP(m, hipMemcpyAsync(ws + o_l, labels, 4 * rows, hipMemcpyHostToDevice, s));
+  if (idx) RM_HIP(m, hipMemcpyAsync(ws + o_i, idx, 4 * (size_t)B, hipMemcpyHostToDevice, s));
+  uint8_t* d_pred = ws + r256(4 * (size_t)B);
+  uint8_t* d_prob = ws + 2 * r256(4 * (size_t)B);
+  uint8_t* d_res = ws + 3 * r256(4 * (size_t)B);
+  if ((rc = evaluate_on(m, version, ws + o_x, rows, F, ws + o_l, idx ? ws + o_i : nullptr, B, d_pred, d_prob, d_res, staged, s)))
+    return rc;
+  float res[4] = {0, 0, 0, 0};
+  RM_HIP(m, hipMemcpyAsync(res, d_res, 12, hipMemcpyDeviceToHost, s));
+  if (pred) RM_HIP(m, hipMemcpyAsync(pred, d_pred, 4 * (size_t)B, hipMemcpyDeviceToHost, s));
+  if (prob) RM_HIP(m, hipMemcpyAsync(prob, d_prob, 4 * (size_t)B, hipMemcpyDeviceToHost, s));
+  if ((rc = fleet_check(m->ctx, (void*)s))) return rfail(m, rc, "evaluate: %s", fleet_last_error(m->ctx));
+  if (error) *error = res[0];
+  if (accuracy) *accuracy = res[1];
+  if (correct) std::memcpy(correct, &res[2], 4);
   return FLEET_OK;
 }
 

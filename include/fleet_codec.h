@@ -864,6 +864,46 @@ int fleet_teacher_forward_device(fleet_ctx* ctx, const void* d_w, const void* d_
 int fleet_teacher_forward(fleet_ctx* ctx, const float* w, size_t n_w, const float* b, size_t n_b, const float* images,
                           size_t n_images, int F, const int32_t* idx, int B, float temperature, float* probs);
 
+/* Evaluation: the Driver's test() (Driver/src/main/c++/cppNN_backend.cpp:53-75, called by
+ * evaluateNative :201-205 on the network of :109-115, the teacher's network above), bit for
+ * bit. For image k of the B evaluated, in the order given:
+ *   out  = cnn.forward(x_k, 1.f, thread, 0) (commonLib/cppNN/network.h:523-592): the
+ *          teacher's forward at temperature 1 with both semi-stochastic pools at
+ *          train == 0 (commonLib/cppNN/layer.h:540: the largest value always);
+ *   argm = arg_max(out, 10) (network.h:146-153; predict_class :510-515): ties keep the
+ *          first index, a NaN never wins and never loses its place;
+ *   p = out[argm]; cost_k = ((0.5f * d) * d), d = p - (float)label_k (cost.h:49-51: the
+ *          target is the label itself); correct += (argm == label_k);
+ * then error = (0.f + cost_0 + cost_1 + ...) / (float)B, added in binary32 in image order,
+ * and accuracy = ((float)correct / (float)B) * 100.f. Without NaN among weights, biases
+ * and pixels every output is bit-identical to the reference's; with NaN inputs the NaN
+ * positions and every other value are, NaN bit patterns are not pinned.
+ * B <= 0 is FLEET_ERR_ARG (the reference divides 0 by 0).
+ * w / b: fleet_teacher_forward's layout; images [n_images][F], F >= 784 (the first 784
+ * floats of a row are read); labels [n_images] int32; idx NULL (images 0..B-1, B <=
+ * n_images) or B indices into the images. */
+/* images a block of the forward kernel takes at a time (its group size) */
+size_t fleet_evaluate_block_images(void);
+/* tests: cap the forward kernel's grid at max_blocks so that a small B walks more than one
+ * grid-stride pass (0: the default, three blocks per CU); returns the previous cap */
+int fleet_evaluate_set_grid(int max_blocks);
+/* device buffers, on the caller's stream, not synchronised. Per-image outputs d_pred
+ * (int32[B]), d_prob (float[B], p), d_cost (float[B]), d_probs10 (float[B][10]) may each
+ * be NULL; d_result: float error, float accuracy, int32 correct. Costs and predictions
+ * the caller does not take go to a workspace of the context, allocated on first use and
+ * grown only for a larger B; evaluations that use it must be ordered with each other (one
+ * stream, or d_cost and d_pred of the caller's own). An index outside [0, n_images) is
+ * reported by fleet_check as FLEET_ERR_ARG, the outputs then unspecified. */
+int fleet_evaluate_device(fleet_ctx* ctx, const void* d_w, const void* d_b, const void* d_images, size_t n_images, int F,
+                          const void* d_labels, const void* d_idx, int B, void* d_pred, void* d_prob, void* d_cost,
+                          void* d_probs10, void* d_result, void* stream);
+/* host buffers, synchronous; error, accuracy, correct, pred[B] and prob[B] may each be
+ * NULL. FLEET_ERR_ARG before any launch: NULL inputs, F < 784, B <= 0, n_w / n_b other than
+ * fleet_teacher_weight_count() / fleet_teacher_bias_count(), an index outside the images. */
+int fleet_evaluate(fleet_ctx* ctx, const float* w, size_t n_w, const float* b, size_t n_b, const float* images,
+                   size_t n_images, int F, const int32_t* labels, const int32_t* idx, int B, float* error,
+                   float* accuracy, int32_t* correct, int32_t* pred, float* prob);
+
 /* Kardam bookkeeping of CppNNUpdater.update (Server/src/main/java/apps/cppNN/
  * CppNNUpdater.java:463-481, utils/Kardam.java:48-62) for the M
  * picked uploads in one call:
@@ -1022,6 +1062,16 @@ int fleet_model_version_id(fleet_model* m, int version, int64_t* id);
  * text. FLEET_ERR_ARG when the ledger's n_weights, n_biases or graph_edges differ from
  * fleet_model_shape's, or as fleet_model_version_id. */
 int fleet_mledger_stage_model(fleet_mledger* ledger, fleet_model* m, int version, int64_t* id);
+/* fleet_evaluate of models[version] (version -1: cnn), whose vectors are uploaded as the
+ * model's other natives upload theirs: what Evaluator.crossValidation gets from
+ * fetchParamsNative + evaluateNative (Driver/src/main/c++/cppNN_backend.cpp:179-205) of
+ * that version's text. The model must be the MNIST network of :109-115 -- I1 input 28 28 1,
+ * C1 convolution 5 8 1 elu, P1 semi_stochastic_pool 3 3, C2i convolution 1 16 1 elu, C2
+ * convolution 5 48 1 elu, P2 semi_stochastic_pool 2 2, FC2 fully_connected 10 softmax --
+ * or FLEET_ERR_ARG names the first layer that differs, with nothing launched. */
+int fleet_model_evaluate(fleet_model* m, int version, const float* images, size_t n_images, int F,
+                         const int32_t* labels, const int32_t* idx, int B, float* error, float* accuracy,
+                         int32_t* correct, int32_t* pred, float* prob);
 
 /* The same model resident in HBM (fleet_rmodel): `cnn` and every entry of `models`
  * live on the device, so a model step takes a merged gradient that is already there
@@ -1106,6 +1156,20 @@ int fleet_rmodel_stage_mledger(fleet_mledger* ledger, fleet_rmodel* m, int versi
  * device_allocs: every hipMalloc / hipHostMalloc made on the model's behalf so far */
 int fleet_rmodel_stats(fleet_rmodel* m, size_t* resident_bytes, int* device_allocs);
 size_t fleet_rmodel_workspace_bytes(const fleet_rmodel* m);
+/* fleet_model_evaluate of the resident row (fleet_rmodel_version_device's pointers): no
+ * weight crosses PCIe. The device form takes images, labels and indices where they live,
+ * runs on the caller's stream and does not synchronise (an index outside the images:
+ * fleet_check of the model's context); d_pred / d_prob may be NULL. The host form uploads
+ * images, labels and indices and returns synchronised. The B costs and predictions the
+ * caller does not take, and the host form's staging, come from a workspace allocated on
+ * first use, grown only for a larger need and counted in fleet_rmodel_stats; a model's
+ * evaluations must be ordered with each other (they share it). */
+int fleet_rmodel_evaluate_device(fleet_rmodel* m, int version, const void* d_images, size_t n_images, int F,
+                                 const void* d_labels, const void* d_idx, int B, void* d_pred, void* d_prob,
+                                 void* d_result, void* stream);
+int fleet_rmodel_evaluate(fleet_rmodel* m, int version, const float* images, size_t n_images, int F,
+                          const int32_t* labels, const int32_t* idx, int B, float* error, float* accuracy,
+                          int32_t* correct, int32_t* pred, float* prob);
 
 /* The offline sampler's state (the CppNNOfflineSampler natives
  * of Server/src/main/c++/cppNN_backend.cpp and the globals they keep). Random
