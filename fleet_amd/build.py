@@ -77,7 +77,7 @@ def build_codec(force: bool = False, out: str = LIB, defines=()) -> str:
         _run([HIPCC, *lang, *COMMON, *extra, *[f"-D{d}" for d in defines], "-c", src, "-o", obj])
         return obj
 
-    with ThreadPoolExecutor(max_workers=len(srcs)) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(srcs), 16)) as ex:  # at most 16 compilers at once
         objs = list(ex.map(compile_one, srcs))
     tmp = out + ".tmp"
     _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, "-o", tmp])

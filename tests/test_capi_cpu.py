@@ -67,9 +67,10 @@ def test_plan_overrides_validated_on_host():
     """fleet_set_plan is host-only: a spec with an unknown key or value is rejected
     as a whole (the plan stays as it was), a valid one is normalised, "" restores
     the default. No environment variable other than FLEET_EXPERIMENTS (read once)
-    reaches the launch path (no kernel unit, header or fleet_codec.cpp reads another)."""
+    reaches the launch path (no unit of the library and no header reads another)."""
     import glob
     import os
+    from fleet_amd.build import SOURCES
     F.set_plan("")
     for bad in ("update=fast", "k_update=stream", "grid", "stage_pieces=0", "fused=1", "update=stream,tile_mix=off",
                 "update=tiled,tile=weave3", "update=stream,stream_enc=inline", "update=tiled,weave_enc=inline"):
@@ -83,8 +84,9 @@ def test_plan_overrides_validated_on_host():
     csrc = os.path.join(F.ROOT, "fleet_amd", "csrc")
     files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
     assert len(files) >= 10  # the kernel units and their headers are all here
-    src = "".join(open(f).read() for f in files + [os.path.join(csrc, "fleet_codec.cpp"),
-                                                   os.path.join(csrc, "launch_plan.cpp")])
+    units = [os.path.join(csrc, s) for s, _ in SOURCES]  # every unit of the library, host ones included
+    assert {f for f in files if f.endswith(".hip")} <= set(units) and len(units) >= 15
+    src = "".join(open(f).read() for f in sorted(set(files + units)))
     assert src.count("getenv(") == 1 and 'getenv("FLEET_EXPERIMENTS")' in src
     assert 'getenv("FLEET_EXPERIMENTS")' in open(os.path.join(csrc, "launch_plan.cpp")).read()
 
