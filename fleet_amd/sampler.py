@@ -28,6 +28,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
+from ._capi import FleetError, Handle, lib
+
 _libc = None
 
 
@@ -144,17 +146,18 @@ class Teacher:
         return self.codec.teacher_forward(self.w, self.b, self.images, idx, self.TEMPERATURE)
 
 
-class NativeSampler:
+class NativeSampler(Handle):
     """fleet_sampler (include/fleet_codec.h): CppNNOfflineSampler's native state.
 
     ``NativeSampler(codec, data_path=...)`` is initSampler on an MNIST directory;
     ``NativeSampler(codec, images=..., labels=...)`` the same over a dataset in
     memory. ``codec`` may be None for the host state alone (buckets)."""
 
+    _destroy, _closed = "fleet_sampler_destroy", "the sampler is closed"
+
     def __init__(self, codec, data_path: Optional[str] = None, images=None, labels=None, num_labels: int = 10,
                  iid: bool = False, outlier: bool = False, num_clients: int = 10, distillation_mode: int = 1,
                  seed: int = 1):
-        from . import lib, FleetError
         self._L = L = lib()
         self.codec = codec
         h = ctypes.c_void_p()
@@ -172,24 +175,14 @@ class NativeSampler:
             raise FleetError(rc, "fleet_sampler_create failed (see stderr)")
         self._h = h.value
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.fleet_sampler_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
     def _check(self, rc):
         if rc != 0:
-            from . import FleetError
             raise FleetError(rc, self._L.fleet_sampler_last_error(self._h).decode())
 
     @staticmethod
     def reseed_updater(seed: int = 1, fetched: bool = True) -> None:
         """initUpdater's srand(seed) and, after fetchParamsNative (fetched), its
         train_class's two rand() draws."""
-        from . import lib
         lib().fleet_updater_reseed_ex(seed, int(bool(fetched)))
 
     def set_hyper(self, E: int, sigma: float, C: float) -> None:

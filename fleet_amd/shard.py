@@ -23,7 +23,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import b64_count
+from ._capi import b64_count
 
 
 def group_range(groups: int, world: int, rank: int) -> Tuple[int, int]:

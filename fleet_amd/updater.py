@@ -378,7 +378,7 @@ class FleetUpdater:
     def _device_out(self, length: int):
         """The tensors a device-form update writes: the merged text and decodeFloat of it."""
         import torch
-        from . import b64_count
+        from ._capi import b64_count
         groups = (b64_count(length) + 2) // 3
         if self._merged_u8 is None or self._merged_u8.numel() < 16 * groups + 16:
             dev = f"cuda:{self.codec.device}"
@@ -389,7 +389,7 @@ class FleetUpdater:
     def _step_resident(self, length: int) -> bytes:
         """descentNative on the resident model from the merged gradient in HBM; the merged text
         is the one thing copied to the host."""
-        from . import b64_count
+        from ._capi import b64_count
         self.model.descent_device(self._merged_f32, self.stale_size, n_values=b64_count(length))
         self.lr = np.float32(self.model.getLrate())
         return self._merged_u8[:length].cpu().numpy().tobytes()
@@ -520,7 +520,7 @@ class FleetUpdater:
         `true ||`): currModel's norms, one KardamFilter.update for every pick's norms and the
         optimistic result, the Kardam loop with the decision after each pick's updateLip, the
         resolve over what was accepted."""
-        from . import ResidentModel
+        from .model import ResidentModel
         km = self.kardam_models
         n_models = km.modelsSize()
         if self._ledger is None:
