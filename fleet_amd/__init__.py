@@ -26,6 +26,7 @@ from .codec import (ByteVec, Codec, Evaluation, _eval_device_out, _eval_host_arg
 from .streaming import Accumulator, Gate, Pool, Vet, header_codes  # noqa: F401
 from .kardam import KardamFilter, Ledger, ModelLedger  # noqa: F401
 from .model import Model, ResidentModel  # noqa: F401
+from . import client  # noqa: F401  (the client's gradients: fleet_amd.client.client_gradients ...)
 
 
 def __getattr__(name):

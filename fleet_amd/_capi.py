@@ -186,6 +186,13 @@ SIGNATURES = {
     "fleet_model_evaluate": (i32, [vp, i32, vp, sz, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
     "fleet_rmodel_evaluate": (i32, [vp, i32, vp, sz, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
     "fleet_rmodel_evaluate_device": (i32, [vp, i32, vp, sz, i32, vp, vp, i32, vp, vp, vp, vp]),
+    "fleet_client_grad_len": (sz, []),
+    "fleet_client_grad_set_chunk": (i32, [i32]),
+    "fleet_client_grads_device": (i32, [vp, vp, sz, i32, vp, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, vp, sz, vp,
+                                        sz, vp]),
+    "fleet_client_grads": (i32, [vp, vp, sz, vp, sz, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, vp, vp, sz]),
+    "fleet_rmodel_client_grads_device": (i32, [vp, vp, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, vp, sz, vp, sz,
+                                               vp]),
     "fleet_model_load": (i32, [vp, vp, sz, i32, C.POINTER(vp)]),
     "fleet_model_destroy": (None, [vp]),
     "fleet_model_last_error": (C.c_char_p, [vp]),

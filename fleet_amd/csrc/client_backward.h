@@ -1,0 +1,356 @@
+// fleet_amd/csrc/client_backward.h -- the client's gradient computation:
+// what cnn.gradients() returns after B train_class calls on the MNIST network
+// (Client/app/src/main/cpp/cppNN-lib.cpp:101-113, 218-234; commonLib/cppNN/network.h:1806-2008
+// train_class, :1551-1611 backward_hidden, :1289-1331 sync_mini_batch, :1038-1056 gradients()),
+// host + device on eval_forward.h's pattern over teacher_math.h: client_kernels.hip runs
+// sample_stages() with one block per sample and grad_element() with one lane per element,
+// client_grad_host() below runs the same two functions in plain loops, and
+// tests/native/check_client_grad.cpp checks the latter against the reference's recorded bits,
+// intermediates included.
+//
+// The reference's 8 pthreads race on batch_index++ and rand(); this restates the single-thread
+// order (sample k of the call takes batch slot k) with the cross_entropy cost. The reference is
+// built -O0 without MOJO_AVX or NEON, so layer.h's and core_math.h's plain-C branches run: one
+// binary32 rounding per operation, no contraction, every sum in the order written there.
+//
+// Per sample (network.h:1806-2008):
+//   shift    m.shift(dx, dy, mojo::edge) (:1840, core_math.h:721-731): pad by replication and
+//            crop, out[y][x] = in[clamp(y - dy)][clamp(x - dx)]
+//   forward  forward(input, temperature, thread, 1) (:1857-1861): teacher.hip's arithmetic,
+//            documented at its head, with both pools' picks kept as p_map (layer.h:481-556;
+//            r = 34909 % 100 = 9, so the second candidate wins where (int)(100*max/(max+max2)) < 9)
+//   delta    FC2: 1.f * (node[j] - target[j]), target one-hot, all zeros for a label outside
+//            [0, 10) (:1896-1903, :1949); E = the mean of mse::cost (:1974-1982), NaN is `bail`
+//   pass 1   (:1561-1578) from FC2 down: delta[i] *= df(node, i) below the last layer, then
+//            distribute_delta into the layer above.
+//            df: elu reads the ACTIVATED node, node > 0 ? 1.f : 0.1f*expf(node) (activation.h:180);
+//            the pools have no p_act and the input layer's is identity: df = 1.f, and x * 1.f is
+//            x for every x that is no NaN, so those products are not written out.
+//            FC2 -> P2  (layer.h:244-255): per t, from 0, b in order: += delta[b] * w[t + b*192]
+//            P2 -> C2, P1 -> C1 (layer.h:461-466): top.delta[p_map[k]] += delta[k]; windows do not
+//                       overlap, so an element receives 0.f + delta[k] (-0 becomes +0) or stays 0.f
+//            C2 -> C2i, C1 -> I1 (layer.h:941-998, the #else arm): delta padded by 4 with zeros,
+//                       unwrap_aligned_NxN(5) and dotsum_unwrapped_5x5 into the top delta: per
+//                       element one running sum from 0, map outer, tap i = row*5 + col inner,
+//                       += pad[map][y + row][x + col] * w[(k*maps + map)*25 + 24 - i]
+//            C2i -> P1  (layer.h:1074-1096): per element, maps in order,
+//                       += delta[map][p] * w[map + k*16]
+//   pass 2   (:1587-1603) calculate_dw per edge, dbias = the layer's delta for every layer that
+//            is no convolution (I1 784, P1 512, P2 192, FC2 10)
+//            FC2 (layer.h:276-302): dw[t + b*192] = node_P2[t] * delta[b], a bare product (-0 stays)
+//            C2, C1 (layer.h:1148-1193): dw.fill(0), then += unwrap_2d_dot(top + tap, delta, n,
+//                       top_n, n): v = 0; per row j: v += dot(row). dot (core_math.h:58-72) is the
+//                       unrolled ((p0 + p1) + p2) + p3 for C2's 4-term rows and the loop from
+//                       v = 0 for C1's 24-term rows. Every element is 0.f + v (-0 becomes +0).
+//            C2i (layer.h:1219-1236): the generic branch, kernel 1: unwrap_2d_dot of size 8,
+//                       rows by the loop from 0
+// Across samples (network.h:1289-1331, 1038-1056): dW_sets[0] += dW_sets[b], b = 1 .. B-1 in
+// order per element, the same for dbias_sets, laid out [nW, (size, vals)*, nB, (size, vals)*]
+// in fleet_amd/layouts.py MNIST's order, 22961 values.
+//
+// Convolution deltas live in channel-aligned matrices (layer.h:771); every map here (576, 16
+// values) is a multiple of 8, so chan_stride == cols*rows and nothing is padded between maps.
+//
+// NaN: bit-identical to the reference whenever no intermediate is NaN. A NaN in the forward
+// output makes E NaN (the reference bails): sample_stages reports it and the output is
+// unspecified. With a NaN met only in the backward pass, positions and bits are unpinned.
+#pragma once
+#include <stdint.h>
+
+#include "eval_forward.h"
+#include "teacher_math.h"
+
+namespace fleet {
+namespace clientnet {
+
+using namespace evalnet;  // the network's sizes and the weight / bias offsets
+
+constexpr int kC1Out = kMaps1 * kC1 * kC1;      // 4608
+constexpr int kC2Out = kMaps2 * kC2 * kC2;      // 768
+constexpr int kC1Pad = kC1 + 8, kC2Pad = kC2 + 8;  // a 5x5 layer's delta padded by 4 on every side
+constexpr int kC1PadOut = kMaps1 * kC1Pad * kC1Pad;  // 8192
+constexpr int kC2PadOut = kMaps2 * kC2Pad * kC2Pad;  // 6912
+
+// gradients(): [6, 200, C1, 0, 128, C2i, 19200, C2, 0, 1920, FC2, 7, 784, I1, 0, 512, P1, 0, 0, 192, P2, 10, FC2]
+constexpr int kGradLen = 22961;
+constexpr int kG_W1 = 2, kG_W2i = kG_W1 + 200 + 2, kG_W2 = kG_W2i + 128 + 1, kG_Wfc = kG_W2 + 19200 + 2;
+constexpr int kG_nB = kG_Wfc + 1920;  // 21455
+constexpr int kG_BI1 = kG_nB + 2, kG_BP1 = kG_BI1 + kPix + 2, kG_BP2 = kG_BP1 + kP1Out + 3, kG_Bfc = kG_BP2 + kFcIn + 1;
+static_assert(kG_Bfc + kClasses == kGradLen, "gradients() layout");
+constexpr int kHeaders = 15;
+struct Header {
+  int pos;
+  float value;
+};
+#define FLEET_CLIENT_HEADERS                                                                                  \
+  {{0, 6.f}, {1, 200.f}, {kG_W2i - 2, 0.f}, {kG_W2i - 1, 128.f}, {kG_W2 - 1, 19200.f}, {kG_Wfc - 2, 0.f},     \
+   {kG_Wfc - 1, 1920.f}, {kG_nB, 7.f}, {kG_BI1 - 1, 784.f}, {kG_BP1 - 2, 0.f}, {kG_BP1 - 1, 512.f},           \
+   {kG_BP2 - 3, 0.f}, {kG_BP2 - 2, 0.f}, {kG_BP2 - 1, 192.f}, {kG_Bfc - 1, 10.f}}
+
+// One sample's layers: nodes, both pools' p_map (indices into the layer above) and deltas;
+// the deltas of C1 and C2 are kept padded by 4 with zeros, as distribute_delta pads them
+// (104 KB: the block's LDS in client_kernels.hip).
+struct Sample {
+  float in[kPix], c1[kC1Out], p1[kP1Out], c2i[kC2iOut], c2[kC2Out], p2[kFcIn], fc[kClasses];
+  int32_t pm1[kP1Out], pm2[kFcIn];
+  float d_in[kPix], d_c1[kC1PadOut], d_p1[kP1Out], d_c2i[kC2iOut], d_c2[kC2PadOut], d_p2[kFcIn], d_fc[kClasses];
+  float E;
+};
+
+// semi_stochastic_pooling_layer::accumulate_signal (layer.h:481-556) for window o of a
+// P x P, stride P pool over top [maps][size][size] in a training forward: the picked index
+FLEET_TM int32_t pool_pick(const float* top, int size, int P, int o) {
+  const int n = size / P, k = o / (n * n), j = P * ((o / n) % n), i = P * (o % n);
+  const int base = i + j * size + k * size * size;
+  int mi = base, mi2 = base;
+  float mx = top[base], mx2 = mx;
+  for (int jj = 0; jj < P; ++jj)
+    for (int ii = 0; ii < P; ++ii) {
+      const int index = base + ii + jj * size;
+      const float v = top[index];
+      if (mx < v) {
+        mx2 = mx, mi2 = mi;
+        mx = v, mi = index;
+      } else if (mx2 < v) {
+        mx2 = v, mi2 = index;
+      }
+    }
+  if (mx + mx2 == 0.0f) return mi;
+  const int32_t t1 = mojo_cvtt(100.0f * mx / (mx + mx2));
+  return 9 <= t1 ? mi : mi2;
+}
+
+// elu::df on the activated node (activation.h:180)
+FLEET_TM float elu_df(float node) { return node > 0.0f ? 1.0f : 0.1f * mojo_expf(node); }
+
+// C1 node o = map*576 + y*24 + x
+FLEET_TM float c1_node(const float* in, const float* w1, const float* b1, int o) {
+  const int map = o / (kC1 * kC1), y = (o / kC1) % kC1, x = o % kC1;
+  const float* wm = w1 + map * 25;
+  const float acc = mojo_sum([&](auto mac) {
+    float a = 0.0f;
+    for (int i = 0; i < 25; ++i) a = mac(a, in[(y + i / 5) * kIn + x + i % 5], wm[i]);
+    return a;
+  });
+  return mojo_elu(acc, b1[map]);
+}
+
+// C2 node o = map*16 + y*4 + x: channel outer, tap inner
+FLEET_TM float c2_node(const float* c2i_all, const float* w2, const float* b2, int o) {
+  const int map = o / (kC2 * kC2), y = (o / kC2) % kC2, x = o % kC2;
+  const float acc = mojo_sum([&](auto mac) {
+    float a = 0.0f;
+    for (int k = 0; k < kMaps2i; ++k) {
+      const float* wm = w2 + (k * kMaps2 + map) * 25;
+      const float* src = c2i_all + k * kP1 * kP1;
+      for (int i = 0; i < 25; ++i) a = mac(a, src[(y + i / 5) * kP1 + x + i % 5], wm[i]);
+    }
+    return a;
+  });
+  return mojo_elu(acc, b2[map]);
+}
+
+// softmax::fc with temperature (activation.h:271-313), teacher.hip's restatement
+FLEET_TM void softmax10(float* node, float temperature) {
+  float in[kClasses];
+  for (int j = 0; j < kClasses; ++j) in[j] = node[j];
+  float mx = in[0];
+  for (int j = 1; j < kClasses; ++j)
+    if (in[j] > mx) mx = mojo_div(in[j], temperature);
+  float denom = 0.0f;
+  for (int j = 0; j < kClasses; ++j) denom = mojo_add(denom, mojo_expf(mojo_sub(mojo_div(in[j], temperature), mx)));
+  for (int j = 0; j < kClasses; ++j) node[j] = mojo_div(mojo_expf(mojo_sub(mojo_div(in[j], temperature), mx)), denom);
+}
+
+// the output delta and E (network.h:1896-1903, 1945-1982); mse::cost is (0.5f*d)*d (cost.h:49-51)
+FLEET_TM float out_delta(const float* node, int32_t label, float* delta) {
+  float E = 0.0f;
+  for (int j = 0; j < kClasses; ++j) {
+    const float target = (label >= 0 && label < kClasses && j == label) ? 1.0f : 0.0f;
+    const float d = node[j] - target;
+    delta[j] = 1.0f * d;
+    E += (0.5f * d) * d;
+  }
+  return E / (float)kClasses;
+}
+
+// a pool's delta scattered through its p_map into element o of the convolution above it,
+// then that layer's elu df: window `win` is the one o lies in
+FLEET_TM float unpool_df(const float* pool_delta, const int32_t* pmap, int win, int o, float node) {
+  const float d = pmap[win] == o ? 0.0f + pool_delta[win] : 0.0f;
+  return d * elu_df(node);
+}
+
+// 5x5 distribute_delta: element (k, y, x) of the layer above from the padded delta
+// pad [maps][n + 8][n + 8] (n x n the convolution's own map) and the weights w of this edge
+FLEET_TM float conv5_back(const float* pad, const float* w, int maps, int padn, int k, int y, int x) {
+  float a = 0.0f;
+  for (int map = 0; map < maps; ++map) {
+    const float* p = pad + map * padn * padn + y * padn + x;
+    const float* wm = w + (k * maps + map) * 25;
+    for (int i = 0; i < 25; ++i) a = a + p[(i / 5) * padn + i % 5] * wm[24 - i];
+  }
+  return a;
+}
+
+// unwrap_2d_dot (core_math.h:74-81) with dot's loop form (sizes above 5): v = 0, per row
+// v += (d = 0; d += x1[i]*x2[i])
+FLEET_TM float dot2d_loop(const float* x1, const float* x2, int size, int stride1, int stride2) {
+  float v = 0.0f;
+  for (int j = 0; j < size; ++j) {
+    float d = 0.0f;
+    for (int i = 0; i < size; ++i) d = d + x1[stride1 * j + i] * x2[stride2 * j + i];
+    v = v + d;
+  }
+  return v;
+}
+
+// the same with dot's unrolled `case 4`
+FLEET_TM float dot2d_4(const float* x1, const float* x2, int stride1, int stride2) {
+  float v = 0.0f;
+  for (int j = 0; j < 4; ++j) {
+    const float* a = x1 + stride1 * j;
+    const float* b = x2 + stride2 * j;
+    v = v + (a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]);
+  }
+  return v;
+}
+
+// One sample, every stage in the reference's order. `par(n, f)` runs f(o) for o in [0, n) and
+// returns once all of them are done (the block's lanes and a barrier in the kernel, a loop on
+// the host). row: the sample's gradients() vector [kGradLen], dW and dbias of this sample alone.
+// image: the unshifted sample [784]. Returns false where E is NaN (the reference's bail).
+template <class Par>
+FLEET_TM bool sample_stages(Par par, Sample& S, const float* w, const float* b, const float* image, int32_t label,
+                            int dx, int dy, float temperature, float* row) {
+  // shift
+  par(kPix, [&](int o) {
+    int y = o / kIn - dy, x = o % kIn - dx;
+    y = y < 0 ? 0 : (y > kIn - 1 ? kIn - 1 : y);
+    x = x < 0 ? 0 : (x > kIn - 1 ? kIn - 1 : x);
+    S.in[o] = image[y * kIn + x];
+  });
+  // forward, train mode
+  par(kC1Out, [&](int o) { S.c1[o] = c1_node(S.in, w + kW1, b + kB1, o); });
+  par(kP1Out, [&](int o) {
+    S.pm1[o] = pool_pick(S.c1, kC1, 3, o);
+    S.p1[o] = S.c1[S.pm1[o]];
+  });
+  par(kC2iOut, [&](int o) { S.c2i[o] = c2i(S.p1, w + kW2i, b + kB2i, o); });
+  par(kC2Out, [&](int o) { S.c2[o] = c2_node(S.c2i, w + kW2, b + kB2, o); });
+  par(kFcIn, [&](int o) {
+    S.pm2[o] = pool_pick(S.c2, kC2, 2, o);
+    S.p2[o] = S.c2[S.pm2[o]];
+  });
+  par(kClasses, [&](int o) { S.fc[o] = fc(S.p2, w + kWfc + o * kFcIn); });
+  par(1, [&](int) {
+    softmax10(S.fc, temperature);
+    S.E = out_delta(S.fc, label, S.d_fc);
+  });
+  // pass 1: FC2 -> P2
+  par(kFcIn, [&](int t) {
+    float a = 0.0f;
+    for (int j = 0; j < kClasses; ++j) a = a + S.d_fc[j] * w[kWfc + j * kFcIn + t];
+    S.d_p2[t] = a;
+  });
+  // P2 -> C2 and C2's df, into the padded delta
+  par(kC2PadOut, [&](int q) {
+    const int map = q / (kC2Pad * kC2Pad), y = (q / kC2Pad) % kC2Pad - 4, x = q % kC2Pad - 4;
+    float d = 0.0f;
+    if (y >= 0 && y < kC2 && x >= 0 && x < kC2) {
+      const int o = map * kC2 * kC2 + y * kC2 + x;
+      d = unpool_df(S.d_p2, S.pm2, map * 4 + (y / 2) * 2 + x / 2, o, S.c2[o]);
+    }
+    S.d_c2[q] = d;
+  });
+  // C2 -> C2i (5x5) and C2i's df
+  par(kC2iOut, [&](int o) {
+    const int k = o / (kP1 * kP1), y = (o / kP1) % kP1, x = o % kP1;
+    S.d_c2i[o] = conv5_back(S.d_c2, w + kW2, kMaps2, kC2Pad, k, y, x) * elu_df(S.c2i[o]);
+  });
+  // C2i -> P1 (1x1)
+  par(kP1Out, [&](int o) {
+    const int k = o / (kP1 * kP1), p = o % (kP1 * kP1);
+    float a = 0.0f;
+    for (int map = 0; map < kMaps2i; ++map) a = a + S.d_c2i[map * kP1 * kP1 + p] * w[kW2i + map + k * kMaps2i];
+    S.d_p1[o] = a;
+  });
+  // P1 -> C1 and C1's df, into the padded delta
+  par(kC1PadOut, [&](int q) {
+    const int map = q / (kC1Pad * kC1Pad), y = (q / kC1Pad) % kC1Pad - 4, x = q % kC1Pad - 4;
+    float d = 0.0f;
+    if (y >= 0 && y < kC1 && x >= 0 && x < kC1) {
+      const int o = map * kC1 * kC1 + y * kC1 + x;
+      d = unpool_df(S.d_p1, S.pm1, map * kP1 * kP1 + (y / 3) * kP1 + x / 3, o, S.c1[o]);
+    }
+    S.d_c1[q] = d;
+  });
+  // C1 -> I1 (5x5)
+  par(kPix, [&](int o) { S.d_in[o] = conv5_back(S.d_c1, w + kW1, kMaps1, kC1Pad, 0, o / kIn, o % kIn); });
+  // pass 2: dW per edge and dbias per layer, with the layout's header values
+  par(kHeaders, [&](int o) {
+    constexpr Header h[kHeaders] = FLEET_CLIENT_HEADERS;
+    row[h[o].pos] = h[o].value;
+  });
+  par(kClasses * kFcIn, [&](int o) { row[kG_Wfc + o] = S.p2[o % kFcIn] * S.d_fc[o / kFcIn]; });
+  par(kMaps2 * kMaps2i * 25, [&](int o) {
+    const int tap = o % 25, mk = o / 25, map = mk % kMaps2, k = mk / kMaps2;
+    const float* top = S.c2i + k * kP1 * kP1 + (tap / 5) * kP1 + tap % 5;
+    const float* delta = S.d_c2 + map * kC2Pad * kC2Pad + 4 * kC2Pad + 4;
+    row[kG_W2 + o] = 0.0f + dot2d_4(top, delta, kP1, kC2Pad);
+  });
+  par(kMaps1 * 25, [&](int o) {
+    const int tap = o % 25, map = o / 25;
+    const float* top = S.in + (tap / 5) * kIn + tap % 5;
+    const float* delta = S.d_c1 + map * kC1Pad * kC1Pad + 4 * kC1Pad + 4;
+    row[kG_W1 + o] = 0.0f + dot2d_loop(top, delta, kC1, kIn, kC1Pad);
+  });
+  par(kMaps2i * kMaps1, [&](int o) {
+    const int map = o % kMaps2i, k = o / kMaps2i;
+    row[kG_W2i + o] = 0.0f + dot2d_loop(S.p1 + k * kP1 * kP1, S.d_c2i + map * kP1 * kP1, kP1, kP1, kP1);
+  });
+  par(kPix, [&](int o) { row[kG_BI1 + o] = S.d_in[o]; });
+  par(kP1Out, [&](int o) { row[kG_BP1 + o] = S.d_p1[o]; });
+  par(kFcIn, [&](int o) { row[kG_BP2 + o] = S.d_p2[o]; });
+  par(kClasses, [&](int o) { row[kG_Bfc + o] = S.d_fc[o]; });
+  return S.E == S.E;
+}
+
+// sync_mini_batch + gradients(): element e of the call's vector from the B per-sample rows
+// (row k at rows + k*pitch), added in sample order in binary32; header values pass through
+FLEET_TM float grad_element(const float* rows, int64_t pitch, int B, int e) {
+  constexpr Header h[kHeaders] = FLEET_CLIENT_HEADERS;
+  for (int i = 0; i < kHeaders; ++i)
+    if (h[i].pos == e) return h[i].value;
+  float a = rows[e];
+  for (int k = 1; k < B; ++k) a = a + rows[(int64_t)k * pitch + e];
+  return a;
+}
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+struct HostPar {
+  template <class F>
+  void operator()(int n, F f) const {
+    for (int o = 0; o < n; ++o) f(o);
+  }
+};
+
+// One client's call in plain loops: images [B][784] (already gathered), labels [B], shifts
+// [B][2] or NULL, out [kGradLen]. rows: scratch [B][kGradLen]. keep: the B samples' layers, or
+// NULL. Returns the number of samples whose E is NaN.
+inline int client_grad_host(const float* w, const float* b, const float* images, const int32_t* labels,
+                            const int32_t* shifts, int B, float temperature, float* rows, float* out, Sample* keep) {
+  Sample* S = keep ? nullptr : new Sample;
+  int blown = 0;
+  for (int k = 0; k < B; ++k)
+    blown += !sample_stages(HostPar{}, keep ? keep[k] : *S, w, b, images + (int64_t)k * kPix, labels[k],
+                            shifts ? shifts[2 * k] : 0, shifts ? shifts[2 * k + 1] : 0, temperature,
+                            rows + (int64_t)k * kGradLen);
+  for (int e = 0; e < kGradLen; ++e) out[e] = grad_element(rows, kGradLen, B, e);
+  delete S;
+  return blown;
+}
+#endif
+
+}  // namespace clientnet
+}  // namespace fleet

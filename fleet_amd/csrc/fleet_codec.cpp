@@ -146,6 +146,10 @@ struct fleet_ctx {
   // (a grown buffer is retired, not freed: an evaluation on another stream may still write it)
   uint8_t* d_eval = nullptr;
   int d_eval_cap = 0;  // the B it holds
+  // fleet_client_grads_device: the per-sample gradient rows of one chunk of clients (retired, not
+  // freed, when it grows, for the same reason)
+  float* d_client_ws = nullptr;
+  size_t d_client_ws_cap = 0;  // bytes
 };
 
 namespace {
@@ -257,6 +261,8 @@ int read_err(fleet_ctx* c, hipStream_t s, int* d_errbuf = nullptr) {
   if (e & 2) return fail(c, FLEET_ERR_LAYOUT, "uploads disagree on the gradient layout header slots");
   if (e & 4) return fail(c, FLEET_ERR_ARG, "sample index outside the dataset");
   if (e & 8) return fail(c, FLEET_ERR_HIP, "a cross-block hand-off timed out (Kardam reduce blocks)");
+  if (e & FLEET_ERRBIT_NAN)
+    return fail(c, FLEET_ERR_ARG, "network blew up: a client sample's E is NaN (train_class's bail)");
   return FLEET_OK;
 }
 
@@ -480,7 +486,8 @@ void fleet_destroy(fleet_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (void* p : {(void*)c->d_a, (void*)c->d_b, (void*)c->d_out, (void*)c->d_f32, (void*)c->d_dampen,
                   (void*)c->d_hdr, (void*)c->d_err, (void*)c->d_partials, (void*)c->d_dev_dampen,
-                  (void*)c->d_dev_hdr, (void*)c->d_dev_err, (void*)c->d_kflags, (void*)c->d_eval})
+                  (void*)c->d_dev_hdr, (void*)c->d_dev_err, (void*)c->d_kflags, (void*)c->d_eval,
+                  (void*)c->d_client_ws})
     if (p) (void)hipFree(p);
   for (void* p : c->retired) (void)hipFree(p);
   for (void* p : {(void*)c->h_stage, (void*)c->h_hdr, (void*)c->h_err})
@@ -1704,6 +1711,109 @@ int fleet_evaluate(fleet_ctx* c, const float* w, size_t n_w, const float* b, siz
     if (correct) std::memcpy(correct, &res[2], 4);
   }
   return FLEET_OK;
+}
+
+// ------------------------------------------ the client's getGradients (client_kernels.hip)
+
+size_t fleet_client_grad_len(void) { return (size_t)fleet::client_grad_len(); }
+int fleet_client_grad_set_chunk(int max_clients) { return fleet::client_grad_set_chunk(max_clients); }
+
+// Client/app/src/main/cpp/cppNN-lib.cpp:101-113, 218-234; commonLib/cppNN/network.h:1806-2008,
+// 1551-1611, 1289-1331, 1038-1056
+namespace {
+
+// both forms, the lock held and the device set: the workspace, the two launches per chunk of
+// clients, the encode of the rows; err: the error word the kernels report to
+int client_grads_locked(fleet_ctx* c, const void* d_models, size_t model_pitch, int n_models,
+                        const void* d_model_of_client, const void* d_images, size_t n_images, int F,
+                        const void* d_labels, const void* d_idx, const void* d_shift, int C, int B, float temperature,
+                        void* d_grads, size_t grad_pitch, void* d_uploads, size_t upload_pitch, hipStream_t s) {
+  const size_t n_up = fleet_client_grad_len();
+  const int chunk = fleet::client_grad_chunk(C, B);
+  const size_t need = fleet::client_grad_workspace_bytes(chunk, B);
+  if (need > c->d_client_ws_cap) {
+    if (c->d_client_ws) c->retired.push_back(c->d_client_ws);
+    c->d_client_ws = nullptr;
+    c->d_client_ws_cap = 0;
+    const hipError_t e = hipMalloc((void**)&c->d_client_ws, need + 64);
+    if (e != hipSuccess) return fail(c, FLEET_ERR_NOMEM, "hipMalloc(%zu): %s", need, hipGetErrorString(e));
+    c->d_client_ws_cap = need;
+  }
+  HIP_TRY(c, fleet::launch_client_grads((const float*)d_models, (int64_t)model_pitch, n_models,
+                                        (const int32_t*)d_model_of_client, (const float*)d_images, (int64_t)n_images, F,
+                                        (const int32_t*)d_labels, (const int32_t*)d_idx, (const int32_t*)d_shift, C, B,
+                                        chunk, temperature, c->d_client_ws, (float*)d_grads, (int64_t)grad_pitch,
+                                        c->d_dev_err, s));
+  if (d_uploads)
+    HIP_TRY(c, fleet::launch_encode_f32((const float*)d_grads, (int64_t)n_up, grad_pitch, C, (uint8_t*)d_uploads,
+                                        upload_pitch, s));
+  return FLEET_OK;
+}
+
+}  // namespace
+
+int fleet_client_grads_device(fleet_ctx* c, const void* d_models, size_t model_pitch, int n_models,
+                              const void* d_model_of_client, const void* d_images, size_t n_images, int F,
+                              const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
+                              float temperature, void* d_grads, size_t grad_pitch, void* d_uploads,
+                              size_t upload_pitch, void* stream) {
+  const size_t n_up = fleet_client_grad_len();
+  if (!c || !d_models || !d_images || !d_labels || !d_grads || C <= 0 || B <= 0 || F < 28 * 28 || n_models <= 0 ||
+      n_images == 0 || model_pitch < fleet_teacher_weight_count() + fleet_teacher_bias_count() || grad_pitch < n_up ||
+      (size_t)C * (size_t)B > (size_t)INT32_MAX || (!d_idx && (size_t)C * (size_t)B > n_images))
+    return FLEET_ERR_ARG;
+  if (d_uploads && (upload_pitch % 16 != 0 || upload_pitch < 16 * groups_of(n_up)))
+    return fail(c, FLEET_ERR_ARG, "bad upload pitch");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  return client_grads_locked(c, d_models, model_pitch, n_models, d_model_of_client, d_images, n_images, F, d_labels, d_idx,
+                             d_shift, C, B, temperature, d_grads, grad_pitch, d_uploads, upload_pitch, pick(c, stream));
+}
+
+int fleet_client_grads(fleet_ctx* c, const float* w, size_t n_w, const float* b, size_t n_b, const float* images,
+                       size_t n_images, int F, const int32_t* labels, const int32_t* idx, const int32_t* shifts, int C,
+                       int B, float temperature, float* grads, char* uploads, size_t upload_pitch) {
+  if (!c || !w || !b || !images || !labels || !grads || C <= 0 || B <= 0 || F < 28 * 28 || n_images == 0)
+    return FLEET_ERR_ARG;
+  if (n_w != fleet_teacher_weight_count() || n_b != fleet_teacher_bias_count())
+    return fail(c, FLEET_ERR_ARG, "client gradients: %zu weights and %zu biases, expected %zu and %zu", n_w, n_b,
+                fleet_teacher_weight_count(), fleet_teacher_bias_count());
+  const size_t n = (size_t)C * (size_t)B, n_up = fleet_client_grad_len();
+  if (n > (size_t)INT32_MAX) return fail(c, FLEET_ERR_ARG, "client gradients: %d clients of %d samples", C, B);
+  if (!idx && n > n_images) return fail(c, FLEET_ERR_ARG, "client gradients: %zu images asked of %zu", n, n_images);
+  for (size_t i = 0; idx && i < n; ++i)
+    if (idx[i] < 0 || (size_t)idx[i] >= n_images)
+      return fail(c, FLEET_ERR_ARG, "sample %zu: index %d outside the %zu images", i, idx[i], n_images);
+  for (size_t i = 0; shifts && i < 2 * n; ++i)
+    if (shifts[i] < -1 || shifts[i] > 1)
+      return fail(c, FLEET_ERR_ARG, "sample %zu: shift %d outside {-1, 0, 1}", i / 2, shifts[i]);
+  const size_t up_len = fleet_b64_len(n_up), groups_bytes = 16 * groups_of(n_up);
+  if (uploads && upload_pitch < up_len) return fail(c, FLEET_ERR_CAPACITY, "upload pitch %zu < %zu", upload_pitch, up_len);
+  const size_t rows = idx ? n_images : n;  // the images the call reads
+  const size_t o_x = round16(sizeof(float) * (n_w + n_b)), o_l = o_x + round16(sizeof(float) * rows * (size_t)F);
+  const size_t o_i = o_l + round16(4 * rows), o_s = o_i + round16(4 * n), o_g = o_s + round16(8 * n);
+  const size_t o_u = o_g + round16(sizeof(float) * (size_t)C * n_up), o_end = o_u + (uploads ? (size_t)C * groups_bytes : 0);
+  int rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  if ((rc = grow_dev(c, &c->d_a, &c->d_a_cap, o_end))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  uint8_t* d = c->d_a;
+  HIP_TRY(c, hipMemcpyAsync(d, w, sizeof(float) * n_w, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(d + sizeof(float) * n_w, b, sizeof(float) * n_b, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(d + o_x, images, sizeof(float) * rows * (size_t)F, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(d + o_l, labels, 4 * rows, hipMemcpyHostToDevice, c->stream));
+  if (idx) HIP_TRY(c, hipMemcpyAsync(d + o_i, idx, 4 * n, hipMemcpyHostToDevice, c->stream));
+  if (shifts) HIP_TRY(c, hipMemcpyAsync(d + o_s, shifts, 8 * n, hipMemcpyHostToDevice, c->stream));
+  if ((rc = client_grads_locked(c, d, n_w + n_b, 1, nullptr, d + o_x, rows, F, d + o_l, idx ? d + o_i : nullptr,
+                                shifts ? d + o_s : nullptr, C, B, temperature, d + o_g, n_up, uploads ? d + o_u : nullptr,
+                                groups_bytes, c->stream)))
+    return rc;
+  HIP_TRY(c, hipMemcpyAsync(grads, d + o_g, sizeof(float) * (size_t)C * n_up, hipMemcpyDeviceToHost, c->stream));
+  if (uploads)
+    HIP_TRY(c, hipMemcpy2DAsync(uploads, upload_pitch, d + o_u, groups_bytes, up_len, (size_t)C, hipMemcpyDeviceToHost,
+                                c->stream));
+  return read_err(c, c->stream, c->d_dev_err);
 }
 
 int fleet_model_params(fleet_ctx* c, const float* weights, size_t n_weights, const float* biases, size_t n_biases,

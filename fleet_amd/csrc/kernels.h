@@ -14,6 +14,7 @@
 #define FLEET_ERRBIT_LAYOUT 2
 #define FLEET_ERRBIT_ARG 4
 #define FLEET_ERRBIT_SYNC 8  // a cross-block hand-off timed out (Kardam reduce blocks)
+#define FLEET_ERRBIT_NAN 16  // a client sample's E is NaN (train_class's bail, network.h:1984)
 
 namespace fleet {
 
@@ -199,6 +200,19 @@ hipError_t launch_eval(const float* w, const float* b, const float* images, int6
                        float* probs10, float* result, int* err, hipStream_t s);
 int eval_block_images();
 int eval_set_grid(int max_blocks);  // 0: three blocks per CU; returns the previous value
+// the client's getGradients (client_kernels.hip): per client c of C its gradients() vector over
+// samples idx[c*B + k] (idx == nullptr: images c*B + k) under shift[c*B + k] = {dx, dy} (nullptr:
+// none) on model row model_of_client[c] (nullptr: row 0) of models (rows of model_pitch floats,
+// w then b), into grads (rows of grad_pitch floats), `chunk` clients at a time. workspace:
+// client_grad_workspace_bytes(chunk, B).
+hipError_t launch_client_grads(const float* models, int64_t model_pitch, int n_models, const int32_t* model_of_client,
+                               const float* images, int64_t n_images, int F, const int32_t* labels, const int32_t* idx,
+                               const int32_t* shift, int C, int B, int chunk, float temperature, float* workspace,
+                               float* grads, int64_t grad_pitch, int* err, hipStream_t s);
+int64_t client_grad_len();  // 22961
+size_t client_grad_workspace_bytes(int chunk, int B);
+int client_grad_chunk(int C, int B);
+int client_grad_set_chunk(int max_clients);  // 0: what fits the workspace cap; returns the previous value
 hipError_t launch_encode_model_params(const float* weights, int64_t n_w, const float* biases, int64_t n_b, int64_t reps,
                                       uint8_t* out, hipStream_t s);
 hipError_t launch_encode_i32(const int32_t* codes, int64_t n, uint8_t* out, hipStream_t s);

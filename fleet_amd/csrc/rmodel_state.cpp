@@ -55,6 +55,8 @@ struct fleet_rmodel {
   int solver = 0;
   bool stepped = false;
   size_t gtext_cap = 0, grad_cap = 0;
+  int32_t* d_client_rows = nullptr;  // client gradients: the row of every client's version
+  int client_rows_cap = 0;
   uint8_t* eval_ws = nullptr;  // evaluation: [B costs | B predictions | B p | result | staged images, labels, indices]
   size_t eval_cap = 0;
   int* h_pin = nullptr;  // pinned: [0] the error word's copy, [4..] the counts line
@@ -195,7 +197,8 @@ void release(fleet_rmodel* m) {
     DeviceScope sc(m->device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
     for (void* p : {(void*)m->state, (void*)m->tab, (void*)m->work, (void*)m->text, (void*)m->a20, (void*)m->gtext,
-                    (void*)m->grad, (void*)m->sstate, (void*)m->eval_ws})
+                    (void*)m->grad, (void*)m->sstate, (void*)m->eval_ws,
+                    (void*)m->d_client_rows})
       if (p) (void)hipFree(p);
     if (m->h_pin) (void)hipHostFree(m->h_pin);
     if (m->stream) (void)hipStreamDestroy(m->stream);
@@ -776,6 +779,46 @@ int fleet_rmodel_evaluate(fleet_rmodel* m, int version, const float* images, siz
   if (error) *error = res[0];
   if (accuracy) *accuracy = res[1];
   if (correct) std::memcpy(correct, &res[2], 4);
+  return FLEET_OK;
+}
+
+int fleet_rmodel_client_grads_device(fleet_rmodel* m, const int32_t* versions, const void* d_images, size_t n_images,
+                                     int F, const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
+                                     float temperature, void* d_grads, size_t grad_pitch, void* d_uploads,
+                                     size_t upload_pitch, void* stream) {
+  if (!m) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  RM_SCOPE(m);
+  if (!versions || !d_images || !d_labels || !d_grads || C <= 0 || B <= 0 || F < 28 * 28 || n_images == 0)
+    return rfail(m, FLEET_ERR_ARG, "client gradients: versions, images, labels and rows, C >= 1, B >= 1, F >= 784");
+  std::string why;
+  if (fleet::eval_check_mnist(m->host, &why)) return rfail(m, FLEET_ERR_ARG, "client gradients: %s", why.c_str());
+  std::vector<int32_t> rows((size_t)C, 0);
+  int rc, n_rows = 1;
+  for (int c = 0; c < C; ++c) {
+    int row = 0;
+    if (versions[c] >= 0 && (rc = version_row(m, versions[c], &row))) return rc;
+    rows[(size_t)c] = row;
+    n_rows = std::max(n_rows, row + 1);
+  }
+  hipStream_t s = caller_stream(stream);
+  if (C > m->client_rows_cap) {
+    if (m->d_client_rows) {  // (a call on another stream may still read the old one)
+      RM_HIP(m, hipDeviceSynchronize());
+      (void)hipFree(m->d_client_rows);
+    }
+    m->d_client_rows = nullptr;
+    m->client_rows_cap = 0;
+    if ((rc = dev_alloc(m, &m->d_client_rows, 4 * (size_t)C))) return rc;
+    m->client_rows_cap = C;
+  }
+  // pageable source: the copy has left `rows` when the call returns
+  RM_HIP(m, hipMemcpyAsync(m->d_client_rows, rows.data(), 4 * (size_t)C, hipMemcpyHostToDevice, s));
+  if ((rc = fleet_client_grads_device(m->ctx, m->state, m->stride, n_rows, m->d_client_rows, d_images, n_images, F,
+                                      d_labels, d_idx, d_shift, C, B, temperature, d_grads, grad_pitch, d_uploads,
+                                      upload_pitch, (void*)s)))
+    return rfail(m, rc, "client gradients: %s", rc == FLEET_ERR_ARG ? "C*B images without indices, a row pitch >= 22961, an upload pitch of whole groups"
+                                                                     : fleet_last_error(m->ctx));
   return FLEET_OK;
 }
 

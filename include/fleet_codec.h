@@ -904,6 +904,51 @@ int fleet_evaluate(fleet_ctx* ctx, const float* w, size_t n_w, const float* b, s
                    size_t n_images, int F, const int32_t* labels, const int32_t* idx, int B, float* error,
                    float* accuracy, int32_t* correct, int32_t* pred, float* prob);
 
+/* The client's gradients: Java_..._getGradients' hot loop (Client/app/src/main/cpp/
+ * cppNN-lib.cpp:101-113 the train_class calls, :218-234 cnn.gradients() and the upload), for
+ * C clients of B samples each. Client c's row is the float vector cnn.gradients() returns
+ * (commonLib/cppNN/network.h:1038-1056, after sync_mini_batch :1289-1331) once train_class
+ * (:1806-2008, with backward_hidden :1551-1611) has run on its B samples in the single-thread
+ * order, sample k taking batch slot k, on the MNIST network above with the cross_entropy
+ * cost: fleet_client_grad_len() = 22961 values, [nW, (size, dW..)*, nB, (size, dbias..)*].
+ * Per sample: m.shift(dx, dy, mojo::edge) (:1840), forward(input, temperature, thread, 1)
+ * (the client passes a teacher_prob, so TEMPERATURE = 2; 1 without), the output delta
+ * 1.f * (node - target) with a one-hot target (all zeros for a label outside [0, 10)), both
+ * passes of backward_hidden in the reference's order of operations (fleet_amd/csrc/
+ * client_backward.h restates it), then dW_sets[0] += dW_sets[b] in sample order. Bit-identical
+ * to the reference whenever no intermediate is NaN. A sample whose E is NaN (the reference
+ * bails) is reported by fleet_check as FLEET_ERR_ARG, its client's row then unspecified; with a
+ * NaN met only in the backward pass, NaN positions and bit patterns are not pinned.
+ * Not covered: DPgradients, the distillation cost, the client's own descent, the reference's
+ * thread race. */
+size_t fleet_client_grad_len(void);
+/* tests: walk the clients in chunks of at most max_clients (0: the default, what fits a
+ * 256 MiB workspace of per-sample rows); returns the previous value */
+int fleet_client_grad_set_chunk(int max_clients);
+/* device buffers, on the caller's stream, not synchronised. d_models: n_models rows of
+ * model_pitch floats, each w then b in fleet_teacher_forward's layout; d_model_of_client:
+ * int32[C] row per client, or NULL for row 0. d_images [n_images][F] (F >= 784), d_labels
+ * int32[n_images]; d_idx int32[C][B], or NULL for images c*B + k; d_shift int32[C][B][2]
+ * = {dx, dy} each in {-1, 0, 1}, or NULL for no shift. d_grads: C rows of grad_pitch floats
+ * (>= 22961). d_uploads: NULL, or C rows of upload_pitch bytes (a multiple of 16, >=
+ * 16 * ceil(22961 / 3)) that receive Base64::encode of the rows, the text fleet_update_device
+ * and fleet_pool_put_device take. The per-sample rows go to a workspace of the context,
+ * allocated on first use and grown only for a larger need; calls that use it must be ordered
+ * with each other. An image index, a model row or a shift outside its range is reported by
+ * fleet_check as FLEET_ERR_ARG, the outputs then unspecified. */
+int fleet_client_grads_device(fleet_ctx* ctx, const void* d_models, size_t model_pitch, int n_models,
+                              const void* d_model_of_client, const void* d_images, size_t n_images, int F,
+                              const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
+                              float temperature, void* d_grads, size_t grad_pitch, void* d_uploads,
+                              size_t upload_pitch, void* stream);
+/* host buffers, one model for every client, synchronous. grads [C][22961]; uploads NULL or C
+ * rows of upload_pitch bytes (>= fleet_b64_len(22961)). FLEET_ERR_ARG before any launch: NULL
+ * inputs, F < 784, C <= 0, B <= 0, n_w / n_b other than fleet_teacher_weight_count() /
+ * fleet_teacher_bias_count(), an index outside the images, a shift outside {-1, 0, 1}. */
+int fleet_client_grads(fleet_ctx* ctx, const float* w, size_t n_w, const float* b, size_t n_b, const float* images,
+                       size_t n_images, int F, const int32_t* labels, const int32_t* idx, const int32_t* shifts, int C,
+                       int B, float temperature, float* grads, char* uploads, size_t upload_pitch);
+
 /* Kardam bookkeeping of CppNNUpdater.update (Server/src/main/java/apps/cppNN/
  * CppNNUpdater.java:463-481, utils/Kardam.java:48-62) for the M
  * picked uploads in one call:
@@ -1170,6 +1215,15 @@ int fleet_rmodel_evaluate_device(fleet_rmodel* m, int version, const void* d_ima
 int fleet_rmodel_evaluate(fleet_rmodel* m, int version, const float* images, size_t n_images, int F,
                           const int32_t* labels, const int32_t* idx, int B, float* error, float* accuracy,
                           int32_t* correct, int32_t* pred, float* prob);
+/* fleet_client_grads_device with the models taken from the resident rows where they live
+ * (cppNN-lib.cpp:101-113, 218-234; network.h:1806-2008, 1551-1611, 1289-1331, 1038-1056):
+ * versions[C] (host) names client c's model as fleet_rmodel_evaluate_device names a version
+ * (-1: cnn); a client on an older version is FLeet's staleness. The MNIST network only. Runs
+ * on the caller's stream and does not synchronise (fleet_check of the model's context). */
+int fleet_rmodel_client_grads_device(fleet_rmodel* m, const int32_t* versions, const void* d_images, size_t n_images,
+                                     int F, const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
+                                     float temperature, void* d_grads, size_t grad_pitch, void* d_uploads,
+                                     size_t upload_pitch, void* stream);
 
 /* The offline sampler's state (the CppNNOfflineSampler natives
  * of Server/src/main/c++/cppNN_backend.cpp and the globals they keep). Random
