@@ -193,6 +193,13 @@ SIGNATURES = {
     "fleet_client_grads": (i32, [vp, vp, sz, vp, sz, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, vp, vp, sz]),
     "fleet_rmodel_client_grads_device": (i32, [vp, vp, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, vp, sz, vp, sz,
                                                vp]),
+    "fleet_client_ex_grads_device": (i32, [vp, vp, sz, i32, vp, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, i32, vp, vp,
+                                           vp, sz, vp, sz, vp]),
+    "fleet_client_ex_grads": (i32, [vp, vp, sz, vp, sz, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, i32, vp, vp, vp,
+                                    vp, sz]),
+    "fleet_rmodel_client_ex_grads_device": (i32, [vp, vp, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, i32, vp, vp, vp,
+                                                  sz, vp, sz, vp]),
+    "fleet_client_dp_noise": (i32, [vp, sz]),
     "fleet_model_load": (i32, [vp, vp, sz, i32, C.POINTER(vp)]),
     "fleet_model_destroy": (None, [vp]),
     "fleet_model_last_error": (C.c_char_p, [vp]),

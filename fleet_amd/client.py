@@ -7,7 +7,13 @@ one launch sequence.
 * :func:`resident_client_gradients_device` -- the models taken from a
   :class:`~fleet_amd.ResidentModel`'s versions;
 * :func:`client_shifts` -- the ``rand()`` draw of the shifts; :class:`client_chunk_override`
-  and :func:`upload_texts` for tests and callers of the upload rows.
+  and :func:`upload_texts` for tests and callers of the upload rows;
+* :func:`dp_noise_table` -- the draws ``addGaussian`` adds, before scaling.
+
+The three gradient functions take the keyword-only ``cost`` ("cross_entropy", or "distillation"
+for the client built with DISTILLATION_MODE 1, cppNN-lib.cpp:251-252) and ``clip`` / ``sigma``
+(a scalar or one value per client; ``sigma`` > 0 is ``cnn.DPgradients(clip, sigma)``,
+cppNN-lib.cpp:218-219). Left at their defaults a call is the one it was before they existed.
 
 They are functions of this module rather than methods: the package's recorded surface
 (tests/api_surface.json) admits new modules only."""
@@ -135,7 +141,48 @@ def upload_texts(uploads) -> list:
     return [a[c, :n].tobytes() for c in range(a.shape[0])]
 
 
-def client_gradients(codec, w, b, images, labels, idx=None, shifts=None, temperature=2.0, uploads=False):
+COSTS = {"cross_entropy": 0, "distillation": 1}
+
+
+def dp_noise_table(n: int = None) -> np.ndarray:
+    """float64 [n] (default all 22961): the standard-normal draws ``addGaussian`` adds to the
+    slots of a DP vector, before it scales them by ``C * sigma`` (commonLib/cppNN/network.h:
+    1125-1130): the same on every call, as the reference constructs its engine anew each time.
+    Host only; they come from the C++ library this package is built with."""
+    n = client_grad_len() if n is None else int(n)
+    out = np.empty(n, np.float64)
+    if lib().fleet_client_dp_noise(out.ctypes.data, n) != 0:
+        raise ValueError(f"at most {client_grad_len()} draws")
+    return out
+
+
+def ex_args(cost, clip, sigma, C):
+    """(cost code, clip float32[C] or None, sigma float32[C] or None) of a call's keywords, or
+    None where all three are the defaults (the call is then the one without them)."""
+    if cost == "cross_entropy" and clip is None and sigma is None:
+        return None
+    if cost not in COSTS:
+        raise ValueError(f"cost: one of {sorted(COSTS)}")
+    if (clip is None) != (sigma is None):
+        raise ValueError("clip and sigma: both or neither")
+
+    def per_client(v):
+        if v is None:
+            return None
+        a = np.asarray(v, dtype=np.float32)
+        a = np.full(C, a, np.float32) if a.ndim == 0 else np.ascontiguousarray(a.reshape(-1))
+        if len(a) != C:
+            raise ValueError("clip and sigma: a scalar or one value per client")
+        return a
+    return COSTS[cost], per_client(clip), per_client(sigma)
+
+
+def _fptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def client_gradients(codec, w, b, images, labels, idx=None, shifts=None, temperature=2.0, uploads=False, *,
+                     cost="cross_entropy", clip=None, sigma=None):
     """What ``cnn.gradients()`` returns after ``train_class`` on each sample of a client's
     mini-batch (Client/app/src/main/cpp/cppNN-lib.cpp:101-113, 218-234), bit for bit, for the
     MNIST network with weights ``w`` and biases ``b``: float32 [C, 22961]. ``idx`` [C, B] picks
@@ -151,15 +198,20 @@ def client_gradients(codec, w, b, images, labels, idx=None, shifts=None, tempera
     grads = np.empty((max(C, 1), n), np.float32)
     pitch = b64_len(n)
     up = np.zeros((max(C, 1), pitch), np.uint8) if uploads else None
-    codec._check(L.fleet_client_grads(h, wv.ctypes.data, len(wv), bv.ctypes.data, len(bv), x.ctypes.data, x.shape[0],
-                                      x.shape[1], lab.ctypes.data, None if ix is None else ix.ctypes.data,
-                                      None if sh is None else sh.ctypes.data, C, B, float(temperature),
-                                      grads.ctypes.data, None if up is None else up.ctypes.data, pitch))
+    head = (h, wv.ctypes.data, len(wv), bv.ctypes.data, len(bv), x.ctypes.data, x.shape[0], x.shape[1], lab.ctypes.data,
+            None if ix is None else ix.ctypes.data, None if sh is None else sh.ctypes.data, C, B, float(temperature))
+    tail = (grads.ctypes.data, None if up is None else up.ctypes.data, pitch)
+    ex = ex_args(cost, clip, sigma, C)
+    if ex is None:
+        codec._check(L.fleet_client_grads(*head, *tail))
+    else:
+        codec._check(L.fleet_client_ex_grads(*head, ex[0], _fptr(ex[1]), _fptr(ex[2]), *tail))
     return (grads, [up[c].tobytes() for c in range(C)]) if uploads else grads
 
 
 def client_gradients_device(codec, models_f32, images_f32, labels_i32, idx=None, shifts=None, model_of_client=None,
-                            C=None, B=None, temperature=2.0, grads=None, uploads=False, stream=None):
+                            C=None, B=None, temperature=2.0, grads=None, uploads=False, stream=None, *,
+                            cost="cross_entropy", clip=None, sigma=None):
     """Device-resident :func:`client_gradients`: CUDA tensors models [rows, >= 21530] (w then b
     per row), images [N, F >= 784] float32, labels [N] int32, idx [C, B] int32 or None (images
     c*B + k; give C and B), shifts [C, B, 2] int32 or None, model_of_client [C] int32 or None
@@ -180,16 +232,20 @@ def client_gradients_device(codec, models_f32, images_f32, labels_i32, idx=None,
     n_img, F, C, B, grads, up = device_args(images_f32, labels_i32, idx, shifts, C, B, grads, uploads)
     if model_of_client is not None and model_of_client.numel() != C:
         raise ValueError("model_of_client: one row per client")
-    codec._check(L.fleet_client_grads_device(h, models_f32.data_ptr(), models_f32.stride(0), models_f32.shape[0],
-                                             _ptr(model_of_client), images_f32.data_ptr(), n_img, F,
-                                             labels_i32.data_ptr(), _ptr(idx), _ptr(shifts), C, B, float(temperature),
-                                             grads.data_ptr(), grads.stride(0), _ptr(up),
-                                             0 if up is None else up.stride(0), _stream(stream)))
+    head = (h, models_f32.data_ptr(), models_f32.stride(0), models_f32.shape[0], _ptr(model_of_client),
+            images_f32.data_ptr(), n_img, F, labels_i32.data_ptr(), _ptr(idx), _ptr(shifts), C, B, float(temperature))
+    tail = (grads.data_ptr(), grads.stride(0), _ptr(up), 0 if up is None else up.stride(0), _stream(stream))
+    ex = ex_args(cost, clip, sigma, C)
+    if ex is None:
+        codec._check(L.fleet_client_grads_device(*head, *tail))
+    else:
+        codec._check(L.fleet_client_ex_grads_device(*head, ex[0], _fptr(ex[1]), _fptr(ex[2]), *tail))
     return (grads, up) if up is not None else grads
 
 
 def resident_client_gradients_device(rm, versions, images_f32, labels_i32, idx=None, shifts=None, uploads=False,
-                                     C=None, B=None, temperature=2.0, grads=None, stream=None):
+                                     C=None, B=None, temperature=2.0, grads=None, stream=None, *,
+                                     cost="cross_entropy", clip=None, sigma=None):
     """The gradients C clients compute on versions of the resident model ``rm``, where the
     versions live (:func:`client_gradients_device` names the tensors). ``versions``: one per
     client, or one for all: a version index, -1 for ``cnn``, None for the newest; a client on
@@ -200,8 +256,12 @@ def resident_client_gradients_device(rm, versions, images_f32, labels_i32, idx=N
     if len(vs) != C:
         raise ValueError("one version per client")
     v = np.array([rm._eval_version(x) for x in vs], np.int32)
-    rm._check(rm._L.fleet_rmodel_client_grads_device(rm._live(), v.ctypes.data, images_f32.data_ptr(), n_img, F,
-                                                     labels_i32.data_ptr(), _ptr(idx), _ptr(shifts), C, B,
-                                                     float(temperature), grads.data_ptr(), grads.stride(0), _ptr(up),
-                                                     0 if up is None else up.stride(0), _stream(stream)))
+    head = (rm._live(), v.ctypes.data, images_f32.data_ptr(), n_img, F, labels_i32.data_ptr(), _ptr(idx), _ptr(shifts),
+            C, B, float(temperature))
+    tail = (grads.data_ptr(), grads.stride(0), _ptr(up), 0 if up is None else up.stride(0), _stream(stream))
+    ex = ex_args(cost, clip, sigma, C)
+    if ex is None:
+        rm._check(rm._L.fleet_rmodel_client_grads_device(*head, *tail))
+    else:
+        rm._check(rm._L.fleet_rmodel_client_ex_grads_device(*head, ex[0], _fptr(ex[1]), _fptr(ex[2]), *tail))
     return (grads, up) if up is not None else grads

@@ -12,6 +12,9 @@
 // order (sample k of the call takes batch slot k) with the cross_entropy cost. The reference is
 // built -O0 without MOJO_AVX or NEON, so layer.h's and core_math.h's plain-C branches run: one
 // binary32 rounding per operation, no contraction, every sum in the order written there.
+// The distillation cost (out_delta_distill) and DPgradients (sample_sqsum, clip_scale, noisy,
+// dp_grad_element) follow the cross-entropy path below and are documented where they stand;
+// tests/native/check_client_dp.cpp checks them against tests/golden/client_dp_ref.npz.
 //
 // Per sample (network.h:1806-2008):
 //   shift    m.shift(dx, dy, mojo::edge) (:1840, core_math.h:721-731): pad by replication and
@@ -56,6 +59,11 @@
 // unspecified. With a NaN met only in the backward pass, positions and bits are unpinned.
 #pragma once
 #include <stdint.h>
+#if !defined(__HIP_DEVICE_COMPILE__)
+#include <stddef.h>
+
+#include <random>
+#endif
 
 #include "eval_forward.h"
 #include "teacher_math.h"
@@ -174,6 +182,35 @@ FLEET_TM float out_delta(const float* node, int32_t label, float* delta) {
   return E / (float)kClasses;
 }
 
+// The output delta under start_epoch("distillation") (cppNN-lib.cpp:251-252, DISTILLATION_MODE 1).
+// FC2 is softmax, so cost_activation_type stays 0 and network.h:1959 runs:
+//   delta[j] = distillation::d_cost(node[j], target[j], teacher_prob[j], T) * softmax::df(node, j, 10, T)
+// d_cost (cost.h:93-113) never reads the teacher's value: with q = (out - target) / (out * (1.f - out))
+// in binary32 it is wtl * pow(T, 2) * q + (1 - wtl) * q, wtl = 0.7f: the first two products and
+// the sum in binary64 (pow of a float promotes; (double)T * T is pow(T, 2) exactly), the product
+// (1 - wtl) * q in binary32, the result narrowed. df (activation.h:301-304) is
+// node/T * (1.f - node/T). E is the mean of mse::cost as under cross_entropy (:1974-1982).
+// Where out * (1 - out) is 0 the delta is NaN or inf at the reference's positions; NaN bits are
+// not pinned (see the head of this file).
+FLEET_TM float out_delta_distill(const float* node, int32_t label, float temperature, float* delta) {
+  const float wtl = 0.7f;
+  float E = 0.0f;
+  for (int j = 0; j < kClasses; ++j) {
+    const float out = node[j];
+    const float target = (label >= 0 && label < kClasses && j == label) ? 1.0f : 0.0f;
+    const float d = out - target;
+    const float q = d / (out * (1.0f - out));
+    const double t2 = (double)temperature * (double)temperature;
+    const float d_cost = (float)((double)wtl * t2 * (double)q + (double)((1.0f - wtl) * q));
+    const float nt = out / temperature;
+    delta[j] = d_cost * (nt * (1.0f - nt));
+    E += (0.5f * d) * d;
+  }
+  return E / (float)kClasses;
+}
+
+constexpr int kCostCrossEntropy = 0, kCostDistillation = 1;
+
 // a pool's delta scattered through its p_map into element o of the convolution above it,
 // then that layer's elu df: window `win` is the one o lies in
 FLEET_TM float unpool_df(const float* pool_delta, const int32_t* pmap, int win, int o, float node) {
@@ -220,7 +257,9 @@ FLEET_TM float dot2d_4(const float* x1, const float* x2, int stride1, int stride
 // returns once all of them are done (the block's lanes and a barrier in the kernel, a loop on
 // the host). row: the sample's gradients() vector [kGradLen], dW and dbias of this sample alone.
 // image: the unshifted sample [784]. Returns false where E is NaN (the reference's bail).
-template <class Par>
+// Cost: kCostCrossEntropy (out_delta) or kCostDistillation (out_delta_distill), a compile-time
+// choice: the cross-entropy instantiation is the code it was before the choice existed.
+template <int Cost, class Par>
 FLEET_TM bool sample_stages(Par par, Sample& S, const float* w, const float* b, const float* image, int32_t label,
                             int dx, int dy, float temperature, float* row) {
   // shift
@@ -245,7 +284,10 @@ FLEET_TM bool sample_stages(Par par, Sample& S, const float* w, const float* b, 
   par(kClasses, [&](int o) { S.fc[o] = fc(S.p2, w + kWfc + o * kFcIn); });
   par(1, [&](int) {
     softmax10(S.fc, temperature);
-    S.E = out_delta(S.fc, label, S.d_fc);
+    if (Cost == kCostDistillation)
+      S.E = out_delta_distill(S.fc, label, temperature, S.d_fc);
+    else
+      S.E = out_delta(S.fc, label, S.d_fc);
   });
   // pass 1: FC2 -> P2
   par(kFcIn, [&](int t) {
@@ -327,7 +369,87 @@ FLEET_TM float grad_element(const float* rows, int64_t pitch, int B, int e) {
   return a;
 }
 
+// ---- DPgradients(C, sigma) (network.h:1133-1181; cppNN-lib.cpp:218-219 calls it when sigma > 0)
+//
+// scale_gradients(C) (:1092-1123), batch slots b = 1 .. B-1 only (slot 0 is never clipped):
+// sqsum = 0 in binary32; layers k = last .. 0, per layer the backward link's dW block element by
+// element, sqsum += x*x, then the layer's dbias block the same way: kClipOrder below, a
+// permutation of the gradients() layout by block. norm = sqrt(sqsum);
+// scale = 1 / std::max<float>(1.0, norm / C): std::max(a, b) is a < b ? b : a, so a NaN norm gives
+// 1 and an infinite one 0. The second loop never reassigns `layer`, which still points at the
+// input layer (no backward links): no dW is scaled, only every layer's dbias block is multiplied
+// by scale. Kept as it is. Then sync_mini_batch, the vector with 0 in the header slots,
+// addGaussian(ret, C * sigma) (:1125-1130) on every slot, and the sizes written over the headers.
+struct Segment {
+  int pos, len;
+};
+constexpr int kClipSegments = 8;
+constexpr int kClipLen = kGradLen - kHeaders;  // 22946 values enter the norm
+#define FLEET_CLIENT_CLIP_ORDER                                                                              \
+  {{kG_Wfc, 1920}, {kG_Bfc, kClasses}, {kG_BP2, kFcIn}, {kG_W2, 19200}, {kG_W2i, 128}, {kG_BP1, kP1Out},     \
+   {kG_W1, 200}, {kG_BI1, kPix}}
+
+// position p of scale_gradients' walk, p in [0, kClipLen): its element of the gradients() layout
+FLEET_TM int clip_element(int p) {
+  constexpr Segment seg[kClipSegments] = FLEET_CLIENT_CLIP_ORDER;
+  int e = 0;
+  for (int i = 0; i < kClipSegments; ++i) {
+    if (p >= 0 && p < seg[i].len) e = seg[i].pos + p;
+    p -= seg[i].len;
+  }
+  return e;
+}
+
+// true for the elements of a dbias block (the ones scale_gradients scales)
+FLEET_TM bool is_bias_element(int e) { return e > kG_nB; }
+
+// one stored row's sqsum in the reference's order
+FLEET_TM float sample_sqsum(const float* row) {
+  constexpr Segment seg[kClipSegments] = FLEET_CLIENT_CLIP_ORDER;
+  float sqsum = 0.0f;
+  for (int i = 0; i < kClipSegments; ++i)
+    for (int j = 0; j < seg[i].len; ++j) sqsum = sqsum + row[seg[i].pos + j] * row[seg[i].pos + j];
+  return sqsum;
+}
+
+// sqrt of a float through binary64 is the correctly rounded binary32 root
+FLEET_TM float clip_norm(float sqsum) { return (float)__builtin_sqrt((double)sqsum); }
+
+FLEET_TM float clip_scale(float sqsum, float clip) {
+  const float r = clip_norm(sqsum) / clip;
+  return 1.0f / (1.0f < r ? r : 1.0f);
+}
+
+// v[i] += dist(generator) with std::normal_distribution<double>(0.0, s): the float widened, the
+// draw z * s + 0.0 added in binary64, the sum narrowed
+FLEET_TM float noisy(float sum, double z, double s) { return (float)((double)sum + (z * s + 0.0)); }
+
+// Element e of DPgradients' vector from the B per-sample rows and the B scales (scale[0] is 1
+// and is not applied). s: the float product C * sigma, widened. z: the draw of slot e.
+FLEET_TM float dp_grad_element(const float* rows, int64_t pitch, int B, const float* scale, int e, double z, double s) {
+  constexpr Header h[kHeaders] = FLEET_CLIENT_HEADERS;
+  for (int i = 0; i < kHeaders; ++i)
+    if (h[i].pos == e) return h[i].value;
+  float a = rows[e];
+  if (is_bias_element(e))
+    for (int k = 1; k < B; ++k) a = a + rows[(int64_t)k * pitch + e] * scale[k];
+  else
+    for (int k = 1; k < B; ++k) a = a + rows[(int64_t)k * pitch + e];
+  return noisy(a, z, s);
+}
+
 #if !defined(__HIP_DEVICE_COMPILE__)
+// The standard-normal draws addGaussian adds, before scaling: a default-constructed
+// std::default_random_engine and a fresh std::normal_distribution<double>(0.0, 1.0), so draw i
+// is the same on every call (network.h:1125-1130 constructs both anew each time; its
+// distribution (0.0, s) returns this draw times s plus 0.0). The sequence is the platform's
+// libstdc++ and libm, as the reference client's is its own platform's.
+inline void dp_noise_draws(double* out, size_t n) {
+  std::default_random_engine generator;
+  std::normal_distribution<double> dist(0.0, 1.0);
+  for (size_t i = 0; i < n; ++i) out[i] = dist(generator);
+}
+
 struct HostPar {
   template <class F>
   void operator()(int n, F f) const {
@@ -338,17 +460,44 @@ struct HostPar {
 // One client's call in plain loops: images [B][784] (already gathered), labels [B], shifts
 // [B][2] or NULL, out [kGradLen]. rows: scratch [B][kGradLen]. keep: the B samples' layers, or
 // NULL. Returns the number of samples whose E is NaN.
-inline int client_grad_host(const float* w, const float* b, const float* images, const int32_t* labels,
-                            const int32_t* shifts, int B, float temperature, float* rows, float* out, Sample* keep) {
+// cost: kCostCrossEntropy or kCostDistillation. sigma > 0 is DPgradients(clip, sigma) with the
+// draws z [kGradLen]; stats, if given, receives sqsum, norm and scale of every sample, [3][B]
+// (slot 0: 0, 0, 1).
+inline int client_grad_host_ex(const float* w, const float* b, const float* images, const int32_t* labels,
+                               const int32_t* shifts, int B, float temperature, int cost, float clip, float sigma,
+                               const double* z, float* rows, float* out, Sample* keep, float* stats) {
   Sample* S = keep ? nullptr : new Sample;
   int blown = 0;
-  for (int k = 0; k < B; ++k)
-    blown += !sample_stages(HostPar{}, keep ? keep[k] : *S, w, b, images + (int64_t)k * kPix, labels[k],
-                            shifts ? shifts[2 * k] : 0, shifts ? shifts[2 * k + 1] : 0, temperature,
-                            rows + (int64_t)k * kGradLen);
-  for (int e = 0; e < kGradLen; ++e) out[e] = grad_element(rows, kGradLen, B, e);
+  for (int k = 0; k < B; ++k) {
+    Sample& s = keep ? keep[k] : *S;
+    const float* image = images + (int64_t)k * kPix;
+    const int dx = shifts ? shifts[2 * k] : 0, dy = shifts ? shifts[2 * k + 1] : 0;
+    float* row = rows + (int64_t)k * kGradLen;
+    blown += cost == kCostDistillation
+                 ? !sample_stages<kCostDistillation>(HostPar{}, s, w, b, image, labels[k], dx, dy, temperature, row)
+                 : !sample_stages<kCostCrossEntropy>(HostPar{}, s, w, b, image, labels[k], dx, dy, temperature, row);
+  }
+  if (sigma > 0.0f) {
+    float* scale = new float[B];
+    for (int k = 0; k < B; ++k) {
+      const float sq = k ? sample_sqsum(rows + (int64_t)k * kGradLen) : 0.0f;
+      scale[k] = k ? clip_scale(sq, clip) : 1.0f;
+      if (stats) stats[k] = sq, stats[B + k] = k ? clip_norm(sq) : 0.0f, stats[2 * B + k] = scale[k];
+    }
+    const double s = (double)(clip * sigma);
+    for (int e = 0; e < kGradLen; ++e) out[e] = dp_grad_element(rows, kGradLen, B, scale, e, z[e], s);
+    delete[] scale;
+  } else {
+    for (int e = 0; e < kGradLen; ++e) out[e] = grad_element(rows, kGradLen, B, e);
+  }
   delete S;
   return blown;
+}
+
+inline int client_grad_host(const float* w, const float* b, const float* images, const int32_t* labels,
+                            const int32_t* shifts, int B, float temperature, float* rows, float* out, Sample* keep) {
+  return client_grad_host_ex(w, b, images, labels, shifts, B, temperature, kCostCrossEntropy, 0.0f, 0.0f, nullptr, rows,
+                             out, keep, nullptr);
 }
 #endif
 

@@ -150,6 +150,11 @@ struct fleet_ctx {
   // freed, when it grows, for the same reason)
   float* d_client_ws = nullptr;
   size_t d_client_ws_cap = 0;  // bytes
+  // the DP forms: clip[C] then sigma[C] of the call (retired when it grows), and the 22961
+  // standard-normal draws, made on the host on the first DP call and resident from then on
+  float* d_client_dp = nullptr;
+  int d_client_dp_cap = 0;  // the C it holds
+  double* d_dp_z = nullptr;
 };
 
 namespace {
@@ -487,7 +492,7 @@ void fleet_destroy(fleet_ctx* c) {
   for (void* p : {(void*)c->d_a, (void*)c->d_b, (void*)c->d_out, (void*)c->d_f32, (void*)c->d_dampen,
                   (void*)c->d_hdr, (void*)c->d_err, (void*)c->d_partials, (void*)c->d_dev_dampen,
                   (void*)c->d_dev_hdr, (void*)c->d_dev_err, (void*)c->d_kflags, (void*)c->d_eval,
-                  (void*)c->d_client_ws})
+                  (void*)c->d_client_ws, (void*)c->d_client_dp, (void*)c->d_dp_z})
     if (p) (void)hipFree(p);
   for (void* p : c->retired) (void)hipFree(p);
   for (void* p : {(void*)c->h_stage, (void*)c->h_hdr, (void*)c->h_err})
@@ -1722,15 +1727,36 @@ int fleet_client_grad_set_chunk(int max_clients) { return fleet::client_grad_set
 // 1551-1611, 1289-1331, 1038-1056
 namespace {
 
-// both forms, the lock held and the device set: the workspace, the two launches per chunk of
-// clients, the encode of the rows; err: the error word the kernels report to
+// the cost and the DP parameters of the _ex_ forms, before anything else is looked at
+bool client_ex_args_ok(int cost, const float* clip, const float* sigma, int C) {
+  if (cost != FLEET_COST_CROSS_ENTROPY && cost != FLEET_COST_DISTILLATION) return false;
+  if (!clip != !sigma) return false;
+  for (int c = 0; clip && c < C; ++c) {
+    if (!(sigma[c] >= 0.0f) || std::isinf(sigma[c])) return false;
+    if (sigma[c] > 0.0f && (!(clip[c] > 0.0f) || std::isinf(clip[c]))) return false;
+  }
+  return true;
+}
+
+// every form, the lock held and the device set: the workspace, the launches per chunk of
+// clients, the encode of the rows; err: the error word the kernels report to. clip, sigma: host
+// [C] or both NULL (checked by client_ex_args_ok).
 int client_grads_locked(fleet_ctx* c, const void* d_models, size_t model_pitch, int n_models,
                         const void* d_model_of_client, const void* d_images, size_t n_images, int F,
                         const void* d_labels, const void* d_idx, const void* d_shift, int C, int B, float temperature,
-                        void* d_grads, size_t grad_pitch, void* d_uploads, size_t upload_pitch, hipStream_t s) {
+                        int cost, const float* clip, const float* sigma, void* d_grads, size_t grad_pitch,
+                        void* d_uploads, size_t upload_pitch, hipStream_t s) {
   const size_t n_up = fleet_client_grad_len();
   const int chunk = fleet::client_grad_chunk(C, B);
-  const size_t need = fleet::client_grad_workspace_bytes(chunk, B);
+  const size_t rows_bytes = fleet::client_grad_workspace_bytes(chunk, B);
+  std::vector<uint8_t> dp_of_client;
+  bool dp = false;
+  if (sigma) {
+    dp_of_client.resize((size_t)C);
+    for (int i = 0; i < C; ++i) dp |= (dp_of_client[(size_t)i] = sigma[i] > 0.0f) != 0;
+  }
+  // the scales lie behind the rows, with or without DP, so a DP call grows nothing a plain one made
+  const size_t need = rows_bytes + fleet::client_grad_scale_bytes(chunk, B);
   if (need > c->d_client_ws_cap) {
     if (c->d_client_ws) c->retired.push_back(c->d_client_ws);
     c->d_client_ws = nullptr;
@@ -1739,11 +1765,43 @@ int client_grads_locked(fleet_ctx* c, const void* d_models, size_t model_pitch, 
     if (e != hipSuccess) return fail(c, FLEET_ERR_NOMEM, "hipMalloc(%zu): %s", need, hipGetErrorString(e));
     c->d_client_ws_cap = need;
   }
-  HIP_TRY(c, fleet::launch_client_grads((const float*)d_models, (int64_t)model_pitch, n_models,
-                                        (const int32_t*)d_model_of_client, (const float*)d_images, (int64_t)n_images, F,
-                                        (const int32_t*)d_labels, (const int32_t*)d_idx, (const int32_t*)d_shift, C, B,
-                                        chunk, temperature, c->d_client_ws, (float*)d_grads, (int64_t)grad_pitch,
-                                        c->d_dev_err, s));
+  if (dp) {
+    if (!c->d_dp_z) {  // once per context
+      // the host table is made once per process and kept: every context uploads the same draws
+      static const std::vector<double> z = [n_up] {
+        std::vector<double> t(n_up);
+        fleet::client_dp_noise(t.data(), t.size());
+        return t;
+      }();
+      const hipError_t e = hipMalloc((void**)&c->d_dp_z, sizeof(double) * n_up);
+      if (e != hipSuccess) return fail(c, FLEET_ERR_NOMEM, "hipMalloc(%zu): %s", sizeof(double) * n_up, hipGetErrorString(e));
+      const hipError_t e2 = hipMemcpy(c->d_dp_z, z.data(), sizeof(double) * n_up, hipMemcpyHostToDevice);
+      if (e2 != hipSuccess) {
+        (void)hipFree(c->d_dp_z);
+        c->d_dp_z = nullptr;
+        return fail(c, FLEET_ERR_HIP, "the DP noise table: %s", hipGetErrorString(e2));
+      }
+    }
+    if (C > c->d_client_dp_cap) {
+      if (c->d_client_dp) c->retired.push_back(c->d_client_dp);
+      c->d_client_dp = nullptr;
+      c->d_client_dp_cap = 0;
+      const hipError_t e = hipMalloc((void**)&c->d_client_dp, 2 * sizeof(float) * (size_t)C);
+      if (e != hipSuccess) return fail(c, FLEET_ERR_NOMEM, "hipMalloc(%zu): %s", 8 * (size_t)C, hipGetErrorString(e));
+      c->d_client_dp_cap = C;
+    }
+    // pageable sources: the copies have left clip and sigma when the call returns
+    HIP_TRY(c, hipMemcpyAsync(c->d_client_dp, clip, sizeof(float) * (size_t)C, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->d_client_dp + C, sigma, sizeof(float) * (size_t)C, hipMemcpyHostToDevice, s));
+  }
+  HIP_TRY(c, fleet::launch_client_grads_ex((const float*)d_models, (int64_t)model_pitch, n_models,
+                                           (const int32_t*)d_model_of_client, (const float*)d_images,
+                                           (int64_t)n_images, F, (const int32_t*)d_labels, (const int32_t*)d_idx,
+                                           (const int32_t*)d_shift, C, B, chunk, temperature, cost,
+                                           dp ? c->d_client_dp : nullptr, dp ? c->d_client_dp + C : nullptr,
+                                           dp ? dp_of_client.data() : nullptr, dp ? c->d_dp_z : nullptr,
+                                           dp ? (float*)((uint8_t*)c->d_client_ws + rows_bytes) : nullptr,
+                                           c->d_client_ws, (float*)d_grads, (int64_t)grad_pitch, c->d_dev_err, s));
   if (d_uploads)
     HIP_TRY(c, fleet::launch_encode_f32((const float*)d_grads, (int64_t)n_up, grad_pitch, C, (uint8_t*)d_uploads,
                                         upload_pitch, s));
@@ -1752,29 +1810,53 @@ int client_grads_locked(fleet_ctx* c, const void* d_models, size_t model_pitch, 
 
 }  // namespace
 
-int fleet_client_grads_device(fleet_ctx* c, const void* d_models, size_t model_pitch, int n_models,
-                              const void* d_model_of_client, const void* d_images, size_t n_images, int F,
-                              const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
-                              float temperature, void* d_grads, size_t grad_pitch, void* d_uploads,
-                              size_t upload_pitch, void* stream) {
+int fleet_client_dp_noise(double* out, size_t n) {
+  if (!out || n > fleet_client_grad_len()) return FLEET_ERR_ARG;
+  fleet::client_dp_noise(out, n);
+  return FLEET_OK;
+}
+
+int fleet_client_ex_grads_device(fleet_ctx* c, const void* d_models, size_t model_pitch, int n_models,
+                                 const void* d_model_of_client, const void* d_images, size_t n_images, int F,
+                                 const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
+                                 float temperature, int cost, const float* clip, const float* sigma, void* d_grads,
+                                 size_t grad_pitch, void* d_uploads, size_t upload_pitch, void* stream) {
   const size_t n_up = fleet_client_grad_len();
   if (!c || !d_models || !d_images || !d_labels || !d_grads || C <= 0 || B <= 0 || F < 28 * 28 || n_models <= 0 ||
       n_images == 0 || model_pitch < fleet_teacher_weight_count() + fleet_teacher_bias_count() || grad_pitch < n_up ||
       (size_t)C * (size_t)B > (size_t)INT32_MAX || (!d_idx && (size_t)C * (size_t)B > n_images))
     return FLEET_ERR_ARG;
+  if (!client_ex_args_ok(cost, clip, sigma, C))
+    return fail(c, FLEET_ERR_ARG, "client gradients: cost 0 or 1; clip and sigma both or neither, sigma >= 0 and "
+                                  "finite, clip > 0 and finite where sigma > 0");
   if (d_uploads && (upload_pitch % 16 != 0 || upload_pitch < 16 * groups_of(n_up)))
     return fail(c, FLEET_ERR_ARG, "bad upload pitch");
   std::lock_guard<std::mutex> lk(c->mu);
   DEVICE_SCOPE(c);
   return client_grads_locked(c, d_models, model_pitch, n_models, d_model_of_client, d_images, n_images, F, d_labels, d_idx,
-                             d_shift, C, B, temperature, d_grads, grad_pitch, d_uploads, upload_pitch, pick(c, stream));
+                             d_shift, C, B, temperature, cost, clip, sigma, d_grads, grad_pitch, d_uploads, upload_pitch,
+                             pick(c, stream));
 }
 
-int fleet_client_grads(fleet_ctx* c, const float* w, size_t n_w, const float* b, size_t n_b, const float* images,
-                       size_t n_images, int F, const int32_t* labels, const int32_t* idx, const int32_t* shifts, int C,
-                       int B, float temperature, float* grads, char* uploads, size_t upload_pitch) {
+int fleet_client_grads_device(fleet_ctx* c, const void* d_models, size_t model_pitch, int n_models,
+                              const void* d_model_of_client, const void* d_images, size_t n_images, int F,
+                              const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
+                              float temperature, void* d_grads, size_t grad_pitch, void* d_uploads,
+                              size_t upload_pitch, void* stream) {
+  return fleet_client_ex_grads_device(c, d_models, model_pitch, n_models, d_model_of_client, d_images, n_images, F,
+                                      d_labels, d_idx, d_shift, C, B, temperature, FLEET_COST_CROSS_ENTROPY, nullptr,
+                                      nullptr, d_grads, grad_pitch, d_uploads, upload_pitch, stream);
+}
+
+int fleet_client_ex_grads(fleet_ctx* c, const float* w, size_t n_w, const float* b, size_t n_b, const float* images,
+                          size_t n_images, int F, const int32_t* labels, const int32_t* idx, const int32_t* shifts,
+                          int C, int B, float temperature, int cost, const float* clip, const float* sigma,
+                          float* grads, char* uploads, size_t upload_pitch) {
   if (!c || !w || !b || !images || !labels || !grads || C <= 0 || B <= 0 || F < 28 * 28 || n_images == 0)
     return FLEET_ERR_ARG;
+  if (!client_ex_args_ok(cost, clip, sigma, C))
+    return fail(c, FLEET_ERR_ARG, "client gradients: cost 0 or 1; clip and sigma both or neither, sigma >= 0 and "
+                                  "finite, clip > 0 and finite where sigma > 0");
   if (n_w != fleet_teacher_weight_count() || n_b != fleet_teacher_bias_count())
     return fail(c, FLEET_ERR_ARG, "client gradients: %zu weights and %zu biases, expected %zu and %zu", n_w, n_b,
                 fleet_teacher_weight_count(), fleet_teacher_bias_count());
@@ -1806,14 +1888,21 @@ int fleet_client_grads(fleet_ctx* c, const float* w, size_t n_w, const float* b,
   if (idx) HIP_TRY(c, hipMemcpyAsync(d + o_i, idx, 4 * n, hipMemcpyHostToDevice, c->stream));
   if (shifts) HIP_TRY(c, hipMemcpyAsync(d + o_s, shifts, 8 * n, hipMemcpyHostToDevice, c->stream));
   if ((rc = client_grads_locked(c, d, n_w + n_b, 1, nullptr, d + o_x, rows, F, d + o_l, idx ? d + o_i : nullptr,
-                                shifts ? d + o_s : nullptr, C, B, temperature, d + o_g, n_up, uploads ? d + o_u : nullptr,
-                                groups_bytes, c->stream)))
+                                shifts ? d + o_s : nullptr, C, B, temperature, cost, clip, sigma, d + o_g, n_up,
+                                uploads ? d + o_u : nullptr, groups_bytes, c->stream)))
     return rc;
   HIP_TRY(c, hipMemcpyAsync(grads, d + o_g, sizeof(float) * (size_t)C * n_up, hipMemcpyDeviceToHost, c->stream));
   if (uploads)
     HIP_TRY(c, hipMemcpy2DAsync(uploads, upload_pitch, d + o_u, groups_bytes, up_len, (size_t)C, hipMemcpyDeviceToHost,
                                 c->stream));
   return read_err(c, c->stream, c->d_dev_err);
+}
+
+int fleet_client_grads(fleet_ctx* c, const float* w, size_t n_w, const float* b, size_t n_b, const float* images,
+                       size_t n_images, int F, const int32_t* labels, const int32_t* idx, const int32_t* shifts, int C,
+                       int B, float temperature, float* grads, char* uploads, size_t upload_pitch) {
+  return fleet_client_ex_grads(c, w, n_w, b, n_b, images, n_images, F, labels, idx, shifts, C, B, temperature,
+                               FLEET_COST_CROSS_ENTROPY, nullptr, nullptr, grads, uploads, upload_pitch);
 }
 
 int fleet_model_params(fleet_ctx* c, const float* weights, size_t n_weights, const float* biases, size_t n_biases,

@@ -209,6 +209,18 @@ hipError_t launch_client_grads(const float* models, int64_t model_pitch, int n_m
                                const float* images, int64_t n_images, int F, const int32_t* labels, const int32_t* idx,
                                const int32_t* shift, int C, int B, int chunk, float temperature, float* workspace,
                                float* grads, int64_t grad_pitch, int* err, hipStream_t s);
+// the same with a cost (0 cross_entropy, 1 distillation) and, where d_clip is given, DPgradients
+// for the clients with sigma > 0: d_clip, d_sigma [C] on the device, dp_of_client [C] on the host
+// (non-zero: sigma > 0), d_z the 22961 draws of client_dp_noise, scale:
+// client_grad_scale_bytes(chunk, B) on the device
+hipError_t launch_client_grads_ex(const float* models, int64_t model_pitch, int n_models,
+                                  const int32_t* model_of_client, const float* images, int64_t n_images, int F,
+                                  const int32_t* labels, const int32_t* idx, const int32_t* shift, int C, int B,
+                                  int chunk, float temperature, int cost, const float* d_clip, const float* d_sigma,
+                                  const uint8_t* dp_of_client, const double* d_z, float* scale, float* workspace,
+                                  float* grads, int64_t grad_pitch, int* err, hipStream_t s);
+size_t client_grad_scale_bytes(int chunk, int B);
+void client_dp_noise(double* out, size_t n);  // host: the standard-normal draws of addGaussian
 int64_t client_grad_len();  // 22961
 size_t client_grad_workspace_bytes(int chunk, int B);
 int client_grad_chunk(int C, int B);

@@ -782,10 +782,11 @@ int fleet_rmodel_evaluate(fleet_rmodel* m, int version, const float* images, siz
   return FLEET_OK;
 }
 
-int fleet_rmodel_client_grads_device(fleet_rmodel* m, const int32_t* versions, const void* d_images, size_t n_images,
-                                     int F, const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
-                                     float temperature, void* d_grads, size_t grad_pitch, void* d_uploads,
-                                     size_t upload_pitch, void* stream) {
+int fleet_rmodel_client_ex_grads_device(fleet_rmodel* m, const int32_t* versions, const void* d_images, size_t n_images,
+                                        int F, const void* d_labels, const void* d_idx, const void* d_shift, int C,
+                                        int B, float temperature, int cost, const float* clip, const float* sigma,
+                                        void* d_grads, size_t grad_pitch, void* d_uploads, size_t upload_pitch,
+                                        void* stream) {
   if (!m) return FLEET_ERR_ARG;
   std::lock_guard<std::mutex> lk(m->mu);
   RM_SCOPE(m);
@@ -814,12 +815,21 @@ int fleet_rmodel_client_grads_device(fleet_rmodel* m, const int32_t* versions, c
   }
   // pageable source: the copy has left `rows` when the call returns
   RM_HIP(m, hipMemcpyAsync(m->d_client_rows, rows.data(), 4 * (size_t)C, hipMemcpyHostToDevice, s));
-  if ((rc = fleet_client_grads_device(m->ctx, m->state, m->stride, n_rows, m->d_client_rows, d_images, n_images, F,
-                                      d_labels, d_idx, d_shift, C, B, temperature, d_grads, grad_pitch, d_uploads,
-                                      upload_pitch, (void*)s)))
-    return rfail(m, rc, "client gradients: %s", rc == FLEET_ERR_ARG ? "C*B images without indices, a row pitch >= 22961, an upload pitch of whole groups"
+  if ((rc = fleet_client_ex_grads_device(m->ctx, m->state, m->stride, n_rows, m->d_client_rows, d_images, n_images, F,
+                                         d_labels, d_idx, d_shift, C, B, temperature, cost, clip, sigma, d_grads,
+                                         grad_pitch, d_uploads, upload_pitch, (void*)s)))
+    return rfail(m, rc, "client gradients: %s", rc == FLEET_ERR_ARG ? "C*B images without indices, a row pitch >= 22961, an upload pitch of whole groups, a cost and DP parameters in range"
                                                                      : fleet_last_error(m->ctx));
   return FLEET_OK;
+}
+
+int fleet_rmodel_client_grads_device(fleet_rmodel* m, const int32_t* versions, const void* d_images, size_t n_images,
+                                     int F, const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
+                                     float temperature, void* d_grads, size_t grad_pitch, void* d_uploads,
+                                     size_t upload_pitch, void* stream) {
+  return fleet_rmodel_client_ex_grads_device(m, versions, d_images, n_images, F, d_labels, d_idx, d_shift, C, B,
+                                             temperature, FLEET_COST_CROSS_ENTROPY, nullptr, nullptr, d_grads,
+                                             grad_pitch, d_uploads, upload_pitch, stream);
 }
 
 int fleet_rmodel_stats(fleet_rmodel* m, size_t* resident_bytes, int* device_allocs) {

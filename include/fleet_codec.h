@@ -919,8 +919,8 @@ int fleet_evaluate(fleet_ctx* ctx, const float* w, size_t n_w, const float* b, s
  * to the reference whenever no intermediate is NaN. A sample whose E is NaN (the reference
  * bails) is reported by fleet_check as FLEET_ERR_ARG, its client's row then unspecified; with a
  * NaN met only in the backward pass, NaN positions and bit patterns are not pinned.
- * Not covered: DPgradients, the distillation cost, the client's own descent, the reference's
- * thread race. */
+ * DPgradients and the distillation cost: the _ex_ forms below. Not covered: the client's own
+ * descent, the reference's thread race. */
 size_t fleet_client_grad_len(void);
 /* tests: walk the clients in chunks of at most max_clients (0: the default, what fits a
  * 256 MiB workspace of per-sample rows); returns the previous value */
@@ -948,6 +948,52 @@ int fleet_client_grads_device(fleet_ctx* ctx, const void* d_models, size_t model
 int fleet_client_grads(fleet_ctx* ctx, const float* w, size_t n_w, const float* b, size_t n_b, const float* images,
                        size_t n_images, int F, const int32_t* labels, const int32_t* idx, const int32_t* shifts, int C,
                        int B, float temperature, float* grads, char* uploads, size_t upload_pitch);
+
+/* The two other configurations of getGradients: the distillation cost and DPgradients.
+ * (The names carry `_ex_` in the middle; the argument lists are those of fleet_client_grads,
+ * fleet_client_grads_device and fleet_rmodel_client_grads_device with cost, clip and sigma
+ * after temperature.)
+ * cost: FLEET_COST_CROSS_ENTROPY, or FLEET_COST_DISTILLATION for start_epoch("distillation")
+ * (cppNN-lib.cpp:251-252 under DISTILLATION_MODE 1): the output delta is
+ * distillation::d_cost(node, target, teacher, T) * softmax::df(node, j, 10, T)
+ * (commonLib/cppNN/network.h:1959, cost.h:93-113, activation.h:301-304) with T = temperature;
+ * d_cost never reads the teacher's value, so no soft labels are taken. E stays the mean of
+ * mse::cost.
+ * clip, sigma: host float[C], both NULL for no DP, else both given. Client c with sigma[c] > 0
+ * gets what cnn.DPgradients(clip[c], sigma[c]) returns (cppNN-lib.cpp:218-219, 295-296;
+ * network.h:1092-1181): scale_gradients over batch slots 1 .. B-1 (sqsum in binary32 in the
+ * reference's walk, layers last to first, each layer's dW block then its dbias block;
+ * scale = 1 / max(1, sqrt(sqsum) / clip); slot 0 is never clipped; as written there only the
+ * dbias blocks are multiplied by scale, no dW is: both kept), the ordered sum, then
+ * addGaussian(C * sigma) (:1125-1130) on every slot and the sizes written back over the header
+ * slots. The draws are fleet_client_dp_noise's, the same on every call, as the reference
+ * default-constructs its engine on every call. A client with sigma[c] == 0 gets
+ * cnn.gradients(), exactly the rows of the calls above. The arrays are copied to the device
+ * on the call's stream before the launches (pageable source: the copy has left them when the
+ * call returns).
+ * FLEET_ERR_ARG before any launch, besides the refusals of the calls above: an unknown cost;
+ * one of clip / sigma NULL and the other not; a negative or non-finite sigma; with sigma > 0,
+ * a clip that is <= 0 or non-finite. */
+#define FLEET_COST_CROSS_ENTROPY 0
+#define FLEET_COST_DISTILLATION 1
+/* fleet_client_grads_device (cppNN-lib.cpp:101-113, 218-234, 251-252; network.h:1092-1181) */
+int fleet_client_ex_grads_device(fleet_ctx* ctx, const void* d_models, size_t model_pitch, int n_models,
+                                 const void* d_model_of_client, const void* d_images, size_t n_images, int F,
+                                 const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
+                                 float temperature, int cost, const float* clip, const float* sigma, void* d_grads,
+                                 size_t grad_pitch, void* d_uploads, size_t upload_pitch, void* stream);
+/* fleet_client_grads (cppNN-lib.cpp:101-113, 218-234, 251-252; network.h:1092-1181) */
+int fleet_client_ex_grads(fleet_ctx* ctx, const float* w, size_t n_w, const float* b, size_t n_b, const float* images,
+                          size_t n_images, int F, const int32_t* labels, const int32_t* idx, const int32_t* shifts,
+                          int C, int B, float temperature, int cost, const float* clip, const float* sigma,
+                          float* grads, char* uploads, size_t upload_pitch);
+/* host only: the first n (<= 22961) of the standard-normal draws addGaussian adds, before they
+ * are scaled by C * sigma (network.h:1125-1130): std::normal_distribution<double>(0.0, 1.0) on
+ * a default-constructed std::default_random_engine, from the C++ library this one is built
+ * with, as the reference client's come from its own. The library makes the table once, on
+ * the first DP call, on the host; a context uploads it on its own first DP call and keeps it
+ * resident. Nothing of it is computed on the device. */
+int fleet_client_dp_noise(double* out, size_t n);
 
 /* Kardam bookkeeping of CppNNUpdater.update (Server/src/main/java/apps/cppNN/
  * CppNNUpdater.java:463-481, utils/Kardam.java:48-62) for the M
@@ -1224,6 +1270,13 @@ int fleet_rmodel_client_grads_device(fleet_rmodel* m, const int32_t* versions, c
                                      int F, const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
                                      float temperature, void* d_grads, size_t grad_pitch, void* d_uploads,
                                      size_t upload_pitch, void* stream);
+/* fleet_rmodel_client_grads_device with the cost and the DP parameters of
+ * fleet_client_ex_grads_device (cppNN-lib.cpp:218-221, 251-252; network.h:1092-1181) */
+int fleet_rmodel_client_ex_grads_device(fleet_rmodel* m, const int32_t* versions, const void* d_images, size_t n_images,
+                                        int F, const void* d_labels, const void* d_idx, const void* d_shift, int C,
+                                        int B, float temperature, int cost, const float* clip, const float* sigma,
+                                        void* d_grads, size_t grad_pitch, void* d_uploads, size_t upload_pitch,
+                                        void* stream);
 
 /* The offline sampler's state (the CppNNOfflineSampler natives
  * of Server/src/main/c++/cppNN_backend.cpp and the globals they keep). Random
