@@ -32,6 +32,7 @@ static_assert(FLEET_MAX_HEADERS == fleet::kMaxHeaderSlots, "the kernels size the
 #include "model_codec.h"
 #include "codec_device.h"
 #include "mledger_table.h"
+#include "dev_mem.h"
 
 #define FLEET_VERSION "fleet-mi355x 0.1.0 (gfx950)"
 
@@ -97,64 +98,53 @@ class WorkerPool {
   bool stop_ = false;
 };
 
-struct fleet_ctx {
+struct FLEET_MEM_LOCAL fleet_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   std::mutex mu;
   std::string err;
-  // device buffers (grown on demand)
-  uint8_t* d_a = nullptr;
-  size_t d_a_cap = 0;
-  uint8_t* d_b = nullptr;
-  size_t d_b_cap = 0;
-  uint8_t* d_out = nullptr;
-  size_t d_out_cap = 0;
-  float* d_f32 = nullptr;
-  size_t d_f32_cap = 0;
-  double* d_dampen = nullptr;
-  size_t d_dampen_cap = 0;
-  int32_t* d_hdr = nullptr;  // {status, count, walk_end, 0, positions[FLEET_MAX_HEADERS]}
-  int* d_err = nullptr;
+  // device buffers, grown on demand by doubling; the old allocation is freed
+  fleet::DevBuf<uint8_t> d_a, d_b, d_out;
+  fleet::DevBuf<float> d_f32;
+  fleet::DevBuf<double> d_dampen;
+  fleet::DevBuf<int32_t> d_hdr;  // {status, count, walk_end, 0, positions[FLEET_MAX_HEADERS]}
+  fleet::DevBuf<int> d_err;
   // Device-resident entry points (fleet_*_device) run on the CALLER's stream and
   // may be captured into HIP graphs, so they own parameter buffers of their own:
   // nothing the host-buffer entry points do on the context's stream touches
   // them, and a buffer a captured graph may reference is never freed before
   // fleet_destroy (a grown dampen buffer is retired, not freed).
-  double* d_dev_dampen = nullptr;
-  size_t d_dev_dampen_cap = 0;
-  int32_t* d_dev_hdr = nullptr;
-  int* d_dev_err = nullptr;           // read by fleet_check
-  std::vector<void*> retired;         // freed in fleet_destroy
+  fleet::DevBuf<double> d_dev_dampen;  // retired on growth
+  fleet::DevBuf<int32_t> d_dev_hdr;
+  fleet::DevBuf<int> d_dev_err;       // read by fleet_check
+  fleet::Retired retired;             // freed in fleet_destroy
   std::vector<double> dev_dampen;     // what d_dev_dampen holds
   std::vector<int32_t> dev_hdr;       // what d_dev_hdr holds
   bool dev_params_valid = false;
-  double* d_partials = nullptr;
-  size_t d_partials_cap = 0;
+  fleet::DevBuf<double> d_partials;
   // pinned host staging
-  uint8_t* h_stage = nullptr;
-  size_t h_stage_cap = 0;
-  int32_t* h_hdr = nullptr;
-  int* h_err = nullptr;
+  fleet::PinBuf<uint8_t> h_stage;  // grown by doubling
+  fleet::PinBuf<int32_t> h_hdr;
+  fleet::PinBuf<int> h_err;
   std::unique_ptr<WorkerPool> pool;  // staging copy threads (stage_uploads)
   int last_ingress = FLEET_INGRESS_NONE;  // how the last host-buffer update reached HBM
-  // the pipelined Kardam form's tile flags (zeroed at allocation) and its launch epoch
-  uint32_t* d_kflags = nullptr;
-  size_t d_kflags_cap = 0;
+  // the pipelined Kardam form's tile flags (zeroed at allocation) and its launch epoch.
+  // FREED on growth although a device-resident entry point uses it on the caller's stream
+  // (its siblings below are retired): the call that grows it is synchronous
+  fleet::DevBuf<uint32_t> d_kflags;
   uint32_t kflag_epoch = 0;
   uint32_t kflag_test_skew = 0;       // fleet_test_kardam_skew: reduce blocks wait for a later epoch
   // fleet_evaluate_device: the costs and predictions a caller does not take, [B floats | B int32]
-  // (a grown buffer is retired, not freed: an evaluation on another stream may still write it)
-  uint8_t* d_eval = nullptr;
-  int d_eval_cap = 0;  // the B it holds
-  // fleet_client_grads_device: the per-sample gradient rows of one chunk of clients (retired, not
-  // freed, when it grows, for the same reason)
-  float* d_client_ws = nullptr;
-  size_t d_client_ws_cap = 0;  // bytes
-  // the DP forms: clip[C] then sigma[C] of the call (retired when it grows), and the 22961
+  // in 8 bytes per image (retired on growth, not freed: an evaluation on another stream may
+  // still write it)
+  fleet::DevBuf<uint8_t> d_eval;
+  // fleet_client_grads_device: the per-sample gradient rows of one chunk of clients (retired on
+  // growth, for the same reason)
+  fleet::DevBuf<uint8_t> d_client_ws;
+  // the DP forms: clip[C] then sigma[C] of the call (retired on growth), and the 22961
   // standard-normal draws, made on the host on the first DP call and resident from then on
-  float* d_client_dp = nullptr;
-  int d_client_dp_cap = 0;  // the C it holds
-  double* d_dp_z = nullptr;
+  fleet::DevBuf<float> d_client_dp;
+  fleet::DevBuf<double> d_dp_z;
 };
 
 namespace {
@@ -201,33 +191,22 @@ struct DeviceGuard {
   DeviceGuard device_guard_((ctx)->device);                                                     \
   if (!device_guard_.ok) return fail((ctx), FLEET_ERR_HIP, "hipSetDevice(%d) failed", (ctx)->device)
 
+// an allocation failure as every grow reports it: the call's name, the bytes asked for, HIP's reason
+int nomem(fleet_ctx* c, const char* call, size_t bytes, hipError_t e) {
+  return fail(c, FLEET_ERR_NOMEM, "%s(%zu): %s", call, bytes, hipGetErrorString(e));
+}
+
 template <typename T>
-int grow_dev(fleet_ctx* c, T** p, size_t* cap, size_t need_elems) {
-  if (need_elems <= *cap) return FLEET_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  size_t n = std::max(need_elems, *cap * 2);
-  hipError_t e = hipMalloc((void**)p, n * sizeof(T) + 64);
-  if (e != hipSuccess) {
-    *cap = 0;
-    return fail(c, FLEET_ERR_NOMEM, "hipMalloc(%zu): %s", n * sizeof(T), hipGetErrorString(e));
-  }
-  *cap = n;
-  return FLEET_OK;
+int grow_dev(fleet_ctx* c, fleet::DevBuf<T>& b, size_t need_elems) {
+  const size_t n = std::max(need_elems, b.cap() * 2);
+  const hipError_t e = b.grow_doubling(need_elems);
+  return e == hipSuccess ? FLEET_OK : nomem(c, "hipMalloc", n * sizeof(T), e);
 }
 
 int grow_pinned(fleet_ctx* c, size_t need) {
-  if (need <= c->h_stage_cap) return FLEET_OK;
-  if (c->h_stage) (void)hipHostFree(c->h_stage);
-  c->h_stage = nullptr;
-  size_t n = std::max(need, c->h_stage_cap * 2);
-  hipError_t e = hipHostMalloc((void**)&c->h_stage, n + 64, hipHostMallocDefault);
-  if (e != hipSuccess) {
-    c->h_stage_cap = 0;
-    return fail(c, FLEET_ERR_NOMEM, "hipHostMalloc(%zu): %s", n, hipGetErrorString(e));
-  }
-  c->h_stage_cap = n;
-  return FLEET_OK;
+  const size_t n = std::max(need, c->h_stage.cap() * 2);
+  const hipError_t e = c->h_stage.grow_doubling(need);
+  return e == hipSuccess ? FLEET_OK : nomem(c, "hipHostMalloc", n, e);
 }
 
 inline size_t round16(size_t x) { return (x + 15) / 16 * 16; }
@@ -239,12 +218,12 @@ inline size_t groups_of(size_t n_values) { return (n_values + 2) / 3; }
 hipStream_t pick(fleet_ctx*, void* s) { return (hipStream_t)s; }
 
 // Copy host text (len chars) into device buffer padded to 16-byte groups.
-int stage_text(fleet_ctx* c, const char* text, size_t len, uint8_t** dbuf, size_t* dcap) {
+int stage_text(fleet_ctx* c, const char* text, size_t len, fleet::DevBuf<uint8_t>& dbuf) {
   size_t padded = round16(len) + 16;
-  int rc = grow_dev(c, dbuf, dcap, padded);
+  int rc = grow_dev(c, dbuf, padded);
   if (rc) return rc;
-  HIP_TRY(c, hipMemsetAsync(*dbuf + (len & ~(size_t)15), 0, padded - (len & ~(size_t)15), c->stream));
-  if (len) HIP_TRY(c, hipMemcpyAsync(*dbuf, text, len, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemsetAsync(dbuf + (len & ~(size_t)15), 0, padded - (len & ~(size_t)15), c->stream));
+  if (len) HIP_TRY(c, hipMemcpyAsync(dbuf, text, len, hipMemcpyHostToDevice, c->stream));
   return FLEET_OK;
 }
 
@@ -428,9 +407,9 @@ int update_host_fallback(fleet_ctx* c, const char* const* uploads, size_t len, i
                          char* merged, float* merged_f32) {
   const size_t n = fleet_b64_count(len), groups = groups_of(n), pitch = round16(len), total = pitch * (size_t)M;
   int rc;
-  if ((rc = grow_dev(c, &c->d_dampen, &c->d_dampen_cap, (size_t)M))) return rc;
-  if ((rc = grow_dev(c, &c->d_out, &c->d_out_cap, 16 * groups + 16))) return rc;
-  if (merged_f32 && (rc = grow_dev(c, &c->d_f32, &c->d_f32_cap, 3 * groups + 3))) return rc;
+  if ((rc = grow_dev(c, c->d_dampen, (size_t)M))) return rc;
+  if ((rc = grow_dev(c, c->d_out, 16 * groups + 16))) return rc;
+  if (merged_f32 && (rc = grow_dev(c, c->d_f32, 3 * groups + 3))) return rc;
   if ((rc = stage_uploads(c, uploads, 0, len, pitch, M, 0, stage_threads(total)))) return rc;
   std::memcpy(c->h_stage + total, dampen, sizeof(double) * (size_t)M);
   HIP_TRY(c, hipMemcpyAsync(c->d_dampen, c->h_stage + total, sizeof(double) * (size_t)M, hipMemcpyHostToDevice,
@@ -472,15 +451,15 @@ int fleet_create(int device, fleet_ctx** out) {
   DeviceGuard dg(device);
   if (!dg.ok) return bail(FLEET_ERR_HIP);
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(FLEET_ERR_HIP);
-  if (hipMalloc((void**)&c->d_hdr, kHdrWords * sizeof(int32_t)) != hipSuccess) return bail(FLEET_ERR_NOMEM);
-  if (hipMalloc((void**)&c->d_err, 64) != hipSuccess) return bail(FLEET_ERR_NOMEM);
+  constexpr size_t kErrWords = 64 / sizeof(int);  // an error word in 64 bytes of its own
+  if (c->d_hdr.alloc(kHdrWords) != hipSuccess) return bail(FLEET_ERR_NOMEM);
+  if (c->d_err.alloc(kErrWords) != hipSuccess) return bail(FLEET_ERR_NOMEM);
   if (hipMemset(c->d_err, 0, 64) != hipSuccess) return bail(FLEET_ERR_HIP);
-  if (hipMalloc((void**)&c->d_dev_hdr, kHdrWords * sizeof(int32_t)) != hipSuccess) return bail(FLEET_ERR_NOMEM);
-  if (hipMalloc((void**)&c->d_dev_err, 64) != hipSuccess) return bail(FLEET_ERR_NOMEM);
+  if (c->d_dev_hdr.alloc(kHdrWords) != hipSuccess) return bail(FLEET_ERR_NOMEM);
+  if (c->d_dev_err.alloc(kErrWords) != hipSuccess) return bail(FLEET_ERR_NOMEM);
   if (hipMemset(c->d_dev_err, 0, 64) != hipSuccess) return bail(FLEET_ERR_HIP);
-  if (hipHostMalloc((void**)&c->h_hdr, kHdrWords * sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
-    return bail(FLEET_ERR_NOMEM);
-  if (hipHostMalloc((void**)&c->h_err, 64, hipHostMallocDefault) != hipSuccess) return bail(FLEET_ERR_NOMEM);
+  if (c->h_hdr.alloc(kHdrWords) != hipSuccess) return bail(FLEET_ERR_NOMEM);
+  if (c->h_err.alloc(kErrWords) != hipSuccess) return bail(FLEET_ERR_NOMEM);
   (void)rc;
   *out = c;
   return FLEET_OK;
@@ -489,16 +468,9 @@ int fleet_create(int device, fleet_ctx** out) {
 void fleet_destroy(fleet_ctx* c) {
   if (!c) return;
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (void* p : {(void*)c->d_a, (void*)c->d_b, (void*)c->d_out, (void*)c->d_f32, (void*)c->d_dampen,
-                  (void*)c->d_hdr, (void*)c->d_err, (void*)c->d_partials, (void*)c->d_dev_dampen,
-                  (void*)c->d_dev_hdr, (void*)c->d_dev_err, (void*)c->d_kflags, (void*)c->d_eval,
-                  (void*)c->d_client_ws, (void*)c->d_client_dp, (void*)c->d_dp_z})
-    if (p) (void)hipFree(p);
-  for (void* p : c->retired) (void)hipFree(p);
-  for (void* p : {(void*)c->h_stage, (void*)c->h_hdr, (void*)c->h_err})
-    if (p) (void)hipHostFree(p);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  hipStream_t s = c->stream;
+  delete c;  // the buffers and the retired allocations go with it
+  if (s) (void)hipStreamDestroy(s);
 }
 
 const char* fleet_last_error(const fleet_ctx* c) { return c ? c->err.c_str() : "no context"; }
@@ -569,7 +541,7 @@ int fleet_layout_parse(fleet_ctx* c, const char* upload, size_t len, int32_t* he
   int rc = check_text_len(c, len);
   if (rc) return rc;
   size_t n = fleet_b64_count(len);
-  if ((rc = stage_text(c, upload, len, &c->d_a, &c->d_a_cap))) return rc;
+  if ((rc = stage_text(c, upload, len, c->d_a))) return rc;
   int nh = 0;
   size_t walk_end = n;
   if ((rc = parse_layout(c, c->d_a, n, &nh, &walk_end))) return rc;
@@ -586,8 +558,8 @@ int fleet_encode_f32(fleet_ctx* c, const float* values, size_t n, char* out, siz
   std::lock_guard<std::mutex> lk(c->mu);
   DEVICE_SCOPE(c);
   int rc;
-  if ((rc = grow_dev(c, &c->d_f32, &c->d_f32_cap, n + 3))) return rc;
-  if ((rc = grow_dev(c, &c->d_out, &c->d_out_cap, 16 * groups_of(n) + 16))) return rc;
+  if ((rc = grow_dev(c, c->d_f32, n + 3))) return rc;
+  if ((rc = grow_dev(c, c->d_out, 16 * groups_of(n) + 16))) return rc;
   if (n) HIP_TRY(c, hipMemcpyAsync(c->d_f32, values, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, fleet::launch_encode_f32(c->d_f32, (int64_t)n, 0, 1, c->d_out, 0, c->stream));
   return finish_text(c, fleet_b64_len(n), out, cap, out_len);
@@ -598,10 +570,10 @@ int fleet_encode_i32(fleet_ctx* c, const int32_t* codes, size_t n, char* out, si
   std::lock_guard<std::mutex> lk(c->mu);
   DEVICE_SCOPE(c);
   int rc;
-  if ((rc = grow_dev(c, &c->d_a, &c->d_a_cap, 4 * n + 16))) return rc;
-  if ((rc = grow_dev(c, &c->d_out, &c->d_out_cap, 16 * groups_of(n) + 16))) return rc;
+  if ((rc = grow_dev(c, c->d_a, 4 * n + 16))) return rc;
+  if ((rc = grow_dev(c, c->d_out, 16 * groups_of(n) + 16))) return rc;
   if (n) HIP_TRY(c, hipMemcpyAsync(c->d_a, codes, n * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, fleet::launch_encode_i32((const int32_t*)c->d_a, (int64_t)n, c->d_out, c->stream));
+  HIP_TRY(c, fleet::launch_encode_i32((const int32_t*)c->d_a.get(), (int64_t)n, c->d_out, c->stream));
   return finish_text(c, fleet_b64_len(n), out, cap, out_len);
 }
 
@@ -615,8 +587,8 @@ static int decode_common(fleet_ctx* c, const char* text, size_t len, void* out, 
   size_t n = fleet_b64_count(len);
   if (n_out) *n_out = n;
   if (cap < n) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu values", cap, n);
-  if ((rc = stage_text(c, text, len, &c->d_a, &c->d_a_cap))) return rc;
-  if ((rc = grow_dev(c, &c->d_f32, &c->d_f32_cap, n + 3))) return rc;
+  if ((rc = stage_text(c, text, len, c->d_a))) return rc;
+  if ((rc = grow_dev(c, c->d_f32, n + 3))) return rc;
   HIP_TRY(c, fleet::launch_decode(c->d_a, (int64_t)n, 0, 1, c->d_f32, 0, as_codes, c->d_err, c->stream));
   if (n) HIP_TRY(c, hipMemcpyAsync(out, c->d_f32, n * 4, hipMemcpyDeviceToHost, c->stream));
   return read_err(c, c->stream);
@@ -638,13 +610,13 @@ int fleet_flat_gradient(fleet_ctx* c, const char* g, size_t len, char* out, size
   int rc = check_text_len(c, len);
   if (rc) return rc;
   size_t n = fleet_b64_count(len);
-  if ((rc = stage_text(c, g, len, &c->d_a, &c->d_a_cap))) return rc;
+  if ((rc = stage_text(c, g, len, c->d_a))) return rc;
   int nh = 0;
   size_t walk_end = 0;
   if ((rc = parse_layout(c, c->d_a, n, &nh, &walk_end))) return rc;
   // network::flatGrad stops after the last bias block: values past the walk are dropped
   const size_t n_flat = walk_end - (size_t)nh;
-  if ((rc = grow_dev(c, &c->d_out, &c->d_out_cap, 16 * groups_of(n_flat) + 16))) return rc;
+  if ((rc = grow_dev(c, c->d_out, 16 * groups_of(n_flat) + 16))) return rc;
   HIP_TRY(c, fleet::launch_flat(c->d_a, c->d_hdr + 4, nh, (int64_t)n_flat, c->d_out, c->d_err, c->stream));
   return finish_text(c, fleet_b64_len(n_flat), out, cap, out_len);
 }
@@ -657,14 +629,14 @@ int fleet_merge_flat_gradient(fleet_ctx* c, const char* g, size_t glen, const ch
   int rc = check_text_len(c, glen);
   if (rc || (rc = check_text_len(c, flen))) return rc;
   size_t n = fleet_b64_count(glen), nf = fleet_b64_count(flen);
-  if ((rc = stage_text(c, g, glen, &c->d_a, &c->d_a_cap))) return rc;
-  if ((rc = stage_text(c, flat, flen, &c->d_b, &c->d_b_cap))) return rc;
+  if ((rc = stage_text(c, g, glen, c->d_a))) return rc;
+  if ((rc = stage_text(c, flat, flen, c->d_b))) return rc;
   int nh = 0;
   size_t walk_end = 0;
   if ((rc = parse_layout(c, c->d_a, n, &nh, &walk_end))) return rc;
   if (nf < walk_end - (size_t)nh)
     return fail(c, FLEET_ERR_ARG, "flat gradient has %zu values, layout needs %zu", nf, walk_end - (size_t)nh);
-  if ((rc = grow_dev(c, &c->d_out, &c->d_out_cap, 16 * groups_of(n) + 16))) return rc;
+  if ((rc = grow_dev(c, c->d_out, 16 * groups_of(n) + 16))) return rc;
   HIP_TRY(c, fleet::launch_merge(c->d_a, c->d_b, c->d_hdr + 4, nh, (int64_t)walk_end, (int64_t)n, c->d_out,
                                  c->d_err, c->stream));
   return finish_text(c, glen, out, cap, out_len);
@@ -678,13 +650,13 @@ static int elementwise(fleet_ctx* c, const char* a, size_t alen, const char* b, 
   int rc = check_text_len(c, alen);
   if (rc) return rc;
   size_t n = fleet_b64_count(alen);
-  if ((rc = stage_text(c, a, alen, &c->d_a, &c->d_a_cap))) return rc;
+  if ((rc = stage_text(c, a, alen, c->d_a))) return rc;
   if (op) {
     if ((rc = check_text_len(c, blen))) return rc;
     if (fleet_b64_count(blen) < n) return fail(c, FLEET_ERR_ARG, "second operand shorter than the first");
-    if ((rc = stage_text(c, b, blen, &c->d_b, &c->d_b_cap))) return rc;
+    if ((rc = stage_text(c, b, blen, c->d_b))) return rc;
   }
-  if ((rc = grow_dev(c, &c->d_out, &c->d_out_cap, 16 * groups_of(n) + 16))) return rc;
+  if ((rc = grow_dev(c, c->d_out, 16 * groups_of(n) + 16))) return rc;
   HIP_TRY(c, fleet::launch_elementwise(c->d_a, op ? c->d_b : c->d_a, op, s, (int64_t)n, c->d_out, c->d_err,
                                        c->stream));
   return finish_text(c, fleet_b64_len(n), out, cap, out_len);
@@ -709,9 +681,9 @@ int fleet_norm(fleet_ctx* c, const char* v, size_t len, double* out) {
   int rc = check_text_len(c, len);
   if (rc) return rc;
   size_t n = fleet_b64_count(len);
-  if ((rc = stage_text(c, v, len, &c->d_a, &c->d_a_cap))) return rc;
+  if ((rc = stage_text(c, v, len, c->d_a))) return rc;
   size_t blocks = (groups_of(n) + 255) / 256 + 1;
-  if ((rc = grow_dev(c, &c->d_partials, &c->d_partials_cap, blocks))) return rc;
+  if ((rc = grow_dev(c, c->d_partials, blocks))) return rc;
   int nb = 0;
   HIP_TRY(c, fleet::launch_norm_partials(c->d_a, (int64_t)n, c->d_partials, &nb, c->d_err, c->stream));
   std::vector<double> part((size_t)nb);
@@ -772,7 +744,7 @@ int update_window(fleet_ctx* c, const char* const* uploads, size_t len, int M, c
   const size_t o_f32 = round16(o_out + wpitch + 16), o_end = o_f32 + sizeof(float) * (3 * w + 3);
   int rc;
   if ((rc = grow_pinned(c, o_end + 64))) return rc;
-  if ((rc = grow_dev(c, &c->d_a, &c->d_a_cap, o_end + 64))) return rc;
+  if ((rc = grow_dev(c, c->d_a, o_end + 64))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // staging buffer reuse
   std::memcpy(c->h_stage + o_hdr, hw, sizeof(int32_t) * kHdrWords);
   std::memcpy(c->h_stage + o_damp, dampen, sizeof(double) * (size_t)M);
@@ -979,12 +951,8 @@ int fleet_host_unregister(fleet_ctx* c, void* ptr) {
 
 namespace {
 
-struct DevMem {
-  void* p = nullptr;
-  ~DevMem() {
-    if (p) (void)hipFree(p);
-  }
-};
+using fleet::DevBuf;
+using fleet::PinBuf;
 
 // A caller's header list for an upload of n values: the kernels search it, so the
 // positions are strictly ascending and inside [0, n).
@@ -1023,12 +991,9 @@ int dev_params(fleet_ctx* c, hipStream_t s, size_t n, int M, const double* dampe
                   "with them before capturing");
     (void)hipGetLastError();
     HIP_TRY(c, hipStreamSynchronize(s));
-    if ((size_t)M > c->d_dev_dampen_cap) {  // grow; the old buffer may sit in a captured graph: retire it
-      if (c->d_dev_dampen) c->retired.push_back(c->d_dev_dampen);
-      c->d_dev_dampen = nullptr;
-      c->d_dev_dampen_cap = 0;
-      if ((rc = grow_dev(c, &c->d_dev_dampen, &c->d_dev_dampen_cap, (size_t)M))) return rc;
-    }
+    // grow; the old buffer may sit in a captured graph: retire it
+    const hipError_t eg = c->d_dev_dampen.grow_exact((size_t)M, 64, &c->retired);
+    if (eg != hipSuccess) return nomem(c, "hipMalloc", sizeof(double) * (size_t)M, eg);
     HIP_TRY(c, hipMemcpy(c->d_dev_dampen, dampen, sizeof(double) * (size_t)M, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->d_dev_hdr, hdr_words.data(), sizeof(int32_t) * hdr_words.size(), hipMemcpyHostToDevice));
     c->dev_dampen.assign(dampen, dampen + M);
@@ -1126,24 +1091,25 @@ int fleet_update_kardam_device(fleet_ctx* c, const void* d_uploads, size_t pitch
   // scratch: [partials M x slots x 2 | norms M x parts x 2 | has_prev M]; synchronous call (host outputs)
   const size_t o_norm = sizeof(double) * 2 * (size_t)M * n_waves;
   const size_t o_has = o_norm + sizeof(double) * 2 * (size_t)M * n_parts;
-  if ((rc = grow_dev(c, &c->d_b, &c->d_b_cap, o_has + (size_t)M + 64))) return rc;
+  if ((rc = grow_dev(c, c->d_b, o_has + (size_t)M + 64))) return rc;
   HIP_TRY(c, hipStreamSynchronize(s));
-  double* d_part = reinterpret_cast<double*>(c->d_b);
+  double* d_part = reinterpret_cast<double*>(c->d_b.get());
   double* d_norm = reinterpret_cast<double*>(c->d_b + o_norm);
   uint8_t* d_has = c->d_b + o_has;
   if (d_prev) HIP_TRY(c, hipMemcpy(d_has, has_prev, (size_t)M, hipMemcpyHostToDevice));
   fleet::KardamOut kd{lr, (const float*)d_prev, d_prev ? d_has : nullptr, vpitch, (float*)d_g_out, d_part};
-  if ((size_t)flags_sz > c->d_kflags_cap) {  // new flags start at 0, which no launch's epoch is
-    if (c->d_kflags) (void)hipFree(c->d_kflags);
-    c->d_kflags = nullptr;
-    c->d_kflags_cap = 0;
-    HIP_TRY(c, hipMalloc(&c->d_kflags, sizeof(uint32_t) * (size_t)flags_sz));
-    HIP_TRY(c, hipMemsetAsync(c->d_kflags, 0, sizeof(uint32_t) * (size_t)flags_sz, s));
-    c->d_kflags_cap = (size_t)flags_sz;
+  if ((size_t)flags_sz > c->d_kflags.cap()) {  // new flags start at 0, which no launch's epoch is
+    HIP_TRY(c, c->d_kflags.grow_exact((size_t)flags_sz));  // the old flags are freed (see the member)
+    const hipError_t ez = hipMemsetAsync(c->d_kflags, 0, sizeof(uint32_t) * (size_t)flags_sz, s);
+    if (ez != hipSuccess) {
+      c->d_kflags.reset();  // flags that were not zeroed are not kept
+      return fail(c, FLEET_ERR_HIP, "hipMemsetAsync(c->d_kflags, 0, sizeof(uint32_t) * (size_t)flags_sz, s): %s",
+                  hipGetErrorString(ez));
+    }
     c->kflag_epoch = 0;
   }
   if (++c->kflag_epoch == 0) {  // wrapped: every flag back to 0 before epoch 1 is used again
-    if (c->d_kflags_cap) HIP_TRY(c, hipMemsetAsync(c->d_kflags, 0, sizeof(uint32_t) * c->d_kflags_cap, s));
+    if (c->d_kflags.cap()) HIP_TRY(c, hipMemsetAsync(c->d_kflags, 0, sizeof(uint32_t) * c->d_kflags.cap(), s));
     c->kflag_epoch = 1;
   }
   int nw = 0, np = 1, nf = 0;
@@ -1229,15 +1195,16 @@ int fleet_synth_window_device(fleet_ctx* c, uint64_t seed, int M, int client0, s
       return fail(c, FLEET_ERR_ARG, "synth: header position %d (%d) is outside [0, %zu)", i, header_pos[i], n_up);
   DEVICE_SCOPE(c);
   hipStream_t s = pick(c, stream);
-  DevMem d_pos, d_val;  // freed on every path
+  DevBuf<int32_t> d_pos;  // freed on every path
+  DevBuf<float> d_val;
   if (n_headers) {
-    HIP_TRY(c, hipMalloc(&d_pos.p, sizeof(int32_t) * (size_t)n_headers));
-    HIP_TRY(c, hipMalloc(&d_val.p, sizeof(float) * (size_t)n_headers));
-    HIP_TRY(c, hipMemcpy(d_pos.p, header_pos, sizeof(int32_t) * (size_t)n_headers, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(d_val.p, header_val, sizeof(float) * (size_t)n_headers, hipMemcpyHostToDevice));
+    HIP_TRY(c, d_pos.alloc((size_t)n_headers));
+    HIP_TRY(c, d_val.alloc((size_t)n_headers));
+    HIP_TRY(c, hipMemcpy(d_pos, header_pos, sizeof(int32_t) * (size_t)n_headers, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_val, header_val, sizeof(float) * (size_t)n_headers, hipMemcpyHostToDevice));
   }
-  HIP_TRY(c, fleet::launch_synth(seed, client0, (int64_t)elem0, M, (int64_t)n_up, (float*)d_values, vpitch,
-                                 (const int32_t*)d_pos.p, (const float*)d_val.p, n_headers, s));
+  HIP_TRY(c, fleet::launch_synth(seed, client0, (int64_t)elem0, M, (int64_t)n_up, (float*)d_values, vpitch, d_pos,
+                                 d_val, n_headers, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   return FLEET_OK;
 }
@@ -1260,20 +1227,19 @@ static int model_total(fleet_ctx* c, const int32_t* dims, int n_mats, size_t* n)
 
 // quantize + dictionary on the device; leaves d_index and the dictionary on the host
 static int model_run(fleet_ctx* c, const float* weights, const int32_t* dims, int n_mats, size_t n, float* quantized,
-              std::vector<float>* dict_host, int32_t* U, DevMem* d_index_keep) {
-  DevMem dw, dq, dd;
+              std::vector<float>* dict_host, int32_t* U, DevBuf<int32_t>* d_index_keep) {
+  DevBuf<float> dw, dq, dd;
   if (n) {
-    HIP_TRY(c, hipMalloc(&dw.p, n * sizeof(float)));
-    HIP_TRY(c, hipMalloc(&dq.p, n * sizeof(float)));
-    HIP_TRY(c, hipMalloc(&dd.p, n * sizeof(float)));
-    HIP_TRY(c, hipMalloc(&d_index_keep->p, n * sizeof(int32_t)));
-    HIP_TRY(c, hipMemcpyAsync(dw.p, weights, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, dw.alloc(n));
+    HIP_TRY(c, dq.alloc(n));
+    HIP_TRY(c, dd.alloc(n));
+    HIP_TRY(c, d_index_keep->alloc(n));
+    HIP_TRY(c, hipMemcpyAsync(dw, weights, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
   }
-  HIP_TRY(c, fleet::model_quantize_index((const float*)dw.p, dims, n_mats, (float*)dq.p, (float*)dd.p,
-                                         (int32_t*)d_index_keep->p, U, c->stream));
-  if (quantized && n) HIP_TRY(c, hipMemcpyAsync(quantized, dq.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, fleet::model_quantize_index(dw, dims, n_mats, dq, dd, *d_index_keep, U, c->stream));
+  if (quantized && n) HIP_TRY(c, hipMemcpyAsync(quantized, dq, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   dict_host->resize((size_t)*U);
-  if (*U) HIP_TRY(c, hipMemcpyAsync(dict_host->data(), dd.p, (size_t)*U * sizeof(float), hipMemcpyDeviceToHost,
+  if (*U) HIP_TRY(c, hipMemcpyAsync(dict_host->data(), dd, (size_t)*U * sizeof(float), hipMemcpyDeviceToHost,
                                     c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return FLEET_OK;
@@ -1292,12 +1258,12 @@ int fleet_model_quantize_index(fleet_ctx* c, const float* weights, const int32_t
   if (n && !weights) return FLEET_ERR_ARG;
   std::vector<float> dh;
   int32_t U = 0;
-  DevMem di;
+  DevBuf<int32_t> di;
   if ((rc = model_run(c, weights, dims, n_mats, n, quantized, &dh, &U, &di))) return rc;
   if (dict && U) std::memcpy(dict, dh.data(), sizeof(float) * (size_t)U);
   if (n_dict) *n_dict = U;
   if (index && n) {
-    HIP_TRY(c, hipMemcpy(index, di.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(index, di, n * sizeof(int32_t), hipMemcpyDeviceToHost));
   }
   return FLEET_OK;
 }
@@ -1313,7 +1279,7 @@ int fleet_model_weights_text(fleet_ctx* c, const float* weights, const int32_t* 
   if (n && !weights) return FLEET_ERR_ARG;
   std::vector<float> dh;
   int32_t U = 0;
-  DevMem di;
+  DevBuf<int32_t> di;
   if ((rc = model_run(c, weights, dims, n_mats, n, nullptr, &dh, &U, &di))) return rc;
   // header and dictionary lines: `ostream << int` / `ostream << float` (precision 6 == %g),
   // U lines of host formatting; the n index tokens are formatted on the device
@@ -1326,7 +1292,7 @@ int fleet_model_weights_text(fleet_ctx* c, const float* weights, const int32_t* 
     head += buf;
   }
   std::vector<char> body;
-  HIP_TRY(c, fleet::model_index_text((const int32_t*)di.p, dims, n_mats, &body, c->stream));
+  HIP_TRY(c, fleet::model_index_text(di, dims, n_mats, &body, c->stream));
   const size_t total = head.size() + body.size();
   if (out_len) *out_len = total;
   if (cap < total) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu", cap, total);
@@ -1385,12 +1351,12 @@ int fleet_values_text(fleet_ctx* c, const float* values, size_t n, const int64_t
   int rc = values_offsets(c, n, block_sizes, n_blocks, &off);
   if (rc) return rc;
   DEVICE_SCOPE(c);
-  DevMem dv;
+  DevBuf<float> dv;
   if (n) {
-    HIP_TRY(c, hipMalloc(&dv.p, n * sizeof(float)));
-    HIP_TRY(c, hipMemcpyAsync(dv.p, values, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, dv.alloc(n));
+    HIP_TRY(c, hipMemcpyAsync(dv, values, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
   }
-  return values_text_out(c, (const float*)dv.p, n, off, n_blocks, out, cap, out_len, c->stream);
+  return values_text_out(c, dv, n, off, n_blocks, out, cap, out_len, c->stream);
 }
 
 int fleet_model_read_weights(fleet_ctx* c, const char* text, size_t len, const int32_t* dims, int n_mats,
@@ -1431,22 +1397,24 @@ int fleet_model_read_weights(fleet_ctx* c, const char* text, size_t len, const i
     if (k == 0 || kv[k].first != kv[k - 1].first) keys.push_back(kv[k].first), vals.push_back(kv[k].second);
   const size_t body = (size_t)(p - t.c_str());
   const size_t blen = len - body;
-  DevMem dt, dk, dv, dw;
-  if (blen) HIP_TRY(c, hipMalloc(&dt.p, blen));
-  HIP_TRY(c, hipMalloc(&dk.p, sizeof(int32_t) * (keys.size() + 1)));
-  HIP_TRY(c, hipMalloc(&dv.p, sizeof(float) * (vals.size() + 1)));
-  if (n) HIP_TRY(c, hipMalloc(&dw.p, sizeof(float) * n));
-  if (blen) HIP_TRY(c, hipMemcpyAsync(dt.p, text + body, blen, hipMemcpyHostToDevice, c->stream));
+  DevBuf<uint8_t> dt;
+  DevBuf<int32_t> dk;
+  DevBuf<float> dv, dw;
+  if (blen) HIP_TRY(c, dt.alloc(blen));
+  HIP_TRY(c, dk.alloc(keys.size() + 1));
+  HIP_TRY(c, dv.alloc(vals.size() + 1));
+  if (n) HIP_TRY(c, dw.alloc(n));
+  if (blen) HIP_TRY(c, hipMemcpyAsync(dt, text + body, blen, hipMemcpyHostToDevice, c->stream));
   if (!keys.empty()) {
-    HIP_TRY(c, hipMemcpyAsync(dk.p, keys.data(), sizeof(int32_t) * keys.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(dv.p, vals.data(), sizeof(float) * vals.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dk, keys.data(), sizeof(int32_t) * keys.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dv, vals.data(), sizeof(float) * vals.size(), hipMemcpyHostToDevice, c->stream));
   }
   int status = 0;
-  HIP_TRY(c, fleet::model_read_index((const uint8_t*)dt.p, (int64_t)blen, (int64_t)n, (const int32_t*)dk.p,
-                                     (const float*)dv.p, (int32_t)keys.size(), (float*)dw.p, &status, c->stream));
+  HIP_TRY(c, fleet::model_read_index(dt, (int64_t)blen, (int64_t)n, dk, dv, (int32_t)keys.size(), dw, &status,
+                                     c->stream));
   if (status == 1) return fail(c, FLEET_ERR_ARG, "weights section: malformed index token");
   if (status == 2) return fail(c, FLEET_ERR_LAYOUT, "weights section: index count differs from the model size");
-  if (n) HIP_TRY(c, hipMemcpy(weights_out, dw.p, sizeof(float) * n, hipMemcpyDeviceToHost));
+  if (n) HIP_TRY(c, hipMemcpy(weights_out, dw, sizeof(float) * n, hipMemcpyDeviceToHost));
   return FLEET_OK;
 }
 
@@ -1498,7 +1466,7 @@ int fleet_kardam_grads(fleet_ctx* c, const char* const* uploads, const size_t* l
   const int nblk = (int)((groups + 255) / 256);
   const size_t o_part = round16(o_g + gpad * (size_t)M), o_end = o_part + sizeof(double) * 2 * (size_t)M * (nblk + 1);
   if ((rc = grow_pinned(c, o_end))) return rc;
-  if ((rc = grow_dev(c, &c->d_a, &c->d_a_cap, o_end))) return rc;
+  if ((rc = grow_dev(c, c->d_a, o_end))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // staging buffer reuse
   uint8_t* h = c->h_stage;
   for (int i = 0; i < M; ++i) {
@@ -1576,7 +1544,7 @@ int fleet_minibatch(fleet_ctx* c, const float* images, size_t n_images, int F, c
   const size_t o_end = o_out + round16(len) + 16;
   int rc;
   if ((rc = grow_pinned(c, o_end))) return rc;
-  if ((rc = grow_dev(c, &c->d_a, &c->d_a_cap, o_end))) return rc;
+  if ((rc = grow_dev(c, c->d_a, o_end))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // staging buffer reuse
   uint8_t* h = c->h_stage;
   for (int b = 0; b < B; ++b) {
@@ -1628,7 +1596,7 @@ int fleet_teacher_forward(fleet_ctx* c, const float* w, size_t n_w, const float*
   const size_t o_end = o_p + round16(sizeof(float) * (size_t)B * 10);
   int rc;
   if ((rc = grow_pinned(c, o_end))) return rc;
-  if ((rc = grow_dev(c, &c->d_a, &c->d_a_cap, o_end))) return rc;
+  if ((rc = grow_dev(c, c->d_a, o_end))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // staging buffer reuse
   uint8_t* h = c->h_stage;
   std::memcpy(h, w, sizeof(float) * n_w);
@@ -1656,16 +1624,12 @@ int fleet_evaluate_device(fleet_ctx* c, const void* d_w, const void* d_b, const 
     return FLEET_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DEVICE_SCOPE(c);
-  if ((!d_cost || !d_pred) && B > c->d_eval_cap) {
-    if (c->d_eval) c->retired.push_back(c->d_eval);
-    c->d_eval = nullptr;
-    c->d_eval_cap = 0;
-    const hipError_t e = hipMalloc((void**)&c->d_eval, 8 * (size_t)B + 64);
-    if (e != hipSuccess) return fail(c, FLEET_ERR_NOMEM, "hipMalloc(%zu): %s", 8 * (size_t)B, hipGetErrorString(e));
-    c->d_eval_cap = B;
+  if (!d_cost || !d_pred) {
+    const hipError_t e = c->d_eval.grow_exact(8 * (size_t)B, 64, &c->retired);
+    if (e != hipSuccess) return nomem(c, "hipMalloc", 8 * (size_t)B, e);
   }
-  float* cost = d_cost ? (float*)d_cost : (float*)c->d_eval;
-  int32_t* pred = d_pred ? (int32_t*)d_pred : (int32_t*)(c->d_eval + 4 * (size_t)c->d_eval_cap);
+  float* cost = d_cost ? (float*)d_cost : (float*)c->d_eval.get();
+  int32_t* pred = d_pred ? (int32_t*)d_pred : (int32_t*)(c->d_eval + c->d_eval.cap() / 2);  // behind the costs
   HIP_TRY(c, fleet::launch_eval((const float*)d_w, (const float*)d_b, (const float*)d_images, (int64_t)n_images, F,
                                 (const int32_t*)d_labels, (const int32_t*)d_idx, B, pred, (float*)d_prob, cost,
                                 (float*)d_probs10, (float*)d_result, c->d_dev_err, pick(c, stream)));
@@ -1694,7 +1658,7 @@ int fleet_evaluate(fleet_ctx* c, const float* w, size_t n_w, const float* b, siz
   {
     std::lock_guard<std::mutex> lk(c->mu);
     DEVICE_SCOPE(c);
-    if ((rc = grow_dev(c, &c->d_a, &c->d_a_cap, o_end))) return rc;
+    if ((rc = grow_dev(c, c->d_a, o_end))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     d = c->d_a;
     HIP_TRY(c, hipMemcpyAsync(d, w, sizeof(float) * n_w, hipMemcpyHostToDevice, c->stream));
@@ -1757,14 +1721,8 @@ int client_grads_locked(fleet_ctx* c, const void* d_models, size_t model_pitch, 
   }
   // the scales lie behind the rows, with or without DP, so a DP call grows nothing a plain one made
   const size_t need = rows_bytes + fleet::client_grad_scale_bytes(chunk, B);
-  if (need > c->d_client_ws_cap) {
-    if (c->d_client_ws) c->retired.push_back(c->d_client_ws);
-    c->d_client_ws = nullptr;
-    c->d_client_ws_cap = 0;
-    const hipError_t e = hipMalloc((void**)&c->d_client_ws, need + 64);
-    if (e != hipSuccess) return fail(c, FLEET_ERR_NOMEM, "hipMalloc(%zu): %s", need, hipGetErrorString(e));
-    c->d_client_ws_cap = need;
-  }
+  const hipError_t ew = c->d_client_ws.grow_exact(need, 64, &c->retired);
+  if (ew != hipSuccess) return nomem(c, "hipMalloc", need, ew);
   if (dp) {
     if (!c->d_dp_z) {  // once per context
       // the host table is made once per process and kept: every context uploads the same draws
@@ -1773,23 +1731,16 @@ int client_grads_locked(fleet_ctx* c, const void* d_models, size_t model_pitch, 
         fleet::client_dp_noise(t.data(), t.size());
         return t;
       }();
-      const hipError_t e = hipMalloc((void**)&c->d_dp_z, sizeof(double) * n_up);
-      if (e != hipSuccess) return fail(c, FLEET_ERR_NOMEM, "hipMalloc(%zu): %s", sizeof(double) * n_up, hipGetErrorString(e));
+      const hipError_t e = c->d_dp_z.alloc(n_up);
+      if (e != hipSuccess) return nomem(c, "hipMalloc", sizeof(double) * n_up, e);
       const hipError_t e2 = hipMemcpy(c->d_dp_z, z.data(), sizeof(double) * n_up, hipMemcpyHostToDevice);
       if (e2 != hipSuccess) {
-        (void)hipFree(c->d_dp_z);
-        c->d_dp_z = nullptr;
+        c->d_dp_z.reset();
         return fail(c, FLEET_ERR_HIP, "the DP noise table: %s", hipGetErrorString(e2));
       }
     }
-    if (C > c->d_client_dp_cap) {
-      if (c->d_client_dp) c->retired.push_back(c->d_client_dp);
-      c->d_client_dp = nullptr;
-      c->d_client_dp_cap = 0;
-      const hipError_t e = hipMalloc((void**)&c->d_client_dp, 2 * sizeof(float) * (size_t)C);
-      if (e != hipSuccess) return fail(c, FLEET_ERR_NOMEM, "hipMalloc(%zu): %s", 8 * (size_t)C, hipGetErrorString(e));
-      c->d_client_dp_cap = C;
-    }
+    const hipError_t ed = c->d_client_dp.grow_exact(2 * (size_t)C, 0, &c->retired);
+    if (ed != hipSuccess) return nomem(c, "hipMalloc", 8 * (size_t)C, ed);
     // pageable sources: the copies have left clip and sigma when the call returns
     HIP_TRY(c, hipMemcpyAsync(c->d_client_dp, clip, sizeof(float) * (size_t)C, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(c->d_client_dp + C, sigma, sizeof(float) * (size_t)C, hipMemcpyHostToDevice, s));
@@ -1800,8 +1751,8 @@ int client_grads_locked(fleet_ctx* c, const void* d_models, size_t model_pitch, 
                                            (const int32_t*)d_shift, C, B, chunk, temperature, cost,
                                            dp ? c->d_client_dp : nullptr, dp ? c->d_client_dp + C : nullptr,
                                            dp ? dp_of_client.data() : nullptr, dp ? c->d_dp_z : nullptr,
-                                           dp ? (float*)((uint8_t*)c->d_client_ws + rows_bytes) : nullptr,
-                                           c->d_client_ws, (float*)d_grads, (int64_t)grad_pitch, c->d_dev_err, s));
+                                           dp ? (float*)(c->d_client_ws + rows_bytes) : nullptr,
+                                           (float*)c->d_client_ws.get(), (float*)d_grads, (int64_t)grad_pitch, c->d_dev_err, s));
   if (d_uploads)
     HIP_TRY(c, fleet::launch_encode_f32((const float*)d_grads, (int64_t)n_up, grad_pitch, C, (uint8_t*)d_uploads,
                                         upload_pitch, s));
@@ -1878,7 +1829,7 @@ int fleet_client_ex_grads(fleet_ctx* c, const float* w, size_t n_w, const float*
   int rc;
   std::lock_guard<std::mutex> lk(c->mu);
   DEVICE_SCOPE(c);
-  if ((rc = grow_dev(c, &c->d_a, &c->d_a_cap, o_end))) return rc;
+  if ((rc = grow_dev(c, c->d_a, o_end))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   uint8_t* d = c->d_a;
   HIP_TRY(c, hipMemcpyAsync(d, w, sizeof(float) * n_w, hipMemcpyHostToDevice, c->stream));
@@ -1912,19 +1863,19 @@ int fleet_model_params(fleet_ctx* c, const float* weights, size_t n_weights, con
   const size_t len = fleet_b64_len(n);
   if (out_len) *out_len = len;
   if (cap < len || !out) return fail(c, FLEET_ERR_CAPACITY, "output capacity %zu < %zu", cap, len);
-  DevMem dw, db, dt;
+  DevBuf<float> dw, db;  // declared out here: freed after the lock and the device scope end
+  DevBuf<uint8_t> dt;
   {
     std::lock_guard<std::mutex> lk(c->mu);
     DEVICE_SCOPE(c);
-    if (n_weights) HIP_TRY(c, hipMalloc(&dw.p, n_weights * sizeof(float)));
-    if (n_biases) HIP_TRY(c, hipMalloc(&db.p, n_biases * sizeof(float)));
-    HIP_TRY(c, hipMalloc(&dt.p, 16 * groups_of(n) + 16));
-    if (n_weights) HIP_TRY(c, hipMemcpyAsync(dw.p, weights, n_weights * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (n_biases) HIP_TRY(c, hipMemcpyAsync(db.p, biases, n_biases * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, fleet::launch_encode_model_params((const float*)dw.p, (int64_t)n_weights, (const float*)db.p,
-                                                 (int64_t)n_biases, n_biases ? (int64_t)graph_edges : 0,
-                                                 (uint8_t*)dt.p, c->stream));
-    if (len) HIP_TRY(c, hipMemcpyAsync(out, dt.p, len, hipMemcpyDeviceToHost, c->stream));
+    if (n_weights) HIP_TRY(c, dw.alloc(n_weights));
+    if (n_biases) HIP_TRY(c, db.alloc(n_biases));
+    HIP_TRY(c, dt.alloc(16 * groups_of(n) + 16));
+    if (n_weights) HIP_TRY(c, hipMemcpyAsync(dw, weights, n_weights * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (n_biases) HIP_TRY(c, hipMemcpyAsync(db, biases, n_biases * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, fleet::launch_encode_model_params(dw, (int64_t)n_weights, db, (int64_t)n_biases,
+                                                 n_biases ? (int64_t)graph_edges : 0, dt, c->stream));
+    if (len) HIP_TRY(c, hipMemcpyAsync(out, dt, len, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   return FLEET_OK;
@@ -2049,20 +2000,19 @@ int fleet_descent(fleet_ctx* c, float* weights, size_t n_weights, float* fc_bias
     idx += (size_t)b_sizes[k];
   }
   if (!ok) return fail(c, FLEET_ERR_LAYOUT, "descent: gradient header does not match the model layout");
-  DevMem dw, db, dg;
+  DevBuf<float> dw, db, dg;  // freed after the lock and the device scope end
   {
     std::lock_guard<std::mutex> lk(c->mu);
     DEVICE_SCOPE(c);
-    if (nw) HIP_TRY(c, hipMalloc(&dw.p, nw * sizeof(float)));
-    if (nf) HIP_TRY(c, hipMalloc(&db.p, nf * sizeof(float)));
-    HIP_TRY(c, hipMalloc(&dg.p, n_grad * sizeof(float)));
-    if (nw) HIP_TRY(c, hipMemcpyAsync(dw.p, weights, nw * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (nf) HIP_TRY(c, hipMemcpyAsync(db.p, fc_bias, nf * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(dg.p, grad, n_grad * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    for (const auto& sg : segs)
-      HIP_TRY(c, fleet::launch_descent((float*)dw.p, (float*)db.p, (const float*)dg.p, sg, lr, c->stream));
-    if (nw) HIP_TRY(c, hipMemcpyAsync(weights, dw.p, nw * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (nf) HIP_TRY(c, hipMemcpyAsync(fc_bias, db.p, nf * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (nw) HIP_TRY(c, dw.alloc(nw));
+    if (nf) HIP_TRY(c, db.alloc(nf));
+    HIP_TRY(c, dg.alloc(n_grad));
+    if (nw) HIP_TRY(c, hipMemcpyAsync(dw, weights, nw * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (nf) HIP_TRY(c, hipMemcpyAsync(db, fc_bias, nf * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dg, grad, n_grad * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    for (const auto& sg : segs) HIP_TRY(c, fleet::launch_descent(dw, db, dg, sg, lr, c->stream));
+    if (nw) HIP_TRY(c, hipMemcpyAsync(weights, dw, nw * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (nf) HIP_TRY(c, hipMemcpyAsync(fc_bias, db, nf * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   return FLEET_OK;
@@ -2158,28 +2108,27 @@ int fleet::descent_solver_host(fleet_ctx* c, int solver, int adam_resets, float*
   const bool two = solver == FLEET_SOLVER_ADAM;
   float b1_t, b2_t;
   fleet::adam_bias_terms(adam_resets, &b1_t, &b2_t);
-  DevMem dw, d1, d2, db, dg;
+  DevBuf<float> dw, d1, d2, db, dg;  // freed after the lock and the device scope end
   {
     std::lock_guard<std::mutex> lk(c->mu);
     DEVICE_SCOPE(c);
     const size_t wb = nw * sizeof(float);
-    if (nw) HIP_TRY(c, hipMalloc(&dw.p, wb));
-    if (nw) HIP_TRY(c, hipMalloc(&d1.p, wb));
-    if (nw && two) HIP_TRY(c, hipMalloc(&d2.p, wb));
-    if (nf) HIP_TRY(c, hipMalloc(&db.p, nf * sizeof(float)));
-    HIP_TRY(c, hipMalloc(&dg.p, n_grad * sizeof(float)));
-    if (nw) HIP_TRY(c, hipMemcpyAsync(dw.p, weights, wb, hipMemcpyHostToDevice, c->stream));
-    if (nw) HIP_TRY(c, hipMemcpyAsync(d1.p, g1, wb, hipMemcpyHostToDevice, c->stream));
-    if (nw && two) HIP_TRY(c, hipMemcpyAsync(d2.p, g2, wb, hipMemcpyHostToDevice, c->stream));
-    if (nf) HIP_TRY(c, hipMemcpyAsync(db.p, fc_bias, nf * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(dg.p, grad, n_grad * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (nw) HIP_TRY(c, dw.alloc(nw));
+    if (nw) HIP_TRY(c, d1.alloc(nw));
+    if (nw && two) HIP_TRY(c, d2.alloc(nw));
+    if (nf) HIP_TRY(c, db.alloc(nf));
+    HIP_TRY(c, dg.alloc(n_grad));
+    if (nw) HIP_TRY(c, hipMemcpyAsync(dw, weights, wb, hipMemcpyHostToDevice, c->stream));
+    if (nw) HIP_TRY(c, hipMemcpyAsync(d1, g1, wb, hipMemcpyHostToDevice, c->stream));
+    if (nw && two) HIP_TRY(c, hipMemcpyAsync(d2, g2, wb, hipMemcpyHostToDevice, c->stream));
+    if (nf) HIP_TRY(c, hipMemcpyAsync(db, fc_bias, nf * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dg, grad, n_grad * sizeof(float), hipMemcpyHostToDevice, c->stream));
     for (const auto& sg : segs)
-      HIP_TRY(c, fleet::launch_descent_solver(solver, (float*)dw.p, (float*)d1.p, (float*)d2.p, (float*)db.p,
-                                              (const float*)dg.p, sg, lr, b1_t, b2_t, c->stream));
-    if (nw) HIP_TRY(c, hipMemcpyAsync(weights, dw.p, wb, hipMemcpyDeviceToHost, c->stream));
-    if (nw) HIP_TRY(c, hipMemcpyAsync(g1, d1.p, wb, hipMemcpyDeviceToHost, c->stream));
-    if (nw && two) HIP_TRY(c, hipMemcpyAsync(g2, d2.p, wb, hipMemcpyDeviceToHost, c->stream));
-    if (nf) HIP_TRY(c, hipMemcpyAsync(fc_bias, db.p, nf * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, fleet::launch_descent_solver(solver, dw, d1, d2, db, dg, sg, lr, b1_t, b2_t, c->stream));
+    if (nw) HIP_TRY(c, hipMemcpyAsync(weights, dw, wb, hipMemcpyDeviceToHost, c->stream));
+    if (nw) HIP_TRY(c, hipMemcpyAsync(g1, d1, wb, hipMemcpyDeviceToHost, c->stream));
+    if (nw && two) HIP_TRY(c, hipMemcpyAsync(g2, d2, wb, hipMemcpyDeviceToHost, c->stream));
+    if (nf) HIP_TRY(c, hipMemcpyAsync(fc_bias, db, nf * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   return FLEET_OK;
@@ -2204,14 +2153,15 @@ int fleet_model_version(fleet_ctx* c, const float* weights, const int32_t* dims,
   int rc = model_total(c, dims, n_mats, &n);
   if (rc) return rc;
   if (n && (!weights || !weights_out)) return FLEET_ERR_ARG;
-  DevMem dw, dd, di, db;
+  DevBuf<float> dw, dd, db;
+  DevBuf<int32_t> di;
   // the biases' text round trip on the device as well (getParams prints them with `<<` too)
   if (n_biases) {
-    HIP_TRY(c, hipMalloc(&db.p, n_biases * sizeof(float)));
-    HIP_TRY(c, hipMemcpyAsync(db.p, biases, n_biases * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, db.alloc(n_biases));
+    HIP_TRY(c, hipMemcpyAsync(db, biases, n_biases * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_err, 0, sizeof(int), c->stream));
-    HIP_TRY(c, fleet::model_g6_inplace((float*)db.p, (int64_t)n_biases, c->d_err, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(biases_out, db.p, n_biases * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, fleet::model_g6_inplace(db, (int64_t)n_biases, c->d_err, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(biases_out, db, n_biases * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->h_err, c->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (*c->h_err) {
@@ -2220,18 +2170,17 @@ int fleet_model_version(fleet_ctx* c, const float* weights, const int32_t* dims,
     }
   }
   if (!n) return FLEET_OK;
-  HIP_TRY(c, hipMalloc(&dw.p, n * sizeof(float)));
-  HIP_TRY(c, hipMalloc(&dd.p, (n + 1) * sizeof(float)));
-  HIP_TRY(c, hipMalloc(&di.p, n * sizeof(int32_t)));
-  HIP_TRY(c, hipMemcpyAsync(dw.p, weights, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, dw.alloc(n));
+  HIP_TRY(c, dd.alloc(n + 1));
+  HIP_TRY(c, di.alloc(n));
+  HIP_TRY(c, hipMemcpyAsync(dw, weights, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
   int32_t U = 0;
-  HIP_TRY(c, fleet::model_quantize_index((const float*)dw.p, dims, n_mats, nullptr, (float*)dd.p, (int32_t*)di.p,
-                                         &U, c->stream, false));
+  HIP_TRY(c, fleet::model_quantize_index(dw, dims, n_mats, nullptr, dd, di, &U, c->stream, false));
   // the U dictionary values through `<<` / `>>` (decimal6.h), in place, then the gather
   HIP_TRY(c, hipMemsetAsync(c->d_err, 0, sizeof(int), c->stream));
-  HIP_TRY(c, fleet::model_g6_inplace((float*)dd.p, (int64_t)U, c->d_err, c->stream));
-  HIP_TRY(c, fleet::model_dict_gather((const int32_t*)di.p, (int64_t)n, (const float*)dd.p, (float*)dw.p, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(weights_out, dw.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, fleet::model_g6_inplace(dd, (int64_t)U, c->d_err, c->stream));
+  HIP_TRY(c, fleet::model_dict_gather(di, (int64_t)n, dd, dw, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(weights_out, dw, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(c->h_err, c->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (*c->h_err) {
@@ -2254,21 +2203,15 @@ constexpr size_t kAccPiece = 1 << 20;  // host rows: copy and DMA overlap in pie
 // uploads of `len` characters (n values), bytes [col0, col0 + width) of the text. Rows
 // and state on the device hold the window alone; merged outputs are addressed by the
 // whole upload (kernels.h).
-struct Window {
+struct FLEET_MEM_LOCAL Window {
   size_t len = 0, n = 0, gb = 0, ge = 0, ng = 0, col0 = 0, width = 0;
   int n_hdr = 0;
-  int32_t* d_hdr = nullptr;     // {0, count, walk_end, 0, positions}
-  int32_t* d_hfirst = nullptr;  // the batch's first upload's header codes
+  DevBuf<int32_t> d_hdr;     // {0, count, walk_end, 0, positions}
+  DevBuf<int32_t> d_hfirst;  // the batch's first upload's header codes
   size_t row_bytes() const { return 16 * ng + 64; }
   size_t state_bytes() const { return sizeof(float) * 3 * ng + 64; }
   fleet::AccWindow launch() const { return {(int64_t)n, (int64_t)gb, (int64_t)ge, d_hdr, d_hfirst}; }
 };
-
-static void window_release(Window* w) {
-  if (w->d_hdr) (void)hipFree(w->d_hdr);
-  if (w->d_hfirst) (void)hipFree(w->d_hfirst);
-  w->d_hdr = w->d_hfirst = nullptr;
-}
 
 // Checks the arguments that describe the window (the entry points made the bare
 // FLEET_ERR_ARG checks), fills the geometry, allocates d_hfirst and uploads the header
@@ -2290,12 +2233,11 @@ static int window_open(fleet_ctx* c, size_t len, const int32_t* header_pos, int 
   // walk_end = n: the caller's layout covers the whole upload (as fleet_update_device)
   std::vector<int32_t> hw{0, n_headers, (int32_t)n, 0};
   if (n_headers) hw.insert(hw.end(), header_pos, header_pos + n_headers);
-  const size_t hdr_bytes = sizeof(int32_t) * hw.size();
-  if (hipMalloc((void**)&w->d_hdr, hdr_bytes) != hipSuccess ||
-      hipMalloc((void**)&w->d_hfirst, sizeof(int32_t) * ((size_t)n_headers + 16)) != hipSuccess ||
-      hipMemcpy(w->d_hdr, hw.data(), hdr_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+  if (w->d_hdr.alloc(hw.size()) != hipSuccess || w->d_hfirst.alloc((size_t)n_headers + 16) != hipSuccess ||
+      hipMemcpy(w->d_hdr, hw.data(), sizeof(int32_t) * hw.size(), hipMemcpyHostToDevice) != hipSuccess) {
     (void)hipGetLastError();
-    window_release(w);
+    w->d_hdr.reset();
+    w->d_hfirst.reset();
     return FLEET_ERR_NOMEM;
   }
   return FLEET_OK;
@@ -2356,21 +2298,21 @@ static int settle(fleet_ctx* c, InFlight* f, hipStream_t same, bool wait) {
 // incoming upload lands in row[last ^ 1]. A host push flips the two indices only after
 // its error word came back clean. The host finish borrows the two spare buffers for its
 // outputs (the next push overwrites both), so the accumulator holds nothing else.
-struct fleet_acc {
+struct FLEET_MEM_LOCAL fleet_acc {
   fleet_ctx* c = nullptr;
   Window w;
-  float* d_state[2] = {nullptr, nullptr};
-  uint8_t* d_row[2] = {nullptr, nullptr};
-  uint8_t* h_row[2] = {nullptr, nullptr};  // pinned
-  int* d_err = nullptr;
-  volatile int* h_err = nullptr;           // pinned: [0] synchronous reads, [1] written back after device pushes
+  DevBuf<float> d_state[2];
+  DevBuf<uint8_t> d_row[2];
+  PinBuf<uint8_t> h_row[2];
+  DevBuf<int> d_err;
+  PinBuf<volatile int> h_err;              // [0] synchronous reads, [1] written back after device pushes
   int cur = 0, last = 0, count = 0;
   int sticky = 0;                          // a device push's error, until fleet_acc_reset
   InFlight fly;                            // device pushes
   // host bursts: rows 0..K-2 of a launch, window bytes at stage_pitch apart; grown on
   // demand to at most kAccBurst rows and kept until fleet_acc_destroy
-  uint8_t* d_stage = nullptr;
-  uint8_t* h_stage = nullptr;  // pinned
+  DevBuf<uint8_t> d_stage;  // both freed on growth, after the context's stream was waited for
+  PinBuf<uint8_t> h_stage;
   size_t stage_rows = 0, stage_pitch = 0;
 };
 
@@ -2409,7 +2351,7 @@ static int acc_clear_err(fleet_acc* a, hipStream_t s) {
 // leaves nothing committed
 static int acc_verdict(fleet_acc* a, hipStream_t s) {
   fleet_ctx* c = a->c;
-  HIP_TRY(c, hipMemcpyAsync((void*)a->h_err, a->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync((void*)a->h_err.get(), a->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   const int e = a->h_err[0];
   if (e) {
@@ -2417,16 +2359,6 @@ static int acc_verdict(fleet_acc* a, hipStream_t s) {
     return rc ? rc : acc_code(c, e);
   }
   return FLEET_OK;
-}
-
-static void release_accumulator(fleet_acc* a) {
-  for (void* p : {(void*)a->d_state[0], (void*)a->d_state[1], (void*)a->d_row[0], (void*)a->d_row[1], (void*)a->d_err,
-                  (void*)a->d_stage})
-    if (p) (void)hipFree(p);
-  for (void* p : {(void*)a->h_row[0], (void*)a->h_row[1], (void*)a->h_err, (void*)a->h_stage})
-    if (p) (void)hipHostFree(p);
-  window_release(&a->w);
-  delete a;
 }
 
 }  // namespace
@@ -2445,22 +2377,21 @@ int fleet_acc_create(fleet_ctx* c, size_t len, const int32_t* header_pos, int n_
   if (rc) return rc;
   fleet_acc* a = new fleet_acc();
   a->c = c;
-  a->w = w;
-  const size_t row_bytes = a->w.row_bytes(), st_bytes = a->w.state_bytes();
+  a->w = std::move(w);
+  const size_t ng = a->w.ng, row_bytes = a->w.row_bytes(), st_bytes = a->w.state_bytes();
   bool ok = true;
   for (int i = 0; i < 2 && ok; ++i) {
-    ok = hipMalloc((void**)&a->d_state[i], st_bytes) == hipSuccess && hipMalloc((void**)&a->d_row[i], row_bytes) == hipSuccess &&
-         hipHostMalloc((void**)&a->h_row[i], row_bytes, hipHostMallocDefault) == hipSuccess;
+    ok = a->d_state[i].alloc(3 * ng, 64) == hipSuccess && a->d_row[i].alloc(row_bytes) == hipSuccess &&
+         a->h_row[i].alloc(row_bytes) == hipSuccess;
     // bytes past `len` in a row's last group stay zero: the uploads' copies stop at len
     if (ok) std::memset(a->h_row[i], 0, row_bytes);
     ok = ok && hipMemset(a->d_row[i], 0, row_bytes) == hipSuccess && hipMemset(a->d_state[i], 0, st_bytes) == hipSuccess;
   }
-  ok = ok && hipMalloc((void**)&a->d_err, 64) == hipSuccess && hipMemset(a->d_err, 0, 64) == hipSuccess &&
-       hipHostMalloc((void**)&a->h_err, 64, hipHostMallocDefault) == hipSuccess;
+  ok = ok && a->d_err.alloc_zero(16) == hipSuccess && a->h_err.alloc(16) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
-    release_accumulator(a);
-    return fail(c, FLEET_ERR_NOMEM, "fleet_acc_create: allocating the accumulator of %zu groups failed", w.ng);
+    delete a;
+    return fail(c, FLEET_ERR_NOMEM, "fleet_acc_create: allocating the accumulator of %zu groups failed", ng);
   }
   a->h_err[0] = 0;
   a->h_err[1] = 0;
@@ -2475,7 +2406,7 @@ void fleet_acc_destroy(fleet_acc* a) {
   DeviceGuard dg(c->device);
   (void)settle(c, &a->fly, nullptr, true);
   (void)hipStreamSynchronize(c->stream);
-  release_accumulator(a);
+  delete a;
 }
 
 int fleet_acc_count(const fleet_acc* a) { return a ? a->count : FLEET_ERR_ARG; }
@@ -2567,19 +2498,16 @@ static int acc_stage_reserve(fleet_acc* a, size_t rows) {
   fleet_ctx* c = a->c;
   if (rows <= a->stage_rows || a->w.ng == 0) return FLEET_OK;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (a->d_stage) (void)hipFree(a->d_stage);
-  if (a->h_stage) (void)hipHostFree(a->h_stage);
-  a->d_stage = a->h_stage = nullptr;
+  a->d_stage.reset();
+  a->h_stage.reset();
   a->stage_rows = 0;
   a->stage_pitch = a->w.row_bytes();
   const size_t bytes = rows * a->stage_pitch;
-  if (hipMalloc((void**)&a->d_stage, bytes) != hipSuccess ||
-      hipHostMalloc((void**)&a->h_stage, bytes, hipHostMallocDefault) != hipSuccess ||
+  if (a->d_stage.alloc(bytes) != hipSuccess || a->h_stage.alloc(bytes) != hipSuccess ||
       hipMemsetAsync(a->d_stage, 0, bytes, c->stream) != hipSuccess) {  // on the stream the rows' copies follow on
     (void)hipGetLastError();
-    if (a->d_stage) (void)hipFree(a->d_stage);
-    if (a->h_stage) (void)hipHostFree(a->h_stage);
-    a->d_stage = a->h_stage = nullptr;
+    a->d_stage.reset();
+    a->h_stage.reset();
     return fail(c, FLEET_ERR_NOMEM, "burst staging of %zu rows of %zu bytes failed", rows, a->stage_pitch);
   }
   std::memset(a->h_stage, 0, bytes);  // as the rows of fleet_acc_create
@@ -2726,7 +2654,7 @@ int fleet_acc_push_finish_device(fleet_acc* a, const void* d_uploads, size_t pit
     return rc;
   // device pushes of this batch still in flight are on `s` and wrote their error word
   // back before this burst ran: theirs is sticky and comes first, the burst's own is not
-  HIP_TRY(c, hipMemcpyAsync((void*)a->h_err, a->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync((void*)a->h_err.get(), a->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   a->fly.done();
   if ((rc = acc_settle(a, s, false))) return rc;
@@ -2758,31 +2686,22 @@ int fleet_acc_reset(fleet_acc* a) {
 // (k_pool_fold) and leaves every slot as it was. d_rows holds slots + 1 rows of the
 // window's bytes: row `slots` receives the host update's merged bytes, whose fp32 go over
 // the state (the finish launch reads a lane's 12 bytes before it writes them).
-struct fleet_pool {
+struct FLEET_MEM_LOCAL fleet_pool {
   fleet_ctx* c = nullptr;
   Window w;
   size_t pitch = 0;
   int slots = 0;
-  uint8_t* d_rows = nullptr;
-  float* d_state = nullptr;  // the running value between the launches of an update of more than kAccBurst picks
-  int* d_status = nullptr;   // one error word per slot, cleared by every update
-  int* h_status = nullptr;   // pinned: what the last update left in d_status
-  uint8_t* h_row = nullptr;  // pinned: a host put's way in
+  DevBuf<uint8_t> d_rows;
+  DevBuf<float> d_state;   // the running value between the launches of an update of more than kAccBurst picks
+  DevBuf<int> d_status;    // one error word per slot, cleared by every update
+  PinBuf<int> h_status;    // what the last update left in d_status
+  PinBuf<uint8_t> h_row;   // a host put's way in
   std::vector<uint8_t> occupied;
   std::vector<uint8_t> seen;  // update: the picks so far
   InFlight fly;               // device puts
 };
 
 namespace {
-
-static void release_pool(fleet_pool* p) {
-  for (void* d : {(void*)p->d_rows, (void*)p->d_state, (void*)p->d_status})
-    if (d) (void)hipFree(d);
-  for (void* h : {(void*)p->h_status, (void*)p->h_row})
-    if (h) (void)hipHostFree(h);
-  window_release(&p->w);
-  delete p;
-}
 
 static int pool_slot_arg(fleet_pool* p, int slot, const char* what) {
   if (slot < 0 || slot >= p->slots) return fail(p->c, FLEET_ERR_ARG, "%s: slot %d outside [0, %d)", what, slot, p->slots);
@@ -2852,27 +2771,23 @@ int fleet_pool_create(fleet_ctx* c, size_t len, const int32_t* header_pos, int n
   if (rc) return rc;
   fleet_pool* p = new fleet_pool();
   p->c = c;
-  p->w = w;
+  p->w = std::move(w);
   p->pitch = p->w.row_bytes();
   p->slots = slots;
   p->occupied.assign((size_t)slots, 0);
   p->seen.assign((size_t)slots, 0);
-  const size_t rows_bytes = ((size_t)slots + 1) * p->pitch, st_bytes = p->w.state_bytes();
-  const size_t status_bytes = sizeof(int) * (size_t)slots;
+  const size_t ng = p->w.ng;
   // the rows are zeroed once: the puts' copies stop at len
-  const bool ok = hipMalloc((void**)&p->d_rows, rows_bytes) == hipSuccess &&
-                  hipMemset(p->d_rows, 0, rows_bytes) == hipSuccess && hipMalloc((void**)&p->d_state, st_bytes) == hipSuccess &&
-                  hipMemset(p->d_state, 0, st_bytes) == hipSuccess &&
-                  hipMalloc((void**)&p->d_status, status_bytes) == hipSuccess &&
-                  hipMemset(p->d_status, 0, status_bytes) == hipSuccess &&
-                  hipHostMalloc((void**)&p->h_status, status_bytes, hipHostMallocDefault) == hipSuccess &&
-                  hipHostMalloc((void**)&p->h_row, p->pitch, hipHostMallocDefault) == hipSuccess;
+  const bool ok = p->d_rows.alloc_zero(((size_t)slots + 1) * p->pitch) == hipSuccess &&
+                  p->d_state.alloc_zero(3 * ng, 64) == hipSuccess &&
+                  p->d_status.alloc_zero((size_t)slots) == hipSuccess &&
+                  p->h_status.alloc((size_t)slots) == hipSuccess && p->h_row.alloc(p->pitch) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
-    release_pool(p);
-    return fail(c, FLEET_ERR_NOMEM, "fleet_pool_create: allocating %d slots of %zu groups failed", slots, w.ng);
+    delete p;
+    return fail(c, FLEET_ERR_NOMEM, "fleet_pool_create: allocating %d slots of %zu groups failed", slots, ng);
   }
-  std::memset(p->h_status, 0, status_bytes);
+  std::memset(p->h_status, 0, sizeof(int) * (size_t)slots);
   *out = p;
   return FLEET_OK;
 }
@@ -2884,7 +2799,7 @@ void fleet_pool_destroy(fleet_pool* p) {
   DeviceGuard dg(c->device);
   (void)settle(c, &p->fly, nullptr, true);
   (void)hipStreamSynchronize(c->stream);
-  release_pool(p);
+  delete p;
 }
 
 int fleet_pool_slots(const fleet_pool* p) { return p ? p->slots : FLEET_ERR_ARG; }
@@ -2987,29 +2902,21 @@ int fleet_pool_update_device(fleet_pool* p, const int32_t* picks, int K, const d
 // cppNN_backend.cpp:701-720, 779-795. One launch's status words and per-wave partials
 // (kAccBurst slots), and the results of a host vet of up to the pool's slots in HBM and
 // pinned. The gate writes nothing of the pool's but, in fleet_gate_put, the row of a free slot.
-struct fleet_gate {
+struct FLEET_MEM_LOCAL fleet_gate {
   fleet_pool* p = nullptr;
   int cap = 0;                    // result entries: max(the pool's slots, kAccBurst)
-  int32_t* d_expected = nullptr;  // the header codes an upload must carry (nullptr: not checked)
-  int* d_work = nullptr;          // one launch's status words
-  double* d_part = nullptr;       // one launch's per-wave partials
-  int32_t* d_status = nullptr;
-  double* d_sumsq = nullptr;
-  float* d_max = nullptr;
-  int32_t* h_status = nullptr;    // pinned
-  double* h_sumsq = nullptr;
-  float* h_max = nullptr;
+  DevBuf<int32_t> d_expected;  // the header codes an upload must carry (empty: not checked)
+  DevBuf<int> d_work;          // one launch's status words
+  DevBuf<double> d_part;       // one launch's per-wave partials
+  DevBuf<int32_t> d_status;
+  DevBuf<double> d_sumsq;
+  DevBuf<float> d_max;
+  PinBuf<int32_t> h_status;
+  PinBuf<double> h_sumsq;
+  PinBuf<float> h_max;
 };
 
 namespace {
-
-static void release_gate(fleet_gate* g) {
-  for (void* d : {(void*)g->d_expected, (void*)g->d_work, (void*)g->d_part, (void*)g->d_status, (void*)g->d_sumsq, (void*)g->d_max})
-    if (d) (void)hipFree(d);
-  for (void* h : {(void*)g->h_status, (void*)g->h_sumsq, (void*)g->h_max})
-    if (h) (void)hipHostFree(h);
-  delete g;
-}
 
 // the launches of a vet of K checked slots on `s`, kAccBurst slots each, into device arrays of K
 static int gate_launch(fleet_gate* g, const int32_t* slots, int K, int32_t* d_status, double* d_sumsq, float* d_max,
@@ -3031,9 +2938,9 @@ static int gate_vet_host(fleet_gate* g, const int32_t* slots, int K, int32_t* st
   HIP_TRY(c, hipMemcpyAsync(g->h_sumsq, g->d_sumsq, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(g->h_max, g->d_max, sizeof(float) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  std::copy(g->h_status, g->h_status + K, status);
-  std::copy(g->h_sumsq, g->h_sumsq + K, sumsq);
-  std::copy(g->h_max, g->h_max + K, max_abs);
+  std::copy(g->h_status.get(), g->h_status + K, status);
+  std::copy(g->h_sumsq.get(), g->h_sumsq + K, sumsq);
+  std::copy(g->h_max.get(), g->h_max + K, max_abs);
   return FLEET_OK;
 }
 
@@ -3057,22 +2964,16 @@ int fleet_gate_create(fleet_pool* p, const int32_t* header_codes, int n_headers,
   g->p = p;
   g->cap = std::max(p->slots, fleet::kAccBurst);
   const size_t n = (size_t)g->cap;
-  const size_t part_bytes = sizeof(double) * (size_t)fleet::pool_vet_partial_doubles(p->w.launch());
-  const size_t exp_bytes = sizeof(int32_t) * ((size_t)p->w.n_hdr + 16);
-  bool ok = hipMalloc((void**)&g->d_work, sizeof(int) * fleet::kAccBurst) == hipSuccess &&
-            hipMalloc((void**)&g->d_part, part_bytes) == hipSuccess &&
-            hipMalloc((void**)&g->d_status, sizeof(int32_t) * n) == hipSuccess &&
-            hipMalloc((void**)&g->d_sumsq, sizeof(double) * n) == hipSuccess &&
-            hipMalloc((void**)&g->d_max, sizeof(float) * n) == hipSuccess &&
-            hipHostMalloc((void**)&g->h_status, sizeof(int32_t) * n, hipHostMallocDefault) == hipSuccess &&
-            hipHostMalloc((void**)&g->h_sumsq, sizeof(double) * n, hipHostMallocDefault) == hipSuccess &&
-            hipHostMalloc((void**)&g->h_max, sizeof(float) * n, hipHostMallocDefault) == hipSuccess;
+  bool ok = g->d_work.alloc(fleet::kAccBurst) == hipSuccess &&
+            g->d_part.alloc((size_t)fleet::pool_vet_partial_doubles(p->w.launch())) == hipSuccess &&
+            g->d_status.alloc(n) == hipSuccess && g->d_sumsq.alloc(n) == hipSuccess && g->d_max.alloc(n) == hipSuccess &&
+            g->h_status.alloc(n) == hipSuccess && g->h_sumsq.alloc(n) == hipSuccess && g->h_max.alloc(n) == hipSuccess;
   if (ok && header_codes)
-    ok = hipMalloc((void**)&g->d_expected, exp_bytes) == hipSuccess && hipMemset(g->d_expected, 0, exp_bytes) == hipSuccess &&
+    ok = g->d_expected.alloc_zero((size_t)p->w.n_hdr + 16) == hipSuccess &&
          (!n_headers || hipMemcpy(g->d_expected, header_codes, sizeof(int32_t) * (size_t)n_headers, hipMemcpyHostToDevice) == hipSuccess);
   if (!ok) {
     (void)hipGetLastError();
-    release_gate(g);
+    delete g;
     return fail(c, FLEET_ERR_NOMEM, "fleet_gate_create: allocating the gate of a pool of %d slots failed", p->slots);
   }
   *out = g;
@@ -3086,7 +2987,7 @@ void fleet_gate_destroy(fleet_gate* g) {
   DeviceGuard dg(c->device);
   (void)settle(c, &g->p->fly, nullptr, true);  // a device vet in flight reads the gate's buffers
   (void)hipStreamSynchronize(c->stream);
-  release_gate(g);
+  delete g;
 }
 
 int fleet_gate_vet(fleet_gate* g, const int32_t* slots, int K, int32_t* status, double* sumsq, float* max_abs) {
@@ -3152,10 +3053,10 @@ struct fleet_kledger {
   fleet_pool* p = nullptr;
   int workers = 0, max_store = 0, rows = 0;
   size_t vpitch = 0;           // floats per row: 12 G bytes rounded up to 16
-  float* d_slab = nullptr;
-  double* d_part = nullptr;    // one launch's per-wave partials
-  double* d_sums = nullptr;    // 2 sums per pick of an update (picks are distinct slots)
-  double* h_sums = nullptr;    // pinned
+  DevBuf<float> d_slab;
+  DevBuf<double> d_part;       // one launch's per-wave partials
+  DevBuf<double> d_sums;       // 2 sums per pick of an update (picks are distinct slots)
+  PinBuf<double> h_sums;
   std::vector<int32_t> row_of, epoch_of, free_rows;
   // one update's resolution
   std::vector<int32_t> t_row, t_epoch, t_free, t_release, k_prev, k_out;
@@ -3163,13 +3064,6 @@ struct fleet_kledger {
 };
 
 namespace {
-
-static void release_kledger(fleet_kledger* l) {
-  for (void* d : {(void*)l->d_slab, (void*)l->d_part, (void*)l->d_sums})
-    if (d) (void)hipFree(d);
-  if (l->h_sums) (void)hipHostFree(l->h_sums);
-  delete l;
-}
 
 static int kledger_worker_arg(const fleet_kledger* l, int worker, const char* what) {
   if (worker < 0 || worker >= l->workers)
@@ -3268,16 +3162,13 @@ int fleet_kledger_create(fleet_pool* p, int workers, int max_store, fleet_kledge
   l->row_of.assign((size_t)workers, -1);
   l->epoch_of.assign((size_t)workers, 0);
   for (int r = l->rows - 1; r >= 0; --r) l->free_rows.push_back(r);
-  const size_t slab_bytes = sizeof(float) * l->vpitch * (size_t)l->rows;
-  const size_t part_bytes = sizeof(double) * (size_t)fleet::pool_kd_partial_doubles(p->w.launch());
-  const size_t sums_bytes = sizeof(double) * 2 * (size_t)p->slots;
-  const bool ok = hipMalloc((void**)&l->d_slab, slab_bytes) == hipSuccess && hipMemset(l->d_slab, 0, slab_bytes) == hipSuccess &&
-                  hipMalloc((void**)&l->d_part, part_bytes) == hipSuccess &&
-                  hipMalloc((void**)&l->d_sums, sums_bytes) == hipSuccess &&
-                  hipHostMalloc((void**)&l->h_sums, sums_bytes, hipHostMallocDefault) == hipSuccess;
+  const bool ok = l->d_slab.alloc_zero(l->vpitch * (size_t)l->rows) == hipSuccess &&
+                  l->d_part.alloc((size_t)fleet::pool_kd_partial_doubles(p->w.launch())) == hipSuccess &&
+                  l->d_sums.alloc(2 * (size_t)p->slots) == hipSuccess &&
+                  l->h_sums.alloc(2 * (size_t)p->slots) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
-    release_kledger(l);
+    delete l;
     return fail(c, FLEET_ERR_NOMEM, "fleet_kledger_create: allocating %d rows of %zu groups failed", workers + max_store, p->w.ng);
   }
   *out = l;
@@ -3290,7 +3181,7 @@ void fleet_kledger_destroy(fleet_kledger* l) {
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard dg(c->device);
   (void)hipStreamSynchronize(c->stream);
-  release_kledger(l);
+  delete l;
 }
 
 int fleet_kledger_workers(const fleet_kledger* l) { return l ? l->workers : FLEET_ERR_ARG; }
@@ -3385,26 +3276,25 @@ int fleet_kledger_update_device(fleet_kledger* l, const int32_t* picks, int K, c
 // the update's result as lastGrad decodes it, Q(f32(f64(A) / accepted)); the two swap when
 // a resolve ends with an average), currModel / lastModel as two rows of a slab (d_m, rows mc and mc ^ 1), and the
 // optimistic result of the pending update (d_out, d_f32).
-struct fleet_kfilter {
+struct FLEET_MEM_LOCAL fleet_kfilter {
   fleet_kledger* l = nullptr;
   size_t n_w = 0, n_b = 0, n_m = 0, mpitch = 0;
   int edges = 0;
-  float* d_lg[2] = {nullptr, nullptr};
+  DevBuf<float> d_lg[2];
   int lg = 0;
   bool has_last = false;
-  uint8_t* d_out = nullptr;     // the merged bytes of the pending update
-  float* d_f32 = nullptr;       // and their decodeFloat
-  double* d_part = nullptr;     // one launch's per-wave partials (four sums a pick)
-  double* d_sums = nullptr;     // 4 sums per pick of an update
-  double* h_sums = nullptr;     // pinned
-  float* d_m = nullptr;         // two model rows
+  DevBuf<uint8_t> d_out;        // the merged bytes of the pending update
+  DevBuf<float> d_f32;          // and their decodeFloat
+  DevBuf<double> d_part;        // one launch's per-wave partials (four sums a pick)
+  DevBuf<double> d_sums;        // 4 sums per pick of an update
+  PinBuf<double> h_sums;
+  DevBuf<float> d_m;            // two model rows
   int mc = 0;
   bool has_model = false, has_last_model = false;  // row mc was staged since the last resolve / row mc ^ 1 holds lastModel
-  float* d_w = nullptr;         // the host form's staging of a model
-  float* d_b = nullptr;
-  double* d_mpart = nullptr;    // kAccBurst * kMlMaxTiles partials
-  double* d_msq = nullptr;      // {row norm, pair norm}
-  double* h_msq = nullptr;      // pinned
+  DevBuf<float> d_w, d_b;       // the host form's staging of a model
+  DevBuf<double> d_mpart;       // kAccBurst * kMlMaxTiles partials
+  DevBuf<double> d_msq;         // {row norm, pair norm}
+  PinBuf<double> h_msq;
   // the pending update
   bool pending = false;
   std::vector<int32_t> picks;
@@ -3412,15 +3302,6 @@ struct fleet_kfilter {
 };
 
 namespace {
-
-static void release_kfilter(fleet_kfilter* f) {
-  for (void* d : {(void*)f->d_lg[0], (void*)f->d_lg[1], (void*)f->d_out, (void*)f->d_f32, (void*)f->d_part, (void*)f->d_sums, (void*)f->d_m,
-                  (void*)f->d_w, (void*)f->d_b, (void*)f->d_mpart, (void*)f->d_msq})
-    if (d) (void)hipFree(d);
-  for (void* h : {(void*)f->h_sums, (void*)f->h_msq})
-    if (h) (void)hipHostFree(h);
-  delete f;
-}
 
 // kledger_fold through the filter form: the merged bytes and their fp32 go to the filter's
 // own rows, the avg to the lastGrad row that is not read, the four sums of every pick to
@@ -3560,25 +3441,19 @@ int fleet_kfilter_create(fleet_kledger* l, size_t n_weights, size_t n_biases, in
   f->l = l;
   f->n_w = n_weights, f->n_b = n_biases, f->edges = graph_edges, f->n_m = n;
   f->mpitch = (n + 3) / 4 * 4;
-  const size_t lg_bytes = p->w.state_bytes(), out_bytes = p->w.row_bytes();
-  const size_t part_bytes = sizeof(double) * (size_t)fleet::pool_kf_partial_doubles(p->w.launch());
-  const size_t sums_bytes = sizeof(double) * 4 * (size_t)p->slots, m_bytes = sizeof(float) * 2 * f->mpitch;
+  const size_t lg = 3 * p->w.ng;  // the floats of a state row (Window::state_bytes: and 64 bytes)
   const bool ok =
-      hipMalloc((void**)&f->d_lg[0], lg_bytes) == hipSuccess && hipMemset(f->d_lg[0], 0, lg_bytes) == hipSuccess &&
-      hipMalloc((void**)&f->d_lg[1], lg_bytes) == hipSuccess && hipMemset(f->d_lg[1], 0, lg_bytes) == hipSuccess &&
-      hipMalloc((void**)&f->d_out, out_bytes) == hipSuccess && hipMemset(f->d_out, 0, out_bytes) == hipSuccess &&
-      hipMalloc((void**)&f->d_f32, lg_bytes) == hipSuccess && hipMemset(f->d_f32, 0, lg_bytes) == hipSuccess &&
-      hipMalloc((void**)&f->d_part, part_bytes) == hipSuccess && hipMalloc((void**)&f->d_sums, sums_bytes) == hipSuccess &&
-      hipHostMalloc((void**)&f->h_sums, sums_bytes, hipHostMallocDefault) == hipSuccess &&
-      hipMalloc((void**)&f->d_m, m_bytes) == hipSuccess && hipMemset(f->d_m, 0, m_bytes) == hipSuccess &&
-      hipMalloc((void**)&f->d_w, sizeof(float) * std::max<size_t>(1, n_weights)) == hipSuccess &&
-      hipMalloc((void**)&f->d_b, sizeof(float) * std::max<size_t>(1, n_biases)) == hipSuccess &&
-      hipMalloc((void**)&f->d_mpart, sizeof(double) * fleet::kAccBurst * fleet::kMlMaxTiles) == hipSuccess &&
-      hipMalloc((void**)&f->d_msq, sizeof(double) * 2) == hipSuccess &&
-      hipHostMalloc((void**)&f->h_msq, sizeof(double) * 2, hipHostMallocDefault) == hipSuccess;
+      f->d_lg[0].alloc_zero(lg, 64) == hipSuccess && f->d_lg[1].alloc_zero(lg, 64) == hipSuccess &&
+      f->d_out.alloc_zero(p->w.row_bytes()) == hipSuccess && f->d_f32.alloc_zero(lg, 64) == hipSuccess &&
+      f->d_part.alloc((size_t)fleet::pool_kf_partial_doubles(p->w.launch())) == hipSuccess &&
+      f->d_sums.alloc(4 * (size_t)p->slots) == hipSuccess && f->h_sums.alloc(4 * (size_t)p->slots) == hipSuccess &&
+      f->d_m.alloc_zero(2 * f->mpitch) == hipSuccess && f->d_w.alloc(std::max<size_t>(1, n_weights)) == hipSuccess &&
+      f->d_b.alloc(std::max<size_t>(1, n_biases)) == hipSuccess &&
+      f->d_mpart.alloc((size_t)fleet::kAccBurst * fleet::kMlMaxTiles) == hipSuccess &&
+      f->d_msq.alloc(2) == hipSuccess && f->h_msq.alloc(2) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
-    release_kfilter(f);
+    delete f;
     return fail(c, FLEET_ERR_NOMEM, "fleet_kfilter_create: allocating the rows of %zu groups and %zu model values failed", p->w.ng, n);
   }
   *out = f;
@@ -3591,7 +3466,7 @@ void fleet_kfilter_destroy(fleet_kfilter* f) {
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard dg(c->device);
   (void)hipStreamSynchronize(c->stream);
-  release_kfilter(f);
+  delete f;
 }
 
 int fleet_kfilter_has_last(const fleet_kfilter* f) {
@@ -3723,36 +3598,27 @@ int fleet_kfilter_resolve_device(fleet_kfilter* f, const uint8_t* accept, int K,
 // Kardam.java's `models` map (worker -> model, Kardam.java:114-125) over a slab of fp32
 // rows that belong to model versions (mledger_table.h keeps the tables and resolves an
 // update into row pairs; mledger_kernels.hip fills rows and computes the pairs' norms).
-struct fleet_mledger {
+struct FLEET_MEM_LOCAL fleet_mledger {
   fleet_ctx* c = nullptr;
   size_t n_w = 0, n_b = 0, n = 0;
   int edges = 0;
   size_t vpitch = 0;            // floats per row: n rounded up to 4
   std::unique_ptr<fleet::MledgerTable> t;
-  float* d_slab = nullptr;
-  float* d_w = nullptr;         // the host form's staging of one version
-  float* d_b = nullptr;
-  double* d_stage_part = nullptr;  // kMlMaxTiles partials per row: stages on different streams do not meet
-  double* d_row_sq = nullptr;   // per row: sum (double)(a * a)
-  double* d_pair_part = nullptr;   // one launch of pairs
-  double* d_pair_sq = nullptr;  // an update's pairs
-  size_t pair_cap = 0;
-  double* h_sq = nullptr;       // pinned: rows row sums, then the pairs'
-  size_t h_cap = 0;
-  hipEvent_t staged = nullptr;  // orders the context's stream after a stage on a caller's stream
+  DevBuf<float> d_slab;
+  DevBuf<float> d_w, d_b;          // the host form's staging of one version
+  DevBuf<double> d_stage_part;     // kMlMaxTiles partials per row: stages on different streams do not meet
+  DevBuf<double> d_row_sq;         // per row: sum (double)(a * a)
+  DevBuf<double> d_pair_part;      // one launch of pairs
+  DevBuf<double> d_pair_sq;        // an update's pairs; freed on growth
+  PinBuf<double> h_sq;             // rows row sums, then the pairs'; freed on growth
+  hipEvent_t staged = nullptr;     // orders the context's stream after a stage on a caller's stream
   std::vector<double> pair_norm;
+  ~fleet_mledger() {
+    if (staged) (void)hipEventDestroy(staged);
+  }
 };
 
 namespace {
-
-static void release_mledger(fleet_mledger* l) {
-  for (void* d : {(void*)l->d_slab, (void*)l->d_w, (void*)l->d_b, (void*)l->d_stage_part, (void*)l->d_row_sq,
-                  (void*)l->d_pair_part, (void*)l->d_pair_sq})
-    if (d) (void)hipFree(d);
-  if (l->h_sq) (void)hipHostFree(l->h_sq);
-  if (l->staged) (void)hipEventDestroy(l->staged);
-  delete l;
-}
 
 static int mledger_worker_arg(const fleet_mledger* l, int worker, const char* what) {
   if (worker < 0 || worker >= l->t->workers())
@@ -3765,19 +3631,9 @@ static int mledger_worker_arg(const fleet_mledger* l, int worker, const char* wh
 static int mledger_pair_room(fleet_mledger* l, size_t P) {
   fleet_ctx* c = l->c;
   const size_t rows = (size_t)l->t->rows();
-  if (P > l->pair_cap) {
-    if (l->d_pair_sq) (void)hipFree(l->d_pair_sq);
-    l->d_pair_sq = nullptr, l->pair_cap = 0;
-    const size_t cap = std::max<size_t>(2 * P, 4 * (size_t)fleet::kAccBurst);
-    HIP_TRY(c, hipMalloc((void**)&l->d_pair_sq, sizeof(double) * cap));
-    l->pair_cap = cap;
-  }
-  if (rows + l->pair_cap > l->h_cap) {
-    if (l->h_sq) (void)hipHostFree(l->h_sq);
-    l->h_sq = nullptr, l->h_cap = 0;
-    HIP_TRY(c, hipHostMalloc((void**)&l->h_sq, sizeof(double) * (rows + l->pair_cap), hipHostMallocDefault));
-    l->h_cap = rows + l->pair_cap;
-  }
+  if (P > l->d_pair_sq.cap())
+    HIP_TRY(c, l->d_pair_sq.grow_exact(std::max<size_t>(2 * P, 4 * (size_t)fleet::kAccBurst)));
+  HIP_TRY(c, l->h_sq.grow_exact(rows + l->d_pair_sq.cap()));
   return FLEET_OK;
 }
 
@@ -3828,19 +3684,15 @@ int fleet_mledger_create(fleet_ctx* c, size_t n_weights, size_t n_biases, int gr
   l->vpitch = (n + 3) / 4 * 4;
   l->t.reset(new fleet::MledgerTable(workers, max_versions));
   const size_t rows = (size_t)l->t->rows();
-  const size_t slab_bytes = sizeof(float) * l->vpitch * rows;
   const bool ok =
-      hipMalloc((void**)&l->d_slab, slab_bytes) == hipSuccess && hipMemset(l->d_slab, 0, slab_bytes) == hipSuccess &&
-      hipMalloc((void**)&l->d_w, sizeof(float) * std::max<size_t>(1, n_weights)) == hipSuccess &&
-      hipMalloc((void**)&l->d_b, sizeof(float) * std::max<size_t>(1, n_biases)) == hipSuccess &&
-      hipMalloc((void**)&l->d_stage_part, sizeof(double) * rows * fleet::kMlMaxTiles) == hipSuccess &&
-      hipMalloc((void**)&l->d_row_sq, sizeof(double) * rows) == hipSuccess &&
-      hipMemset(l->d_row_sq, 0, sizeof(double) * rows) == hipSuccess &&
-      hipMalloc((void**)&l->d_pair_part, sizeof(double) * fleet::kAccBurst * fleet::kMlMaxTiles) == hipSuccess &&
+      l->d_slab.alloc_zero(l->vpitch * rows) == hipSuccess && l->d_w.alloc(std::max<size_t>(1, n_weights)) == hipSuccess &&
+      l->d_b.alloc(std::max<size_t>(1, n_biases)) == hipSuccess &&
+      l->d_stage_part.alloc(rows * fleet::kMlMaxTiles) == hipSuccess && l->d_row_sq.alloc_zero(rows) == hipSuccess &&
+      l->d_pair_part.alloc((size_t)fleet::kAccBurst * fleet::kMlMaxTiles) == hipSuccess &&
       hipEventCreateWithFlags(&l->staged, hipEventDisableTiming) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
-    release_mledger(l);
+    delete l;
     return fail(c, FLEET_ERR_NOMEM, "fleet_mledger_create: allocating %zu rows of %zu values failed", rows, n);
   }
   *out = l;
@@ -3853,7 +3705,7 @@ void fleet_mledger_destroy(fleet_mledger* l) {
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard dg(c->device);
   (void)hipStreamSynchronize(c->stream);
-  release_mledger(l);
+  delete l;
 }
 
 fleet_ctx* fleet_ctx_of_mledger(const fleet_mledger* l) { return l ? l->c : nullptr; }
@@ -4033,14 +3885,13 @@ int fleet_selftest_digest(fleet_ctx* c, int fn, uint64_t* out) {
   if (fn < 0 || fn > 30) return fail(c, FLEET_ERR_ARG, "no self-test function %d", fn);
   std::lock_guard<std::mutex> lk(c->mu);
   DEVICE_SCOPE(c);
-  unsigned long long* d = nullptr;
-  HIP_TRY(c, hipMalloc((void**)&d, sizeof(unsigned long long)));
+  DevBuf<unsigned long long> d;  // freed on every path
+  HIP_TRY(c, d.alloc(1));
   HIP_TRY(c, hipMemsetAsync(d, 0, sizeof(unsigned long long), c->stream));
   HIP_TRY(c, fn >= 25 ? fleet::launch_digest_solver(fn, d, c->stream) : fleet::launch_digest(fn, d, c->stream));
   unsigned long long h = 0;
   HIP_TRY(c, hipMemcpyAsync(&h, d, sizeof h, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(d);
   *out = h;
   return FLEET_OK;
 }

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "model_codec.h"
+#include "dev_mem.h"
 #include "decimal6.h"
 
 namespace fleet {
@@ -414,22 +415,21 @@ __global__ void __launch_bounds__(256) k_read_tokens(const uint8_t* __restrict__
 
 inline unsigned nb(int64_t n) { return (unsigned)((n + 255) / 256); }
 
+// n elements, at least one
 template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  bool own = true;
-  hipError_t alloc(size_t n) { return hipMalloc((void**)&p, sizeof(T) * (n ? n : 1)); }
-  // a caller-owned workspace's buffer when there is one, else an allocation of n
-  hipError_t take(T* from_ws, size_t n) {
-    if (!from_ws) return alloc(n);
-    p = from_ws;
-    own = false;
-    return hipSuccess;
-  }
-  ~DevBuf() {
-    if (p && own) (void)hipFree(p);
-  }
-};
+hipError_t alloc1(DevBuf<T>& b, size_t n) { return b.alloc(n ? n : 1); }
+
+// *p: a caller-owned workspace's buffer when there is one, else an allocation of n (at least
+// one) that `owned` keeps until the function returns
+template <typename T>
+hipError_t ws_or_alloc(T* from_ws, size_t n, std::vector<DevBuf<void>>& owned, T** p) {
+  *p = from_ws;
+  if (from_ws) return hipSuccess;
+  owned.emplace_back();
+  const hipError_t e = owned.back().alloc(sizeof(T) * (n ? n : 1));
+  *p = (T*)owned.back().get();
+  return e;
+}
 
 #define MC_TRY(x)                      \
   do {                                 \
@@ -446,67 +446,68 @@ hipError_t model_quantize_index(const float* d_w, const int32_t* h_dims, int n_m
   const int64_t n = off[n_mats];
   *h_U = 0;
   if (n == 0) return hipSuccess;
-  DevBuf<int64_t> d_off;
-  DevBuf<int32_t> d_dims;
-  DevBuf<MatParams> d_prm;
-  MC_TRY(d_off.take(ws ? ws->off : nullptr, n_mats + 1));
-  MC_TRY(d_dims.take(ws ? ws->dims : nullptr, 3 * n_mats));
-  MC_TRY(d_prm.take(ws ? (MatParams*)ws->prm : nullptr, n_mats));
-  MC_TRY(hipMemcpyAsync(d_off.p, off.data(), sizeof(int64_t) * (n_mats + 1), hipMemcpyHostToDevice, s));
-  MC_TRY(hipMemcpyAsync(d_dims.p, h_dims, sizeof(int32_t) * 3 * n_mats, hipMemcpyHostToDevice, s));
+  std::vector<DevBuf<void>> owned;  // what the workspace does not bring
+  int64_t* d_off;
+  int32_t* d_dims;
+  MatParams* d_prm;
+  MC_TRY(ws_or_alloc(ws ? ws->off : nullptr, n_mats + 1, owned, &d_off));
+  MC_TRY(ws_or_alloc(ws ? ws->dims : nullptr, 3 * n_mats, owned, &d_dims));
+  MC_TRY(ws_or_alloc(ws ? (MatParams*)ws->prm : nullptr, n_mats, owned, &d_prm));
+  MC_TRY(hipMemcpyAsync(d_off, off.data(), sizeof(int64_t) * (n_mats + 1), hipMemcpyHostToDevice, s));
+  MC_TRY(hipMemcpyAsync(d_dims, h_dims, sizeof(int32_t) * 3 * n_mats, hipMemcpyHostToDevice, s));
   if (quantize) {
-    hipLaunchKernelGGL(k_mm_minmax, dim3(n_mats), dim3(256), 0, s, d_w, d_off.p, d_dims.p, d_prm.p);
-    hipLaunchKernelGGL(k_mm_quantize, dim3(nb(n)), dim3(256), 0, s, d_w, n, d_off.p, n_mats, d_prm.p, d_wq);
+    hipLaunchKernelGGL(k_mm_minmax, dim3(n_mats), dim3(256), 0, s, d_w, d_off, d_dims, d_prm);
+    hipLaunchKernelGGL(k_mm_quantize, dim3(nb(n)), dim3(256), 0, s, d_w, n, d_off, n_mats, d_prm, d_wq);
     MC_TRY(hipGetLastError());
   } else {  // the dictionary of the weights as they are (descentNative's model copy)
     d_wq = const_cast<float*>(d_w);
   }
 
   // dictionary over the quantised weights
-  DevBuf<uint32_t> key, key2;
-  DevBuf<int32_t> idx, sidx, start, cid, cbeg, creator, scratch, rank, flag32;
-  DevBuf<uint8_t> is_creator;
-  MC_TRY(key.take(ws ? ws->key : nullptr, n));
-  MC_TRY(key2.take(ws ? ws->key2 : nullptr, n));
-  MC_TRY(idx.take(ws ? ws->idx : nullptr, n));
-  MC_TRY(sidx.take(ws ? ws->sidx : nullptr, n));
-  MC_TRY(start.take(ws ? ws->start : nullptr, n));
-  MC_TRY(cid.take(ws ? ws->cid : nullptr, n));
-  MC_TRY(cbeg.take(ws ? ws->cbeg : nullptr, n + 1));
-  MC_TRY(creator.take(ws ? ws->creator : nullptr, n));
-  MC_TRY(scratch.take(ws ? ws->scratch : nullptr, n));
-  MC_TRY(rank.take(ws ? ws->rank : nullptr, n));
-  MC_TRY(flag32.take(ws ? ws->flag32 : nullptr, n));
-  MC_TRY(is_creator.take(ws ? ws->is_creator : nullptr, n));
-  hipLaunchKernelGGL(k_dict_keys, dim3(nb(n)), dim3(256), 0, s, d_wq, n, key.p, idx.p);
+  uint32_t *key, *key2;
+  int32_t *idx, *sidx, *start, *cid, *cbeg, *creator, *scratch, *rank, *flag32;
+  uint8_t* is_creator;
+  MC_TRY(ws_or_alloc(ws ? ws->key : nullptr, n, owned, &key));
+  MC_TRY(ws_or_alloc(ws ? ws->key2 : nullptr, n, owned, &key2));
+  MC_TRY(ws_or_alloc(ws ? ws->idx : nullptr, n, owned, &idx));
+  MC_TRY(ws_or_alloc(ws ? ws->sidx : nullptr, n, owned, &sidx));
+  MC_TRY(ws_or_alloc(ws ? ws->start : nullptr, n, owned, &start));
+  MC_TRY(ws_or_alloc(ws ? ws->cid : nullptr, n, owned, &cid));
+  MC_TRY(ws_or_alloc(ws ? ws->cbeg : nullptr, n + 1, owned, &cbeg));
+  MC_TRY(ws_or_alloc(ws ? ws->creator : nullptr, n, owned, &creator));
+  MC_TRY(ws_or_alloc(ws ? ws->scratch : nullptr, n, owned, &scratch));
+  MC_TRY(ws_or_alloc(ws ? ws->rank : nullptr, n, owned, &rank));
+  MC_TRY(ws_or_alloc(ws ? ws->flag32 : nullptr, n, owned, &flag32));
+  MC_TRY(ws_or_alloc(ws ? ws->is_creator : nullptr, n, owned, &is_creator));
+  hipLaunchKernelGGL(k_dict_keys, dim3(nb(n)), dim3(256), 0, s, d_wq, n, key, idx);
   size_t tmp_bytes = 0, t2 = 0, t3 = 0;
-  MC_TRY(sort_pairs(nullptr, tmp_bytes, key.p, key2.p, idx.p, sidx.p, n, s));
-  MC_TRY(inclusive_sum(nullptr, t2, start.p, cid.p, n, s));
-  MC_TRY(exclusive_sum(nullptr, t3, flag32.p, rank.p, n, s));
+  MC_TRY(sort_pairs(nullptr, tmp_bytes, key, key2, idx, sidx, n, s));
+  MC_TRY(inclusive_sum(nullptr, t2, start, cid, n, s));
+  MC_TRY(exclusive_sum(nullptr, t3, flag32, rank, n, s));
   tmp_bytes = std::max(tmp_bytes, std::max(t2, t3));
-  DevBuf<uint8_t> tmp;
+  uint8_t* tmp;
   if (ws && ws->tmp_bytes < tmp_bytes) return hipErrorInvalidValue;  // (sized by model_dict_ws_carve for this n)
-  MC_TRY(tmp.take(ws ? (uint8_t*)ws->tmp : nullptr, tmp_bytes));
-  MC_TRY(sort_pairs(tmp.p, tmp_bytes, key.p, key2.p, idx.p, sidx.p, n, s));
-  hipLaunchKernelGGL(k_dict_starts, dim3(nb(n)), dim3(256), 0, s, d_wq, sidx.p, n, start.p);
+  MC_TRY(ws_or_alloc(ws ? (uint8_t*)ws->tmp : nullptr, tmp_bytes, owned, &tmp));
+  MC_TRY(sort_pairs(tmp, tmp_bytes, key, key2, idx, sidx, n, s));
+  hipLaunchKernelGGL(k_dict_starts, dim3(nb(n)), dim3(256), 0, s, d_wq, sidx, n, start);
   size_t tb = tmp_bytes;
-  MC_TRY(inclusive_sum(tmp.p, tb, start.p, cid.p, n, s));
+  MC_TRY(inclusive_sum(tmp, tb, start, cid, n, s));
   int32_t n_clusters = 0;
-  MC_TRY(hipMemcpyAsync(&n_clusters, cid.p + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  MC_TRY(hipMemcpyAsync(&n_clusters, cid + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
   MC_TRY(hipStreamSynchronize(s));
-  hipLaunchKernelGGL(k_dict_cbeg, dim3(nb(n)), dim3(256), 0, s, start.p, cid.p, n, cbeg.p);
+  hipLaunchKernelGGL(k_dict_cbeg, dim3(nb(n)), dim3(256), 0, s, start, cid, n, cbeg);
   const int32_t nn = (int32_t)n;
-  MC_TRY(hipMemcpyAsync(cbeg.p + n_clusters, &nn, sizeof(int32_t), hipMemcpyHostToDevice, s));
-  MC_TRY(hipMemsetAsync(is_creator.p, 0, n, s));
-  hipLaunchKernelGGL(k_dict_resolve, dim3(nb(n_clusters)), dim3(256), 0, s, d_wq, sidx.p, cbeg.p, n_clusters,
-                     creator.p, is_creator.p, scratch.p);
-  hipLaunchKernelGGL(k_dict_u8_to_i32, dim3(nb(n)), dim3(256), 0, s, is_creator.p, n, flag32.p);
+  MC_TRY(hipMemcpyAsync(cbeg + n_clusters, &nn, sizeof(int32_t), hipMemcpyHostToDevice, s));
+  MC_TRY(hipMemsetAsync(is_creator, 0, n, s));
+  hipLaunchKernelGGL(k_dict_resolve, dim3(nb(n_clusters)), dim3(256), 0, s, d_wq, sidx, cbeg, n_clusters,
+                     creator, is_creator, scratch);
+  hipLaunchKernelGGL(k_dict_u8_to_i32, dim3(nb(n)), dim3(256), 0, s, is_creator, n, flag32);
   tb = tmp_bytes;
-  MC_TRY(exclusive_sum(tmp.p, tb, flag32.p, rank.p, n, s));
+  MC_TRY(exclusive_sum(tmp, tb, flag32, rank, n, s));
   int32_t last_rank = 0, last_flag = 0;
-  MC_TRY(hipMemcpyAsync(&last_rank, rank.p + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  MC_TRY(hipMemcpyAsync(&last_flag, flag32.p + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  hipLaunchKernelGGL(k_dict_emit, dim3(nb(n)), dim3(256), 0, s, d_wq, sidx.p, creator.p, is_creator.p, rank.p, n,
+  MC_TRY(hipMemcpyAsync(&last_rank, rank + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  MC_TRY(hipMemcpyAsync(&last_flag, flag32 + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  hipLaunchKernelGGL(k_dict_emit, dim3(nb(n)), dim3(256), 0, s, d_wq, sidx, creator, is_creator, rank, n,
                      d_dict, d_index);
   MC_TRY(hipGetLastError());
   MC_TRY(hipStreamSynchronize(s));
@@ -559,27 +560,27 @@ hipError_t model_index_text(const int32_t* d_index, const int32_t* h_dims, int n
   }
   DevBuf<int64_t> d_off, len, pos;
   DevBuf<char> txt;
-  MC_TRY(d_off.alloc(n_mats + 1));
-  MC_TRY(len.alloc(n));
-  MC_TRY(pos.alloc(n));
-  MC_TRY(hipMemcpyAsync(d_off.p, off.data(), sizeof(int64_t) * (n_mats + 1), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_text_len, dim3(nb(n)), dim3(256), 0, s, d_index, n, d_off.p, n_mats, len.p);
+  MC_TRY(alloc1(d_off, n_mats + 1));
+  MC_TRY(alloc1(len, n));
+  MC_TRY(alloc1(pos, n));
+  MC_TRY(hipMemcpyAsync(d_off.get(), off.data(), sizeof(int64_t) * (n_mats + 1), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_text_len, dim3(nb(n)), dim3(256), 0, s, d_index, n, d_off.get(), n_mats, len.get());
   size_t tb = 0;
-  MC_TRY(exclusive_sum(nullptr, tb, len.p, pos.p, n, s));
+  MC_TRY(exclusive_sum(nullptr, tb, len.get(), pos.get(), n, s));
   DevBuf<uint8_t> tmp;
-  MC_TRY(tmp.alloc(tb));
-  MC_TRY(exclusive_sum(tmp.p, tb, len.p, pos.p, n, s));
+  MC_TRY(alloc1(tmp, tb));
+  MC_TRY(exclusive_sum(tmp.get(), tb, len.get(), pos.get(), n, s));
   int64_t last_pos = 0, last_len = 0;
-  MC_TRY(hipMemcpyAsync(&last_pos, pos.p + (n - 1), sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  MC_TRY(hipMemcpyAsync(&last_len, len.p + (n - 1), sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  MC_TRY(hipMemcpyAsync(&last_pos, pos.get() + (n - 1), sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  MC_TRY(hipMemcpyAsync(&last_len, len.get() + (n - 1), sizeof(int64_t), hipMemcpyDeviceToHost, s));
   MC_TRY(hipStreamSynchronize(s));
   const int64_t total = last_pos + last_len;
-  MC_TRY(txt.alloc(total));
-  hipLaunchKernelGGL(k_text_write, dim3(nb(n)), dim3(256), 0, s, d_index, n, d_off.p, n_mats, pos.p, txt.p);
+  MC_TRY(alloc1(txt, total));
+  hipLaunchKernelGGL(k_text_write, dim3(nb(n)), dim3(256), 0, s, d_index, n, d_off.get(), n_mats, pos.get(), txt.get());
   MC_TRY(hipGetLastError());
   // empty matrices print a lone '\n' in their place: stitch them in on the host
   std::vector<char> body((size_t)total);
-  MC_TRY(hipMemcpyAsync(body.data(), txt.p, (size_t)total, hipMemcpyDeviceToHost, s));
+  MC_TRY(hipMemcpyAsync(body.data(), txt.get(), (size_t)total, hipMemcpyDeviceToHost, s));
   MC_TRY(hipStreamSynchronize(s));
   bool any_empty = false;
   for (int j = 0; j < n_mats; ++j) any_empty |= off[j + 1] == off[j];
@@ -623,22 +624,22 @@ hipError_t model_values_text(const float* d_v, int64_t n, const int64_t* h_off, 
   }
   DevBuf<int64_t> d_off;
   DevBuf<uint8_t> wsmem;
-  MC_TRY(d_off.alloc((size_t)n_blocks + 1));
+  MC_TRY(alloc1(d_off, (size_t)n_blocks + 1));
   TextWs ws;
   const size_t ws_bytes = model_text_ws_carve(nullptr, n, &ws);
   if (!ws_bytes) return hipErrorUnknown;
-  MC_TRY(wsmem.alloc(ws_bytes));
-  model_text_ws_carve(wsmem.p, n, &ws);
+  MC_TRY(alloc1(wsmem, ws_bytes));
+  model_text_ws_carve(wsmem.get(), n, &ws);
   if (n_blocks > 0)
-    MC_TRY(hipMemcpyAsync(d_off.p, h_off, sizeof(int64_t) * ((size_t)n_blocks + 1), hipMemcpyHostToDevice, s));
+    MC_TRY(hipMemcpyAsync(d_off.get(), h_off, sizeof(int64_t) * ((size_t)n_blocks + 1), hipMemcpyHostToDevice, s));
   // 12 bytes and a separator per value, an int key and its newline (pairs) or the blocks' newlines
   const int64_t cap = n_blocks > 0 ? 13 * n + n_blocks : 24 * n;
   DevBuf<char> txt;
-  MC_TRY(txt.alloc((size_t)cap));
+  MC_TRY(alloc1(txt, (size_t)cap));
   int64_t total = 0;
-  MC_TRY(model_values_text_ws(d_v, n, d_off.p, n_blocks, ws, txt.p, cap, &total, s));
+  MC_TRY(model_values_text_ws(d_v, n, d_off.get(), n_blocks, ws, txt.get(), cap, &total, s));
   out->resize((size_t)total);
-  MC_TRY(hipMemcpyAsync(out->data(), txt.p, (size_t)total, hipMemcpyDeviceToHost, s));
+  MC_TRY(hipMemcpyAsync(out->data(), txt.get(), (size_t)total, hipMemcpyDeviceToHost, s));
   return hipStreamSynchronize(s);
 }
 
@@ -725,23 +726,23 @@ hipError_t model_read_index(const uint8_t* d_text, int64_t len, int64_t n_w, con
   }
   DevBuf<int32_t> st, tok;
   DevBuf<int> bad;
-  MC_TRY(st.alloc(len));
-  MC_TRY(tok.alloc(len));
-  MC_TRY(bad.alloc(1));
-  MC_TRY(hipMemsetAsync(bad.p, 0, sizeof(int), s));
-  hipLaunchKernelGGL(k_read_starts, dim3(nb(len)), dim3(256), 0, s, d_text, len, st.p);
+  MC_TRY(alloc1(st, len));
+  MC_TRY(alloc1(tok, len));
+  MC_TRY(alloc1(bad, 1));
+  MC_TRY(hipMemsetAsync(bad.get(), 0, sizeof(int), s));
+  hipLaunchKernelGGL(k_read_starts, dim3(nb(len)), dim3(256), 0, s, d_text, len, st.get());
   size_t tb = 0;
-  MC_TRY(inclusive_sum(nullptr, tb, st.p, tok.p, (size_t)len, s));
+  MC_TRY(inclusive_sum(nullptr, tb, st.get(), tok.get(), (size_t)len, s));
   DevBuf<uint8_t> tmp;
-  MC_TRY(tmp.alloc(tb));
-  MC_TRY(inclusive_sum(tmp.p, tb, st.p, tok.p, (size_t)len, s));
-  hipLaunchKernelGGL(k_read_tokens, dim3(nb(len)), dim3(256), 0, s, d_text, len, st.p, tok.p, n_w, d_keys, d_vals,
-                     n_keys, d_w, bad.p);
+  MC_TRY(alloc1(tmp, tb));
+  MC_TRY(inclusive_sum(tmp.get(), tb, st.get(), tok.get(), (size_t)len, s));
+  hipLaunchKernelGGL(k_read_tokens, dim3(nb(len)), dim3(256), 0, s, d_text, len, st.get(), tok.get(), n_w, d_keys, d_vals,
+                     n_keys, d_w, bad.get());
   MC_TRY(hipGetLastError());
   int32_t n_tok = 0;
   int hbad = 0;
-  MC_TRY(hipMemcpyAsync(&n_tok, tok.p + (len - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  MC_TRY(hipMemcpyAsync(&hbad, bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  MC_TRY(hipMemcpyAsync(&n_tok, tok.get() + (len - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  MC_TRY(hipMemcpyAsync(&hbad, bad.get(), sizeof(int), hipMemcpyDeviceToHost, s));
   MC_TRY(hipStreamSynchronize(s));
   *h_status = hbad ? hbad : (n_tok != n_w ? 2 : 0);
   return hipSuccess;

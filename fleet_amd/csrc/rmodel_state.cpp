@@ -30,12 +30,13 @@
 #include <vector>
 
 #include "../../include/fleet_codec.h"
+#include "dev_mem.h"
 #include "model_codec.h"
 #include "model_state.h"
 #include "rmodel_kernels.h"
 #include "solver_math.h"
 
-struct fleet_rmodel {
+struct FLEET_MEM_LOCAL fleet_rmodel {
   fleet_ctx* ctx = nullptr;
   fleet_model* host = nullptr;  // layout, header, dims (its cnn is released after the upload)
   int device = 0, mode = 1, max_versions = 0;
@@ -43,23 +44,20 @@ struct fleet_rmodel {
   hipStream_t stream = nullptr;
   size_t nw = 0, nb = 0, nfc = 0, stride = 0;
   int n_mats = 0, n_bias_blocks = 0;
-  // HBM
-  float* state = nullptr;
-  uint8_t* tab = nullptr;
-  uint8_t* work = nullptr;
-  char* text = nullptr;
-  uint8_t* a20 = nullptr;
-  uint8_t* gtext = nullptr;  // a host gradient text, staged (grown on first use)
-  float* grad = nullptr;
-  float* sstate = nullptr;  // the solver's state rows g1 | g2, nw floats each (fleet_rmodel_set_solver)
+  // HBM; what grows is freed and allocated at the exact size (nothing here is retired: the
+  // two that a caller's stream may still use wait for the device first)
+  fleet::DevBuf<float> state;
+  fleet::DevBuf<uint8_t> tab, work;
+  fleet::DevBuf<char> text;
+  fleet::DevBuf<uint8_t> a20;
+  fleet::DevBuf<uint8_t> gtext;  // a host gradient text, staged (grown on first use)
+  fleet::DevBuf<float> grad;
+  fleet::DevBuf<float> sstate;  // the solver's state rows g1 | g2, nw floats each (fleet_rmodel_set_solver)
   int solver = 0;
   bool stepped = false;
-  size_t gtext_cap = 0, grad_cap = 0;
-  int32_t* d_client_rows = nullptr;  // client gradients: the row of every client's version
-  int client_rows_cap = 0;
-  uint8_t* eval_ws = nullptr;  // evaluation: [B costs | B predictions | B p | result | staged images, labels, indices]
-  size_t eval_cap = 0;
-  int* h_pin = nullptr;  // pinned: [0] the error word's copy, [4..] the counts line
+  fleet::DevBuf<int32_t> d_client_rows;  // client gradients: the row of every client's version
+  fleet::DevBuf<uint8_t> eval_ws;  // evaluation: [B costs | B predictions | B p | result | staged images, labels, indices]
+  fleet::PinBuf<int> h_pin;  // [0] the error word's copy, [4..] the counts line
   // carved from tab / work
   fleet::RmLayout lay{};
   int* d_err = nullptr;
@@ -69,7 +67,7 @@ struct fleet_rmodel {
   fleet::TextWs tws{};
   float *d_wq = nullptr, *d_dict = nullptr;
   int32_t* d_index = nullptr;
-  size_t text_cap = 0, a20_len = 0;
+  size_t a20_len = 0;
   // ring
   std::deque<int> models;  // row numbers, oldest first
   std::vector<int> free_rows;
@@ -119,9 +117,10 @@ struct DeviceScope {
   DeviceScope device_scope_((m)->device); \
   if (!device_scope_.ok) return rfail((m), FLEET_ERR_HIP, "hipSetDevice(%d) failed", (m)->device)
 
+// exactly n elements (an empty request still gets a byte); what b held is freed first
 template <typename T>
-int dev_alloc(fleet_rmodel* m, T** p, size_t bytes) {
-  RM_HIP(m, hipMalloc((void**)p, bytes ? bytes : 1));
+int dev_alloc(fleet_rmodel* m, fleet::DevBuf<T>& b, size_t n) {
+  RM_HIP(m, b.alloc(n, n ? 0 : 1));
   m->device_allocs++;
   return FLEET_OK;
 }
@@ -193,18 +192,15 @@ size_t carve_work(fleet_rmodel* m, uint8_t* base) {
 
 void release(fleet_rmodel* m) {
   if (!m) return;
+  fleet_model* host = m->host;
   {
     DeviceScope sc(m->device);
-    if (m->stream) (void)hipStreamSynchronize(m->stream);
-    for (void* p : {(void*)m->state, (void*)m->tab, (void*)m->work, (void*)m->text, (void*)m->a20, (void*)m->gtext,
-                    (void*)m->grad, (void*)m->sstate, (void*)m->eval_ws,
-                    (void*)m->d_client_rows})
-      if (p) (void)hipFree(p);
-    if (m->h_pin) (void)hipHostFree(m->h_pin);
-    if (m->stream) (void)hipStreamDestroy(m->stream);
+    hipStream_t s = m->stream;
+    if (s) (void)hipStreamSynchronize(s);
+    delete m;  // the model's memory, inside the device scope
+    if (s) (void)hipStreamDestroy(s);
   }
-  if (m->host) fleet_model_destroy(m->host);
-  delete m;
+  if (host) fleet_model_destroy(host);
 }
 
 int set_up(fleet_rmodel* m) {
@@ -221,27 +217,27 @@ int set_up(fleet_rmodel* m) {
   if (m->stride == 0) m->stride = 64;
   const size_t rows = (size_t)m->max_versions + 2;
   RM_HIP(m, hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-  RM_HIP(m, hipHostMalloc((void**)&m->h_pin, 256, hipHostMallocDefault));
+  RM_HIP(m, m->h_pin.alloc(64));
   m->device_allocs++;
   int rc;
   m->resident_bytes = sizeof(float) * m->stride * rows;
-  if ((rc = dev_alloc(m, &m->state, m->resident_bytes))) return rc;
+  if ((rc = dev_alloc(m, m->state, m->stride * rows))) return rc;
   RM_HIP(m, hipMemsetAsync(m->state, 0, m->resident_bytes, m->stream));
   const size_t tab_bytes = carve_tables(m, nullptr);
-  if ((rc = dev_alloc(m, &m->tab, tab_bytes))) return rc;
+  if ((rc = dev_alloc(m, m->tab, tab_bytes))) return rc;
   carve_tables(m, m->tab);
   m->work_bytes = carve_work(m, nullptr);
   if (!m->work_bytes && std::max(m->nw, m->nb)) return rfail(m, FLEET_ERR_HIP, "rocPRIM would not size its storage");
-  if ((rc = dev_alloc(m, &m->work, m->work_bytes))) return rc;
+  if ((rc = dev_alloc(m, m->work, m->work_bytes))) return rc;
   carve_work(m, m->work);
   // the longest getParams text: 12 bytes and a separator per value, a line break per
   // block; mode 1 adds the counts, an int key per dictionary entry and an index per weight
-  m->text_cap = h->header.size() + 13 * m->nb + (size_t)m->n_bias_blocks + 64 +
-                (m->mode ? 24 * m->nw + 12 * m->nw + (size_t)m->n_mats : 13 * m->nw + (size_t)m->n_mats);
-  if ((rc = dev_alloc(m, &m->text, m->text_cap))) return rc;
+  const size_t text_cap = h->header.size() + 13 * m->nb + (size_t)m->n_bias_blocks + 64 +
+                          (m->mode ? 24 * m->nw + 12 * m->nw + (size_t)m->n_mats : 13 * m->nw + (size_t)m->n_mats);
+  if ((rc = dev_alloc(m, m->text, text_cap))) return rc;
   m->a20_len = fleet_b64_len(m->nb * h->edge_w_size.size() + m->nw);
-  if ((rc = dev_alloc(m, &m->a20, (m->a20_len + 15) / 16 * 16 + 64))) return rc;
-  m->work_bytes += tab_bytes + m->text_cap + (m->a20_len + 15) / 16 * 16 + 64;
+  if ((rc = dev_alloc(m, m->a20, (m->a20_len + 15) / 16 * 16 + 64))) return rc;
+  m->work_bytes += tab_bytes + text_cap + (m->a20_len + 15) / 16 * 16 + 64;
 
   // tables: what the model knows
   const size_t ne = h->edge_w_size.size(), nl = h->layers.size();
@@ -374,17 +370,10 @@ int version_row(fleet_rmodel* m, int version, int* row) {
 
 // the evaluation workspace: allocated on first use, grown only for a larger need
 int eval_workspace(fleet_rmodel* m, size_t bytes) {
-  if (bytes <= m->eval_cap) return FLEET_OK;
-  if (m->eval_ws) {  // (an evaluation on a caller's stream may still write the old one)
-    RM_HIP(m, hipDeviceSynchronize());
-    (void)hipFree(m->eval_ws);
-  }
-  m->eval_ws = nullptr;
-  m->eval_cap = 0;
-  const int rc = dev_alloc(m, &m->eval_ws, bytes);
-  if (rc) return rc;
-  m->eval_cap = bytes;
-  return FLEET_OK;
+  if (bytes <= m->eval_ws.cap()) return FLEET_OK;
+  // (an evaluation on a caller's stream may still write the old one)
+  if (m->eval_ws) RM_HIP(m, hipDeviceSynchronize());
+  return dev_alloc(m, m->eval_ws, bytes);
 }
 
 inline size_t r256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -463,20 +452,9 @@ int fleet_rmodel_descent(fleet_rmodel* m, const char* merged, size_t len, int cl
   if (len % 4 != 0) return rfail(m, FLEET_ERR_BASE64, "descent: Base64 length %zu is not a multiple of 4", len);
   const size_t n = fleet_b64_count(len), padded = (len + 15) / 16 * 16 + 16;
   int rc;
-  if (padded > m->gtext_cap) {  // grows on the first use (and for a longer text)
-    if (m->gtext) (void)hipFree(m->gtext);
-    m->gtext = nullptr;
-    m->gtext_cap = 0;
-    if ((rc = dev_alloc(m, &m->gtext, padded))) return rc;
-    m->gtext_cap = padded;
-  }
-  if (n + 3 > m->grad_cap) {
-    if (m->grad) (void)hipFree(m->grad);
-    m->grad = nullptr;
-    m->grad_cap = 0;
-    if ((rc = dev_alloc(m, &m->grad, sizeof(float) * (n + 3)))) return rc;
-    m->grad_cap = n + 3;
-  }
+  // both grow on the first use (and for a longer text)
+  if (padded > m->gtext.cap() && (rc = dev_alloc(m, m->gtext, padded))) return rc;
+  if (n + 3 > m->grad.cap() && (rc = dev_alloc(m, m->grad, n + 3))) return rc;
   hipStream_t s = m->stream;
   RM_HIP(m, hipMemsetAsync(m->gtext + (len & ~(size_t)15), 0, padded - (len & ~(size_t)15), s));
   if (len) RM_HIP(m, hipMemcpyAsync(m->gtext, merged, len, hipMemcpyHostToDevice, s));
@@ -510,14 +488,13 @@ int fleet_rmodel_set_solver(fleet_rmodel* m, const char* name) {
   if (m->stepped) return rfail(m, FLEET_ERR_ARG, "set_solver: the model has been stepped");
   const auto rows_of = [](int v) { return (size_t)(v == FLEET_SOLVER_SGD ? 0 : v == FLEET_SOLVER_ADAM ? 2 : 1); };
   // (a second call before the first step starts over: state rows are small beside the versions)
-  if (m->sstate) (void)hipFree(m->sstate);
-  m->sstate = nullptr;
+  m->sstate.reset();
   m->resident_bytes -= sizeof(float) * m->nw * rows_of(m->solver);
   m->solver = FLEET_SOLVER_SGD;
   const size_t bytes = sizeof(float) * m->nw * rows_of(sv);
   if (rows_of(sv)) {
     int rc;
-    if ((rc = dev_alloc(m, &m->sstate, bytes))) return rc;
+    if ((rc = dev_alloc(m, m->sstate, m->nw * rows_of(sv)))) return rc;
     m->resident_bytes += bytes;
     RM_HIP(m, hipMemsetAsync(m->sstate, 0, bytes, m->stream));
     RM_HIP(m, hipStreamSynchronize(m->stream));
@@ -549,7 +526,7 @@ int fleet_rmodel_count(fleet_rmodel* m) {
   return (int)m->models.size();
 }
 
-size_t fleet_rmodel_params_cap(const fleet_rmodel* m) { return m ? m->text_cap : 0; }
+size_t fleet_rmodel_params_cap(const fleet_rmodel* m) { return m ? m->text.cap() : 0; }
 
 int fleet_rmodel_get_params(fleet_rmodel* m, int version, char* out, size_t cap, size_t* out_len) {
   if (!m) return FLEET_ERR_ARG;
@@ -564,7 +541,7 @@ int fleet_rmodel_get_params(fleet_rmodel* m, int version, char* out, size_t cap,
   if (at) RM_HIP(m, hipMemcpyAsync(m->text, m->d_header, at, hipMemcpyDeviceToDevice, s));
   if (m->nb) {
     RM_HIP(m, fleet::model_values_text_ws(row_b(m, row), (int64_t)m->nb, m->d_boff, m->n_bias_blocks, m->tws,
-                                          m->text + at, (int64_t)(m->text_cap - at), &got, s));
+                                          m->text + at, (int64_t)(m->text.cap() - at), &got, s));
     at += (size_t)got;
   } else if (m->n_bias_blocks) {  // every use_bias() layer still prints its line
     RM_HIP(m, hipMemsetAsync(m->text + at, '\n', (size_t)m->n_bias_blocks, s));
@@ -573,7 +550,7 @@ int fleet_rmodel_get_params(fleet_rmodel* m, int version, char* out, size_t cap,
   if (!m->mode) {
     if (m->nw) {
       RM_HIP(m, fleet::model_values_text_ws(row_w(m, row), (int64_t)m->nw, m->d_woff, m->n_mats, m->tws, m->text + at,
-                                            (int64_t)(m->text_cap - at), &got, s));
+                                            (int64_t)(m->text.cap() - at), &got, s));
       at += (size_t)got;
     }
   } else {
@@ -589,12 +566,12 @@ int fleet_rmodel_get_params(fleet_rmodel* m, int version, char* out, size_t cap,
     at += (size_t)cl;
     if (U) {
       RM_HIP(m, fleet::model_values_text_ws(m->d_dict, (int64_t)U, nullptr, 0, m->tws, m->text + at,
-                                            (int64_t)(m->text_cap - at), &got, s));
+                                            (int64_t)(m->text.cap() - at), &got, s));
       at += (size_t)got;
     }
     if (m->nw) {
       RM_HIP(m, fleet::model_index_text_ws(m->d_index, (int64_t)m->nw, m->d_woff, m->n_mats, m->tws, m->text + at,
-                                           (int64_t)(m->text_cap - at), &got, s));
+                                           (int64_t)(m->text.cap() - at), &got, s));
       at += (size_t)got;
     }
   }
@@ -803,15 +780,10 @@ int fleet_rmodel_client_ex_grads_device(fleet_rmodel* m, const int32_t* versions
     n_rows = std::max(n_rows, row + 1);
   }
   hipStream_t s = caller_stream(stream);
-  if (C > m->client_rows_cap) {
-    if (m->d_client_rows) {  // (a call on another stream may still read the old one)
-      RM_HIP(m, hipDeviceSynchronize());
-      (void)hipFree(m->d_client_rows);
-    }
-    m->d_client_rows = nullptr;
-    m->client_rows_cap = 0;
-    if ((rc = dev_alloc(m, &m->d_client_rows, 4 * (size_t)C))) return rc;
-    m->client_rows_cap = C;
+  if ((size_t)C > m->d_client_rows.cap()) {
+    // (a call on another stream may still read the old one)
+    if (m->d_client_rows) RM_HIP(m, hipDeviceSynchronize());
+    if ((rc = dev_alloc(m, m->d_client_rows, (size_t)C))) return rc;
   }
   // pageable source: the copy has left `rows` when the call returns
   RM_HIP(m, hipMemcpyAsync(m->d_client_rows, rows.data(), 4 * (size_t)C, hipMemcpyHostToDevice, s));
