@@ -13,6 +13,15 @@
 // vector computed for every case is written to <vectors.out> after the 22961 draws (doubles),
 // so the caller can compare the digests the fixture holds. Stand-alone, so it also runs under
 // the host sanitizers.
+//
+//   check_client_dp --mirror <jobs.bin> <out.bin>
+//
+// the host mirror alone, for shapes the fixture does not hold (tests/client_dp_jobs.py writes the
+// jobs and reads the output): int32 n, then per job int32 n_models, the model rows (w[21448]
+// then b[82] each), int32 C, B, float temperature, int32 cost, model_of_client[C], clip[C],
+// sigma[C], images[C*B][784] (gathered), labels[C*B], shifts[C*B][2]. Writes per job the C
+// vectors and then the stats [C][3][B] (sqsum, norm, scale; zeros for a client with sigma = 0),
+// and prints per client how many of its samples came out with E NaN.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -44,9 +53,50 @@ bool get(FILE* f, std::vector<T>& v, size_t n) {
   return std::fread(v.data(), sizeof(T), n, f) == n;
 }
 
+int mirror(const char* in, const char* out) {
+  FILE* f = std::fopen(in, "rb");
+  FILE* res = std::fopen(out, "wb");
+  int32_t n = 0;
+  if (!f || !res || std::fread(&n, 4, 1, f) != 1 || n <= 0 || n > 1000) return 2;
+  std::vector<double> z(kGradLen);
+  dp_noise_draws(z.data(), z.size());
+  constexpr size_t kRow = (size_t)kWTotal + kBTotal;
+  for (int i = 0; i < n; ++i) {
+    std::vector<float> models, clip, sigma, x;
+    std::vector<int32_t> model_of, labels, shifts;
+    int32_t n_models = 0, cb[2], cost = 0;
+    float temperature = 0;
+    if (std::fread(&n_models, 4, 1, f) != 1 || n_models <= 0 || n_models > 16 || !get(f, models, n_models * kRow) ||
+        std::fread(cb, 4, 2, f) != 2 || cb[0] <= 0 || cb[1] <= 0 || (int64_t)cb[0] * cb[1] > 100000 ||
+        std::fread(&temperature, 4, 1, f) != 1 || std::fread(&cost, 4, 1, f) != 1 ||
+        (cost != kCostCrossEntropy && cost != kCostDistillation))
+      return 2;
+    const size_t C = (size_t)cb[0], B = (size_t)cb[1];
+    if (!get(f, model_of, C) || !get(f, clip, C) || !get(f, sigma, C) || !get(f, x, C * B * kPix) ||
+        !get(f, labels, C * B) || !get(f, shifts, 2 * C * B))
+      return 2;
+    for (size_t c = 0; c < C; ++c)
+      if (model_of[c] < 0 || model_of[c] >= n_models) return 2;
+    std::vector<float> rows(B * kGradLen), outv(kGradLen), stats(C * 3 * B, 0.0f);
+    for (size_t c = 0; c < C; ++c) {
+      const float* w = models.data() + (size_t)model_of[c] * kRow;
+      const int blown = client_grad_host_ex(w, w + kWTotal, x.data() + c * B * kPix, labels.data() + c * B,
+                                            shifts.data() + 2 * c * B, (int)B, temperature, cost, clip[c], sigma[c],
+                                            z.data(), rows.data(), outv.data(), nullptr, stats.data() + c * 3 * B);
+      std::fwrite(outv.data(), 4, kGradLen, res);
+      std::printf("job %d client %zu blown %d\n", i, c, blown);
+    }
+    std::fwrite(stats.data(), 4, stats.size(), res);
+  }
+  if (std::fgetc(f) != EOF) return 2;  // the writer and this reader disagree on the format
+  std::fclose(f);
+  return std::fclose(res) ? 2 : 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+  if (argc == 4 && !std::strcmp(argv[1], "--mirror")) return mirror(argv[2], argv[3]);
   if (argc != 3) {
     std::fprintf(stderr, "usage: check_client_dp client_dp_ref.bin vectors.out\n");
     return 2;

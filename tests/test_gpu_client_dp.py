@@ -1,7 +1,10 @@
 """DPgradients and the distillation cost on the device: k_client_clip,
 k_client_sum_dp and k_client_sample_distill through every entry point, bit for bit against
 tests/golden/client_dp_ref.npz (recorded from the reference's own network class). Only the
-fixture's shapes run: B <= 4, C <= 3."""
+fixture's shapes run here: B <= 4, C <= 3, the clients of a call on the same samples and model row.
+tests/test_gpu_client_dp_shapes.py runs the shapes beyond them (clients with samples, model rows,
+clips and sigmas of their own, B up to 33, the chunk walk over mixed chunks, clip_scale's edges)
+against the host mirror of the same source."""
 import numpy as np
 import pytest
 
