@@ -241,18 +241,107 @@ class Pending:
     slot: Optional[int] = None      # picker: the upload's slot in the pool
 
 
+class _HostSeat:
+    """The model on the host: ``weights``, ``fc_bias`` and the ``lrates`` schedule, stepped by ``codec.descent``
+    (always sgd). A batch is merged by the host form of its update call: ``(merged, fp32 gradient, ...)``."""
+
+    model = None
+    fused_finish = True  # update_many: push_finish folds a run and merges the batch in one call
+
+    def __init__(self, updater, weights, fc_bias):
+        self.u = updater  # its codec, layout, lrates and curr_epoch are read when they are used
+        self.lr = np.float32(updater.lrates[0])  # initUpdater: cnn.set_learning_rate(lrates_vec[0])
+        self.weights = np.array(weights, dtype=np.float32, copy=True)
+        self.fc_bias = np.array(fc_bias, dtype=np.float32, copy=True)
+
+    def rate(self) -> float:
+        """getLrate() before descentNative (:478): the rate of the previous step."""
+        return float(self.lr)
+
+    def merge(self, obj, form: str, length: int, *args, **host_kw):
+        """``obj.<form>(*args, **host_kw)``; the result begins with ``(merged, fp32)``."""
+        return getattr(obj, form)(*args, **host_kw)
+
+    def merge_uploads(self, uploads, dampen):
+        """A FIFO batch of upload texts: ``(result, length for step)``."""
+        return self.u.codec.update(uploads, dampen, want_f32=True), None
+
+    def step(self, result, length) -> bytes:
+        """descentNative (cppNN_backend.cpp:329-353): lr from the schedule, then the model step."""
+        u, (merged, grad) = self.u, result[:2]
+        if u.curr_epoch < len(u.lrates):
+            self.lr = np.float32(u.lrates[u.curr_epoch])
+        self.weights, self.fc_bias = u.codec.descent(self.weights, self.fc_bias, grad, u.layout, self.lr)
+        return merged
+
+
+class _ResidentSeat:
+    """The model in HBM (a ``fleet_amd.ResidentModel``). A batch is merged by the ``_device`` form of its
+    update call into tensors the seat keeps, the model steps there (``descent_device``), and only the
+    merged text comes back to the host, for the return value. ``weights`` / ``fc_bias`` are not used."""
+
+    weights = fc_bias = None
+    fused_finish = False  # the finish is the accumulator's device form, in _finish_batch
+
+    def __init__(self, updater, model):
+        self.u, self.model = updater, model
+        self.lr = np.float32(updater.lrates[0])
+        self._merged_u8 = self._merged_f32 = None
+        if model.modelsSize() == 0:
+            model.initUpdater(updater.lrates)
+
+    def rate(self) -> float:
+        return float(self.model.getLrate())
+
+    def outputs(self, length: int):
+        """The tensors a device-form update writes: the merged text and decodeFloat of it."""
+        import torch
+        from ._capi import b64_count
+        groups = (b64_count(length) + 2) // 3
+        if self._merged_u8 is None or self._merged_u8.numel() < 16 * groups + 16:
+            dev = f"cuda:{self.u.codec.device}"
+            self._merged_u8 = torch.zeros(16 * groups + 16, dtype=torch.uint8, device=dev)
+            self._merged_f32 = torch.zeros(3 * groups + 4, dtype=torch.float32, device=dev)
+        return self._merged_u8, self._merged_f32
+
+    def merge(self, obj, form: str, length: int, *args, **host_kw):
+        """``obj.<form>_device(*args, merged_u8, merged_f32)``: the host form's result less (merged, fp32)."""
+        return getattr(obj, form + "_device")(*args, *self.outputs(length))
+
+    def merge_uploads(self, uploads, dampen):
+        import torch
+        length = len(uploads[0])
+        if any(len(u) != length for u in uploads):
+            raise ValueError("the batch's uploads differ in length (one model layout)")
+        mu8, mf32 = self.outputs(length)
+        pitch = (length + 15) // 16 * 16 + 16
+        rows = np.zeros((len(uploads), pitch), np.uint8)
+        for i, u in enumerate(uploads):
+            rows[i, :length] = np.frombuffer(u, np.uint8)
+        d_rows = torch.from_numpy(rows).to(f"cuda:{self.u.codec.device}")
+        self.u.codec.update_device(d_rows, length, dampen, self.u.layout.header_positions(), mu8, mf32)
+        self.u.codec.check()  # a malformed upload raises before the model steps
+        return None, length
+
+    def step(self, result, length: int) -> bytes:
+        """descentNative from the merged gradient in HBM; the merged text is all that is copied to the host."""
+        from ._capi import b64_count
+        self.model.descent_device(self._merged_f32, self.u.stale_size, n_values=b64_count(length))
+        self.lr = np.float32(self.model.getLrate())
+        return self._merged_u8[:length].cpu().numpy().tobytes()
+
+
 class FleetUpdater:
     """CppNNUpdater.update's aggregation + descentNative's model step.
 
-    ``weights`` (the non-null W concatenated in slot order) and ``fc_bias`` (the
-    fully-connected layers' biases) are the model the server keeps
-    (``cnn`` in cppNN_backend.cpp); ``lrates`` is initUpdater's schedule
-    (cppNN_backend.cpp:161-172). With ``model=`` (a ``fleet_amd.ResidentModel``) the model lives in
-    HBM instead: ``weights`` and ``fc_bias`` may be None, every path runs the device form of its
-    update into tensors the updater keeps and steps the model there (``descent_device``), and
-    only the merged text comes back to the host. ``kardam_models=`` may be that same model.
-    The model steps under the solver it was made with (``ResidentModel(..., solver=)``); the
-    ``weights=`` / ``fc_bias=`` path keeps no solver state and is always sgd."""
+    ``weights`` (the non-null W concatenated in slot order) and ``fc_bias`` (the fully-connected layers'
+    biases) are the model the server keeps (``cnn`` in cppNN_backend.cpp); ``lrates`` is initUpdater's
+    schedule (cppNN_backend.cpp:161-172). With ``model=`` (a ``fleet_amd.ResidentModel``) the model lives
+    in HBM instead: ``weights`` and ``fc_bias`` may be None, every path runs the device form of its update
+    into tensors the updater keeps and steps the model there (``descent_device``), and only the merged
+    text comes back to the host. ``kardam_models=`` may be that same model. The model steps under the
+    solver it was made with (``ResidentModel(..., solver=)``); the ``weights=`` / ``fc_bias=`` path keeps
+    no solver state and is always sgd."""
 
     def __init__(self, codec, layout, M: int, lrates: Sequence[float], weights, fc_bias, policy: int = 0,
                  alpha: float = 0.0, stale_size: int = 0, num_labels: int = 10, has_outlier: bool = False,
@@ -280,84 +369,29 @@ class FleetUpdater:
             raise ValueError("vet checks an upload on its way into the upload pool: it needs a picker")
         if vet_max_norm is not None and not vet:
             raise ValueError("vet_max_norm is a threshold on the norm the vet computes: it needs vet=True")
-        self.codec = codec
-        self.layout = layout
-        self.M = M
-        self.policy = policy
-        self.alpha = alpha
-        self.stale_size = stale_size
-        self.has_outlier = has_outlier
+        self.codec, self.layout, self.M = codec, layout, M
+        self.policy, self.alpha, self.stale_size, self.has_outlier = policy, alpha, stale_size, has_outlier
         self.lrates = [float(v) for v in lrates]
-        self.lr = np.float32(self.lrates[0])  # initUpdater: cnn.set_learning_rate(lrates_vec[0])
-        # model: a fleet_amd.ResidentModel. The model step then is its descent_device on the merged
-        # gradient where the update left it (tensors the updater keeps); only the merged text
-        # comes back to the host, for the return value. weights / fc_bias are not used.
-        self.model = model
-        self.weights = None if model is not None else np.array(weights, dtype=np.float32, copy=True)
-        self.fc_bias = None if model is not None else np.array(fc_bias, dtype=np.float32, copy=True)
-        self._merged_u8 = self._merged_f32 = None
-        if model is not None and model.modelsSize() == 0:
-            model.initUpdater(self.lrates)
+        self._seat = _ResidentSeat(self, model) if model is not None else _HostSeat(self, weights, fc_bias)
         self.curr_epoch = 0
         self.acc: List[Pending] = []
         self.global_labels = [0] * num_labels
         self.last_merged: Optional[bytes] = None
-        # streaming: every upload is folded into a resident sum when it arrives
-        # (Codec.accumulator), so the M-th call is left with one push, the finish and the
-        # model step. With staleSize == 0 picking order is arrival order (:409, :421) and
-        # getDampen reads only curr_epoch and global_labels, which change inside the M-th
-        # call alone (:502-504, descentNative): the factor computed at arrival is the one
-        # the loop below computes for that pick.
-        self.streaming = bool(streaming)
-        self._stream_acc = None
-        # picker: the staleSize > 0 branch (:394-407). ``picker(pending, curr_epoch)`` stands
-        # where staleSim.stalenessSim stands: called at every arrival once M uploads are
-        # buffered, it returns ``(picks, discard)`` -- ``picks`` None when no update is
-        # possible yet (:405-406), else M distinct indices into ``pending`` in pick order;
-        # ``discard`` the indices of buffered uploads to drop unpicked (the simulator's
-        # too-old gradients, which it removes whether or not it picks). The uploads wait in
-        # a pool of ``pool_slots`` slots in HBM and the update folds the picked slots there.
-        self.picker = picker
+        self.streaming = bool(streaming)  # (_push)
+        self.picker = picker  # (_pick)
         self.pool_slots = 4 * M if pool_slots is None else int(pool_slots)
-        self._pool = None
-        # kardam: Kardam's bookkeeping of the picked uploads (:470-484), opt-in. ``kardam`` is a
-        # :class:`Kardam`; its `grads` then live in a ledger beside the pool (``Pool.ledger``),
-        # and one ``Ledger.update`` gives the merged bytes and every pick's setGrad result.
-        # ``kardam_model(tau)`` stands where getModelParametersNative(modelsSize()-1-tau) and
-        # the modelsSize() == staleSize gate stand (:472-474): the picked model's text, or
-        # None when Kardam does not run for that pick (:483-484). The caller holds the
-        # fleet_amd.Model with the versions.
-        # ``kardam_models`` instead: the fleet_amd.Model with the versions itself. The updater then
-        # applies the gate of :472-474 (v = modelsSize()-1-tau >= 0 and modelsSize() == staleSize)
-        # and `models` lives in a model ledger too (``Model.kardam_ledger``): the picked versions
-        # are made resident once each and one ``ModelLedger.update`` gives every pick's setModel
-        # result, so no model text is built and no pick makes a host round trip.
-        self.kardam = kardam
-        self.kardam_model = kardam_model
-        self.kardam_models = kardam_models
-        self._ledger = None
-        self._mledger = None
-        # kardam_filter: the filter CppNNUpdater bypasses (`true ||`, :488). An update then asks a
-        # fleet_amd.KardamFilter for every pick's checkByz norms in the pass that folds the picks,
-        # decides per pick in the Kardam loop (modelsSize() < staleSize or Kardam.check_byz) and
-        # resolves: the average is over the accepted picks, and an update none of whose picks was
-        # accepted has no average -- no model step, the epoch stays, update returns None (:506).
-        self.kardam_filter = bool(kardam_filter)
-        self._filter = None
+        self.kardam, self.kardam_model, self.kardam_models = kardam, kardam_model, kardam_models  # (_update_picked)
+        self.kardam_filter = bool(kardam_filter)  # (_update_filtered)
         self.last_accept: Optional[List[bool]] = None
-        # vet: an arrival goes into the pool through an arrival gate (``Pool.gate`` with the
-        # layout's header codes, ``Gate.put``) instead of ``Pool.put``. An upload that is not
-        # Base64::encode output, or whose header slots are not this model's, is refused on the
-        # request that brought it: it never joins `acc`, does not count toward M, and update
-        # returns None for it, as for the reference's hash mismatch (:350-353). With
-        # ``vet_max_norm`` an upload whose flat gradient's norm (new
-        # ByteVec(getFlatGradient(g)).getNorm()) exceeds it is refused too, its slot dropped.
-        # ``refused`` lists (client_id, status, norm) of every refused arrival. Without vet the
-        # updater makes the calls it made before.
-        self.vet = bool(vet)
+        self.vet = bool(vet)  # (_arrive)
         self.vet_max_norm = None if vet_max_norm is None else float(vet_max_norm)
-        self._gate = None
         self.refused: List[tuple] = []
+        self._stream_acc = self._pool = self._gate = self._ledger = self._mledger = self._filter = None
+
+    weights = property(lambda self: self._seat.weights)
+    fc_bias = property(lambda self: self._seat.fc_bias)
+    lr = property(lambda self: self._seat.lr)
+    model = property(lambda self: self._seat.model)
 
     def _dampen_of(self, p: "Pending") -> float:
         """getDampen for one pick (:463-464) from the current epoch and label vector."""
@@ -365,51 +399,149 @@ class FleetUpdater:
         sim = similarity(p.labels, self.global_labels)
         return get_dampen(self.policy, tau, sim, self.stale_size, self.alpha, self.has_outlier)
 
-    def _push(self, p: "Pending") -> None:
-        a = self._stream_acc
-        if a is None or (a.length != len(p.upload) and a.count == 0):
-            if a is not None:
-                a.close()
-            a = self._stream_acc = self.codec.accumulator(len(p.upload), self.layout.header_positions())
-        p.dampen = self._dampen_of(p)
-        a.push(p.upload, p.dampen)  # a malformed upload raises here and joins nothing
-        p.upload = b""
+    def _add_labels(self, picked) -> None:
+        """The picks' label vectors summed into ``global_labels`` (:502-504)."""
+        window = [0] * len(self.global_labels)
+        for q in picked:
+            for j, v in enumerate(q.labels[: len(window)]):
+                window[j] += v
+        for j, v in enumerate(window):
+            self.global_labels[j] += v
 
-    def _device_out(self, length: int):
-        """The tensors a device-form update writes: the merged text and decodeFloat of it."""
-        import torch
-        from ._capi import b64_count
-        groups = (b64_count(length) + 2) // 3
-        if self._merged_u8 is None or self._merged_u8.numel() < 16 * groups + 16:
-            dev = f"cuda:{self.codec.device}"
-            self._merged_u8 = torch.zeros(16 * groups + 16, dtype=torch.uint8, device=dev)
-            self._merged_f32 = torch.zeros(3 * groups + 4, dtype=torch.float32, device=dev)
-        return self._merged_u8, self._merged_f32
+    def _close_round(self, result, length, averaged: bool = True) -> Optional[bytes]:
+        """The model step on the merged gradient an update left (``result``, ``length``: what the seat's
+        merge gave), then the epoch. With nothing averaged (``avg == null``, :506-512: the filter
+        accepted no pick) there is no model step, the epoch stays and the round returns None."""
+        if not averaged:
+            return None
+        merged = self._seat.step(result, length)
+        self.curr_epoch += 1
+        self.last_merged = merged
+        return merged
 
-    def _step_resident(self, length: int) -> bytes:
-        """descentNative on the resident model from the merged gradient in HBM; the merged text
-        is the one thing copied to the host."""
-        from ._capi import b64_count
-        self.model.descent_device(self._merged_f32, self.stale_size, n_values=b64_count(length))
-        self.lr = np.float32(self.model.getLrate())
-        return self._merged_u8[:length].cpu().numpy().tobytes()
+    def _leave(self, picked) -> None:
+        """Uploads leave the pool and `acc`: the picked ones (:421, :516), whatever was decided about them,
+        or the ones an update found at fault. Everything else stays buffered."""
+        for q in picked:
+            self._pool.drop(q.slot)
+        gone = {q.slot for q in picked}
+        self.acc = [q for q in self.acc if q.slot not in gone]
 
     def update(self, upload: bytes, labels: Sequence[int], epoch: int, client_id: int = 0) -> Optional[bytes]:
-        """One client upload (CppNNUpdater.update, :330-518). Returns the merged
-        gradient when this upload completed a batch of M (and the model stepped),
-        else None."""
+        """One client upload (CppNNUpdater.update, :330-518). Returns the merged gradient when this upload
+        completed a batch of M (and the model stepped), else None."""
         p = Pending(bytes(upload), list(labels), int(epoch), int(client_id))
         if self.picker is not None:
             return self._update_pooled(p)
         if self.streaming:
             self._push(p)
         self.acc.append(p)
-        if len(self.acc) < self.M:  # M-softsync (:388-391)
-            return None
-        return self._finish_batch()
+        return None if len(self.acc) < self.M else self._finish_batch()  # M-softsync (:388-391)
+
+    def _open_acc(self, length: int):
+        """The accumulator for uploads of ``length`` bytes: opened, or re-opened between batches for a new one."""
+        a = self._stream_acc
+        if a is None or (a.length != length and a.count == 0):
+            if a is not None:
+                a.close()
+            a = self._stream_acc = self.codec.accumulator(length, self.layout.header_positions())
+        return a
+
+    def _push(self, p: "Pending") -> None:
+        """streaming: every upload is folded into a resident sum when it arrives (Codec.accumulator), so
+        the M-th call is left with one push, the finish and the model step. With staleSize == 0 picking
+        order is arrival order (:409, :421) and getDampen reads only curr_epoch and global_labels, which
+        change inside the M-th call alone (:502-504, descentNative): the factor computed at arrival is
+        the one _finish_batch's loop computes for that pick."""
+        a = self._open_acc(len(p.upload))
+        p.dampen = self._dampen_of(p)
+        a.push(p.upload, p.dampen)  # a malformed upload raises here and joins nothing
+        p.upload = b""
+
+    def _finish_batch(self, fused=None) -> bytes:
+        """The M-th call's part after the arrival (:420-421, :463-464, :490-516): picks the batch, merges
+        it (``fused``: the (merged, grad) a push_finish already produced) and steps the model."""
+        picked, dampen = [], []
+        for _ in range(self.M):  # FIFO (:420-421)
+            p = self.acc.pop(0)
+            picked.append(p)
+            dampen.append(self._dampen_of(p) if p.dampen is None else p.dampen)
+        self._add_labels(picked)
+        # A merge that raises from here on (codec.update on a malformed upload) leaves the batch popped
+        # and its labels summed, unlike the pooled paths, which drop only the slots at fault.
+        a = self._stream_acc
+        if self.streaming:
+            result, length = fused or self._seat.merge(a, "finish", a.length, want_f32=True), a.length
+        else:
+            result, length = self._seat.merge_uploads([p.upload for p in picked], dampen)
+        merged = self._close_round(result, length)
+        self.acc.clear()  # aggregated.clear() (:516)
+        return merged
+
+    def update_many(self, arrivals) -> List[Optional[bytes]]:
+        """Several uploads that are at hand together: ``arrivals`` is a list of ``(upload, labels, epoch,
+        client_id)``, the result the list of what ``update`` returns for each in turn. With
+        ``streaming=True`` the list is cut at batch boundaries and each run is folded by one call:
+        ``push_many`` for a run that leaves the batch open, ``push_finish`` (the fold and the merged
+        gradient from one kernel; the host model only) followed by the model step for a run that
+        completes it. The factors are computed at arrival, as ``update`` does; ``_dampen_of`` reads
+        ``curr_epoch`` and ``global_labels``, which the model step changes, so a run's factors are
+        computed after the previous run's step. A run is all or nothing: a malformed upload raises and
+        none of its run joins the batch (the runs before it stay)."""
+        arrivals = list(arrivals)
+        if not self.streaming:
+            return [self.update(*a) for a in arrivals]
+        out: List[Optional[bytes]] = []
+        i = 0
+        while i < len(arrivals):
+            room = self.M - len(self.acc)
+            run = [Pending(bytes(u), list(l), int(e), int(cid)) for u, l, e, cid in arrivals[i: i + room]]
+            i += len(run)
+            a = self._open_acc(len(run[0].upload))
+            for p in run:
+                p.dampen = self._dampen_of(p)
+            ups, d = [p.upload for p in run], [p.dampen for p in run]
+            fused = None
+            if len(run) == room and self._seat.fused_finish:
+                fused = a.push_finish(ups, d, want_f32=True)
+            else:
+                a.push_many(ups, d)
+            for p in run:
+                p.upload = b""
+            self.acc.extend(run)
+            out += [None] * (len(run) - 1)
+            out.append(self._finish_batch(fused) if len(run) == room else None)
+        return out
 
     def _update_pooled(self, p: "Pending") -> Optional[bytes]:
         """One arrival with a picker (:383-411, then :420-516 over the picked uploads)."""
+        if not self._arrive(p) or len(self.acc) < self.M:  # M-softsync (:388-391)
+            return None
+        picked = self._pick()
+        if picked is None:  # not possible to update with the buffered uploads (:405-406)
+            return None
+        dampen = [self._dampen_of(q) for q in picked]  # tau from the epoch at pick time (:427)
+        # (before anything changes)
+        versions = None if self.kardam is None or self.kardam_models is None else self._kardam_versions(picked)
+        if self.kardam_filter:
+            return self._update_filtered(picked, dampen, versions)
+        result, kd = self._update_picked(picked, dampen, versions)
+        if kd is not None:
+            (self._kardam_texts_loop if versions is None else self._kardam_models_loop)(picked, *kd)
+        self._add_labels(picked)
+        merged = self._close_round(result, self._pool.length)
+        self._leave(picked)
+        return merged
+
+    def _arrive(self, p: "Pending") -> bool:
+        """The upload takes a free slot of the pool and joins `acc`; False when it was refused.
+        vet: the arrival goes into the pool through an arrival gate (``Pool.gate`` with the layout's
+        header codes, ``Gate.put``) instead of ``Pool.put``. An upload that is not Base64::encode output,
+        or whose header slots are not this model's, is refused on the request that brought it: it never
+        joins `acc`, does not count toward M, and update returns None for it, as for the reference's hash
+        mismatch (:350-353). With ``vet_max_norm`` an upload whose flat gradient's norm (new
+        ByteVec(getFlatGradient(g)).getNorm()) exceeds it is refused too, its slot dropped. ``refused``
+        lists (client_id, status, norm) of every refused arrival."""
         pool = self._pool
         if pool is None:
             pool = self._pool = self.codec.pool(len(p.upload), self.layout.header_positions(), self.pool_slots)
@@ -425,13 +557,21 @@ class FleetUpdater:
                 if v.status == 0:  # a good text that is kept out: the slot it took is freed
                     pool.drop(slot)
                 self.refused.append((p.client_id, v.status, v.norm))
-                return None
+                return False
         else:
             pool.put(slot, p.upload)
         p.slot, p.upload = slot, b""
         self.acc.append(p)
-        if len(self.acc) < self.M:  # M-softsync (:388-391)
-            return None
+        return True
+
+    def _pick(self) -> Optional[List[Pending]]:
+        """picker: the staleSize > 0 branch (:394-407). ``picker(pending, curr_epoch)`` stands where
+        staleSim.stalenessSim stands: called at every arrival once M uploads are buffered, it returns
+        ``(picks, discard)`` -- ``picks`` None when no update is possible yet (:405-406), else M distinct
+        indices into ``pending`` in pick order; ``discard`` the indices of buffered uploads to drop
+        unpicked (the simulator's too-old gradients, which it removes whether or not it picks). The
+        uploads wait in a pool of ``pool_slots`` slots in HBM and the update folds the picked slots
+        there. Returns the picked uploads, or None; the discarded ones are gone either way."""
         picks, discard = self.picker(list(self.acc), self.curr_epoch)
         picks = None if picks is None else [int(i) for i in picks]
         discard = sorted({int(i) for i in discard or ()})
@@ -442,94 +582,70 @@ class FleetUpdater:
             raise ValueError("picker: M distinct indices into the buffered uploads, none of them discarded")
         picked = None if picks is None else [self.acc[i] for i in picks]
         for i in reversed(discard):
-            pool.drop(self.acc.pop(i).slot)
-        if picked is None:  # not possible to update with the buffered uploads (:405-406)
-            return None
-        dampen = [self._dampen_of(q) for q in picked]  # tau from the epoch at pick time (:427)
-        kd = None
-        versions = None
-        if self.kardam is not None and self.kardam_models is not None:
-            versions = self._kardam_versions(picked)  # before anything changes
-        if self.kardam_filter:
-            return self._update_filtered(pool, picked, dampen, versions)
-        try:
-            if self.model is not None:
-                mu8, mf32 = self._device_out(pool.length)
-            if self.kardam is None and self.model is not None:
-                pool.update_device([q.slot for q in picked], dampen, mu8, mf32)
-            elif self.kardam is None:
-                merged, grad = pool.update([q.slot for q in picked], dampen, want_f32=True)
-            else:
-                if self._ledger is None:
-                    self._ledger = self.kardam.ledger = pool.ledger(self.kardam.workers)
-                models = versions if versions is not None else [
-                    self.kardam_model(self.curr_epoch - q.epoch) for q in picked]
-                workers = [-1 if m is None else q.client_id for q, m in zip(picked, models)]
-                # getLrate() before descentNative (:478): the rate of the previous step
-                if self.model is not None:
-                    _, diff, was_set = self._ledger.update_device(
-                        [q.slot for q in picked], dampen, workers, [q.epoch for q in picked],
-                        float(self.model.getLrate()), mu8, mf32)
-                else:
-                    merged, grad, _, diff, was_set = self._ledger.update(
-                        [q.slot for q in picked], dampen, workers, [q.epoch for q in picked], float(self.lr),
-                        want_f32=True)
-                kd = (models, diff, was_set)
-        except Exception as e:
-            self._drop_at_fault(pool, e)
-            raise
-        if kd is not None and versions is not None:
-            self._kardam_models_loop(picked, *kd)
-        elif kd is not None:  # the loop's order (:476-480): a worker picked twice gets the reference's lips
-            for q, m, dn, st in zip(picked, *kd):
-                if m is None:
-                    continue
-                self.kardam.set_model(q.client_id, m)
-                if self.kardam.apply(q.client_id, bool(st), float(dn)):
-                    self.kardam.update_lip(q.client_id)
-        window = [0] * len(self.global_labels)
-        for q in picked:
-            for j, v in enumerate(q.labels[: len(window)]):
-                window[j] += v
-        for j, v in enumerate(window):
-            self.global_labels[j] += v
-        if self.model is not None:
-            merged = self._step_resident(pool.length)
-        else:
-            if self.curr_epoch < len(self.lrates):
-                self.lr = np.float32(self.lrates[self.curr_epoch])
-            self.weights, self.fc_bias = self.codec.descent(self.weights, self.fc_bias, grad, self.layout, self.lr)
-        self.curr_epoch += 1
-        for q in picked:  # the picked uploads leave `acc` (:421), everything else stays buffered
-            pool.drop(q.slot)
-        gone = {q.slot for q in picked}
-        self.acc = [q for q in self.acc if q.slot not in gone]
-        self.last_merged = merged
-        return merged
+            self._pool.drop(self.acc.pop(i).slot)
+        return picked
 
-    def _drop_at_fault(self, pool, e) -> None:
+    def _kardam_ledger(self):
+        """Kardam's `grads` in a ledger beside the pool (``Pool.ledger``), made at first use."""
+        if self._ledger is None:
+            self._ledger = self.kardam.ledger = self._pool.ledger(self.kardam.workers)
+        return self._ledger
+
+    def _update_picked(self, picked, dampen, versions):
+        """The update over the picked slots: ``(result, kd)`` with ``result`` for _close_round and ``kd``
+        None, or Kardam's ``(models, diff, was_set)`` for the Kardam loop.
+        kardam: Kardam's bookkeeping of the picked uploads (:470-484), opt-in. ``kardam`` is a
+        :class:`Kardam`; its `grads` then live in a ledger beside the pool, and one ``Ledger.update``
+        gives the merged bytes and every pick's setGrad result. ``kardam_model(tau)`` stands where
+        getModelParametersNative(modelsSize()-1-tau) and the modelsSize() == staleSize gate stand
+        (:472-474): the picked model's text, or None when Kardam does not run for that pick (:483-484).
+        The caller holds the fleet_amd.Model with the versions. ``kardam_models``: _kardam_models_loop."""
+        pool, seat = self._pool, self._seat
+        slots = [q.slot for q in picked]
+        try:
+            if self.kardam is None:
+                return seat.merge(pool, "update", pool.length, slots, dampen, want_f32=True), None
+            ledger = self._kardam_ledger()
+            models = versions if versions is not None else [
+                self.kardam_model(self.curr_epoch - q.epoch) for q in picked]
+            workers = [-1 if m is None else q.client_id for q, m in zip(picked, models)]
+            result = seat.merge(ledger, "update", pool.length, slots, dampen, workers, [q.epoch for q in picked],
+                                seat.rate(), want_f32=True)
+            return result, (models, *result[-2:])  # (..., norm_g, norm_diff, set)
+        except Exception as e:
+            self._drop_at_fault(e)
+            raise
+
+    def _drop_at_fault(self, e) -> None:
         """Base64Error / LayoutError of an update: the slots at fault leave, the model stays."""
         bad = set(getattr(e, "slots", ()))
-        for q in self.acc:
-            if q.slot in bad:
-                pool.drop(q.slot)
-        self.acc = [q for q in self.acc if q.slot not in bad]
+        self._leave([q for q in self.acc if q.slot in bad])
 
-    def _update_filtered(self, pool, picked, dampen, versions) -> Optional[bytes]:
-        """The update over the picked uploads with Kardam's filter (:417-516, :488 without its
-        `true ||`): currModel's norms, one KardamFilter.update for every pick's norms and the
-        optimistic result, the Kardam loop with the decision after each pick's updateLip, the
-        resolve over what was accepted."""
+    def _kardam_texts_loop(self, picked, models, diff, was_set) -> None:
+        """The Kardam loop over ``kardam_model``'s texts, in the loop's order (:476-480): a worker
+        picked twice gets the reference's lips."""
+        for q, m, dn, st in zip(picked, models, diff, was_set):
+            if m is None:
+                continue
+            self.kardam.set_model(q.client_id, m)
+            if self.kardam.apply(q.client_id, bool(st), float(dn)):
+                self.kardam.update_lip(q.client_id)
+
+    def _update_filtered(self, picked, dampen, versions) -> Optional[bytes]:
+        """The update over the picked uploads with Kardam's filter (:417-516, :488 without its `true ||`,
+        which CppNNUpdater bypasses): currModel's norms, one KardamFilter.update for every pick's
+        checkByz norms and the optimistic result in the pass that folds the picks, the Kardam loop with
+        the decision after each pick's updateLip (modelsSize() < staleSize or Kardam.check_byz), the
+        resolve: the average is over the accepted picks, and an update none of whose picks was accepted
+        has no average -- no model step, the epoch stays, update returns None (:506)."""
         from .model import ResidentModel
-        km = self.kardam_models
+        pool, seat, km = self._pool, self._seat, self.kardam_models
         n_models = km.modelsSize()
-        if self._ledger is None:
-            self._ledger = self.kardam.ledger = pool.ledger(self.kardam.workers)
+        ledger = self._kardam_ledger()
         if self._filter is None:
             nw, nb, ge, _ = km.shape()
-            self._filter = self._ledger.filter(nw, nb, ge)
+            self._filter = ledger.filter(nw, nb, ge)
         f = self._filter
-        slots, epochs = [q.slot for q in picked], [q.epoch for q in picked]
         workers = [-1 if v is None else q.client_id for q, v in zip(picked, versions)]
         try:
             if isinstance(km, ResidentModel):  # currModel (:417)
@@ -537,14 +653,11 @@ class FleetUpdater:
             else:
                 norm_model, norm_model_diff = f.set_model(*km.export(n_models - 1))
             has_last = f.has_last
-            if self.model is not None:
-                mu8, mf32 = self._device_out(pool.length)
-                _, diff, was_set, norm_p, norm_pdiff = f.update_device(
-                    slots, dampen, workers, epochs, float(self.model.getLrate()), mu8, mf32)
-            else:
-                _, _, _, diff, was_set, norm_p, norm_pdiff = f.update(slots, dampen, workers, epochs, float(self.lr))
+            diff, was_set, norm_p, norm_pdiff = seat.merge(
+                f, "update", pool.length, [q.slot for q in picked], dampen, workers, [q.epoch for q in picked],
+                seat.rate())[-4:]  # (..., norm_g, norm_diff, set, norm_p, norm_pdiff)
         except Exception as e:
-            self._drop_at_fault(pool, e)
+            self._drop_at_fault(e)
             raise
         accept: List[bool] = []
 
@@ -553,30 +666,10 @@ class FleetUpdater:
                 picked[k].client_id, float(norm_p[k]), float(norm_pdiff[k]), norm_model, norm_model_diff, has_last))
         self._kardam_models_loop(picked, versions, diff, was_set, decide)
         self.last_accept = list(accept)
-        window = [0] * len(self.global_labels)
-        for q in picked:
-            for j, v in enumerate(q.labels[: len(window)]):
-                window[j] += v
-        for j, v in enumerate(window):
-            self.global_labels[j] += v
-        merged = None
-        if self.model is not None:
-            if f.resolve_device(accept, mu8, mf32):
-                merged = self._step_resident(pool.length)
-        else:
-            r = f.resolve(accept, want_f32=True)
-            if r is not None:
-                merged, grad = r
-                if self.curr_epoch < len(self.lrates):
-                    self.lr = np.float32(self.lrates[self.curr_epoch])
-                self.weights, self.fc_bias = self.codec.descent(self.weights, self.fc_bias, grad, self.layout, self.lr)
-        if merged is not None:  # avg != null (:506-512)
-            self.curr_epoch += 1
-            self.last_merged = merged
-        for q in picked:  # the picked uploads leave `acc` whatever was decided (:421, :516)
-            pool.drop(q.slot)
-        gone = {q.slot for q in picked}
-        self.acc = [q for q in self.acc if q.slot not in gone]
+        self._add_labels(picked)
+        result = seat.merge(f, "resolve", pool.length, accept, want_f32=True)  # None / False: none accepted
+        merged = self._close_round(result, pool.length, averaged=bool(result))
+        self._leave(picked)
         return merged
 
     def _kardam_versions(self, picked) -> List[Optional[int]]:
@@ -593,16 +686,18 @@ class FleetUpdater:
         return out
 
     def _kardam_models_loop(self, picked, versions, diff, was_set, decide=None) -> None:
-        """setModel for every pick from one model-ledger update, then the loop's host part in
-        pick order (:476-480): apply_model, apply, update_lip. ``decide(k)``, when given, runs
-        after pick k's part, for every pick (:488)."""
+        """``kardam_models``: the fleet_amd.Model with the versions itself. The updater applies the gate of
+        :472-474 (_kardam_versions) and `models` lives in a model ledger too (``Model.kardam_ledger``):
+        the picked versions are made resident once each and one ``ModelLedger.update`` gives every pick's
+        setModel result, so no model text is built and no pick makes a host round trip. Then the loop's
+        host part in pick order (:476-480): apply_model, apply, update_lip. ``decide(k)``, when given,
+        runs after pick k's part, for every pick (:488)."""
+        if self._mledger is None:
+            if self.kardam.model_ledger is None:
+                self.kardam.model_ledger = self.kardam_models.kardam_ledger(
+                    self.kardam.workers, max(1, self.stale_size))
+            self._mledger = self.kardam.model_ledger
         m = self._mledger
-        if m is None:
-            m = self.kardam.model_ledger
-            if m is None:
-                m = self.kardam.model_ledger = self.kardam_models.kardam_ledger(self.kardam.workers,
-                                                                                max(1, self.stale_size))
-            self._mledger = m
         ids = {}
         for v in versions:
             if v is not None and v not in ids:
@@ -616,100 +711,3 @@ class FleetUpdater:
                     self.kardam.update_lip(q.client_id)
             if decide is not None:
                 decide(k)
-
-    def _finish_batch(self, fused=None) -> bytes:
-        """The M-th call's part after the arrival (:420-421, :463-464, :490-516): picks the
-        batch, merges it (``fused``: the (merged, grad) a push_finish already produced) and
-        steps the model."""
-        picked, dampen = [], []
-        window = [0] * len(self.global_labels)
-        for _ in range(self.M):  # FIFO (:420-421)
-            p = self.acc.pop(0)
-            picked.append(p.upload)
-            dampen.append(self._dampen_of(p) if p.dampen is None else p.dampen)
-            for j, v in enumerate(p.labels[: len(window)]):
-                window[j] += v
-        for j, v in enumerate(window):
-            self.global_labels[j] += v
-        if self.model is not None:
-            return self._finish_resident(picked, dampen)
-        if fused is not None:
-            merged, grad = fused
-        elif self.streaming:
-            merged, grad = self._stream_acc.finish(want_f32=True)
-        else:
-            merged, grad = self.codec.update(picked, dampen, want_f32=True)
-        # descentNative (cppNN_backend.cpp:329-353): lr from the schedule, then the model step
-        if self.curr_epoch < len(self.lrates):
-            self.lr = np.float32(self.lrates[self.curr_epoch])
-        self.weights, self.fc_bias = self.codec.descent(self.weights, self.fc_bias, grad, self.layout, self.lr)
-        self.curr_epoch += 1
-        self.acc.clear()  # aggregated.clear() (:516)
-        self.last_merged = merged
-        return merged
-
-    def _finish_resident(self, picked, dampen) -> bytes:
-        """_finish_batch's merge and step with a resident model: the accumulator's finish_device,
-        or update_device over the batch's uploads, then the step in HBM."""
-        if self.streaming:
-            length = self._stream_acc.length
-            mu8, mf32 = self._device_out(length)
-            self._stream_acc.finish_device(mu8, mf32)
-        else:
-            import torch
-            length = len(picked[0])
-            if any(len(u) != length for u in picked):
-                raise ValueError("the batch's uploads differ in length (one model layout)")
-            mu8, mf32 = self._device_out(length)
-            pitch = (length + 15) // 16 * 16 + 16
-            rows = np.zeros((len(picked), pitch), np.uint8)
-            for i, u in enumerate(picked):
-                rows[i, :length] = np.frombuffer(u, np.uint8)
-            d_rows = torch.from_numpy(rows).to(f"cuda:{self.codec.device}")
-            self.codec.update_device(d_rows, length, dampen, self.layout.header_positions(), mu8, mf32)
-            self.codec.check()  # a malformed upload raises before the model steps
-        merged = self._step_resident(length)
-        self.curr_epoch += 1
-        self.acc.clear()  # aggregated.clear() (:516)
-        self.last_merged = merged
-        return merged
-
-    def update_many(self, arrivals) -> List[Optional[bytes]]:
-        """Several uploads that are at hand together: ``arrivals`` is a list of ``(upload,
-        labels, epoch, client_id)``, the result the list of what ``update`` returns for each
-        in turn. With ``streaming=True`` the list is cut at batch boundaries and each run is
-        folded by one call: ``push_many`` for a run that leaves the batch open,
-        ``push_finish`` (the fold and the merged gradient from one kernel) followed by the
-        model step for a run that completes it. The factors are computed at arrival, as
-        ``update`` does; ``_dampen_of`` reads ``curr_epoch`` and ``global_labels``, which the
-        model step changes, so a run's factors are computed after the previous run's step.
-        A run is all or nothing: a malformed upload raises and none of its run joins the
-        batch (the runs before it stay)."""
-        arrivals = list(arrivals)
-        if not self.streaming:
-            return [self.update(*a) for a in arrivals]
-        out: List[Optional[bytes]] = []
-        i = 0
-        while i < len(arrivals):
-            room = self.M - len(self.acc)
-            run = [Pending(bytes(u), list(l), int(e), int(cid)) for u, l, e, cid in arrivals[i: i + room]]
-            i += len(run)
-            a = self._stream_acc
-            if a is None or (a.length != len(run[0].upload) and a.count == 0):
-                if a is not None:
-                    a.close()
-                a = self._stream_acc = self.codec.accumulator(len(run[0].upload), self.layout.header_positions())
-            for p in run:
-                p.dampen = self._dampen_of(p)
-            ups, d = [p.upload for p in run], [p.dampen for p in run]
-            fused = None
-            if len(run) == room and self.model is None:
-                fused = a.push_finish(ups, d, want_f32=True)
-            else:  # (a resident model: the finish is the device form's, in _finish_batch)
-                a.push_many(ups, d)
-            for p in run:
-                p.upload = b""
-            self.acc.extend(run)
-            out += [None] * (len(run) - 1)
-            out.append(self._finish_batch(fused) if len(run) == room else None)
-        return out
