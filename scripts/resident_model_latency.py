@@ -34,7 +34,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from acc_latency import spread  # noqa: E402
+from model_nets import header, lines  # noqa: E402  (the getParams text builders the tests use)
 
 # the CIFAR-10 network of fleet_amd/layouts.py as a getParams header (the activation names are
 # not read by the model state)
@@ -45,23 +47,12 @@ CIFAR10_DIMS = [(3, 3, 48), (3, 3, 1024), (576, 384, 1), (384, 192, 1), (192, 10
 CIFAR10_BIAS = [16, 64, 384, 192, 10]
 
 
-def lines(values, blocks):
-    out, o = [], 0
-    for n in blocks:
-        out.append("".join("%g " % float(v) for v in values[o:o + n]) + "\n")
-        o += n
-    return "".join(out).encode()
-
-
 def cifar10_texts(codec):
-    names = [n for n, _ in CIFAR10_LAYERS]
-    head = "mojo01\n%d\n" % len(names) + "".join(f"{n}\n{c}\n" for n, c in CIFAR10_LAYERS)
-    head += "%d\n" % (len(names) - 1) + "".join(f"{a}\n{b}\n" for a, b in zip(names, names[1:])) + "0\n"
     rng = np.random.default_rng(10)
     sizes = [c * r * k for c, r, k in CIFAR10_DIMS]
     w = rng.normal(0, 0.05, sum(sizes)).astype(np.float32)
     b = rng.normal(0, 0.05, sum(CIFAR10_BIAS)).astype(np.float32)
-    top = head.encode() + lines(b, CIFAR10_BIAS)
+    top = header(CIFAR10_LAYERS) + lines(b, CIFAR10_BIAS)
     dims = np.array(CIFAR10_DIMS, np.int32).reshape(-1)
     return {0: top + lines(w, sizes), 1: top + codec.model_weights_text(w, dims)}
 
