@@ -186,6 +186,15 @@ SIGNATURES = {
     "fleet_model_evaluate": (i32, [vp, i32, vp, sz, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
     "fleet_rmodel_evaluate": (i32, [vp, i32, vp, sz, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
     "fleet_rmodel_evaluate_device": (i32, [vp, i32, vp, sz, i32, vp, vp, i32, vp, vp, vp, vp]),
+    "fleet_cifar_weight_count": (sz, [i32]),
+    "fleet_cifar_bias_count": (sz, [i32]),
+    "fleet_cifar_block_images": (sz, []),
+    "fleet_cifar_set_grid": (i32, [i32]),
+    "fleet_cifar_test_device": (i32, [vp, i32, vp, vp, vp, sz, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+    "fleet_cifar_test": (i32, [vp, i32, vp, sz, vp, sz, vp, sz, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "fleet_model_cifar_test": (i32, [vp, i32, vp, sz, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "fleet_rmodel_cifar_test": (i32, [vp, i32, vp, sz, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "fleet_rmodel_cifar_test_device": (i32, [vp, i32, vp, sz, i32, vp, vp, i32, vp, vp, vp, vp]),
     "fleet_client_grad_len": (sz, []),
     "fleet_client_grad_set_chunk": (i32, [i32]),
     "fleet_client_grads_device": (i32, [vp, vp, sz, i32, vp, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, vp, sz, vp,

@@ -32,7 +32,8 @@ SOURCES = [("kernels.hip", True), ("stream_kernels.hip", True), ("acc_kernels.hi
            ("fleet_codec.cpp", True), ("launch_plan.cpp", False),  # (file, needs HIP)
            ("model_state.cpp", True), ("teacher.hip", True), ("sampler_state.cpp", True),
            ("rmodel_kernels.hip", True), ("rmodel_state.cpp", True),
-           ("solver_kernels.hip", True), ("eval_kernels.hip", True), ("client_kernels.hip", True)]
+           ("solver_kernels.hip", True), ("eval_kernels.hip", True), ("client_kernels.hip", True),
+           ("cifar_kernels.hip", True)]
 
 
 def _newer(target: str, deps) -> bool:

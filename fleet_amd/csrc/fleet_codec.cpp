@@ -24,6 +24,7 @@
 #include <sched.h>
 
 #include "../../include/fleet_codec.h"
+#include "cifar_forward.h"
 #include "kernels.h"
 #include "solver_host.h"
 #include "solver_math.h"
@@ -134,7 +135,7 @@ struct FLEET_MEM_LOCAL fleet_ctx {
   fleet::DevBuf<uint32_t> d_kflags;
   uint32_t kflag_epoch = 0;
   uint32_t kflag_test_skew = 0;       // fleet_test_kardam_skew: reduce blocks wait for a later epoch
-  // fleet_evaluate_device: the costs and predictions a caller does not take, [B floats | B int32]
+  // fleet_evaluate_device, fleet_cifar_test_device: the costs and predictions a caller does not take, [B floats | B int32]
   // in 8 bytes per image (retired on growth, not freed: an evaluation on another stream may
   // still write it)
   fleet::DevBuf<uint8_t> d_eval;
@@ -1679,6 +1680,83 @@ int fleet_evaluate(fleet_ctx* c, const float* w, size_t n_w, const float* b, siz
     if (accuracy) *accuracy = res[1];
     if (correct) std::memcpy(correct, &res[2], 4);
   }
+  return FLEET_OK;
+}
+
+// ------------------------------------------ test() on the CIFAR network (cifar_kernels.hip)
+
+size_t fleet_cifar_weight_count(int classes) { return (size_t)fleet::cifarnet::weight_count(classes); }
+size_t fleet_cifar_bias_count(int classes) { return (size_t)fleet::cifarnet::bias_count(classes); }
+size_t fleet_cifar_block_images(void) { return (size_t)fleet::cifar_block_images(); }
+int fleet_cifar_set_grid(int max_blocks) { return fleet::cifar_set_grid(max_blocks); }
+
+int fleet_cifar_test_device(fleet_ctx* c, int classes, const void* d_w, const void* d_b, const void* d_images,
+                            size_t n_images, int F, const void* d_labels, const void* d_idx, int B, void* d_pred,
+                            void* d_prob, void* d_cost, void* d_probsN, void* d_result, void* stream) {
+  if (!c || !fleet::cifarnet::classes_ok(classes) || !d_w || !d_b || !d_images || !d_labels || !d_result || B <= 0 ||
+      F < fleet::cifarnet::kPix || n_images == 0 || (!d_idx && (size_t)B > n_images))
+    return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  if (!d_cost || !d_pred) {  // the evaluation's workspace and its rule
+    const hipError_t e = c->d_eval.grow_exact(8 * (size_t)B, 64, &c->retired);
+    if (e != hipSuccess) return nomem(c, "hipMalloc", 8 * (size_t)B, e);
+  }
+  float* cost = d_cost ? (float*)d_cost : (float*)c->d_eval.get();
+  int32_t* pred = d_pred ? (int32_t*)d_pred : (int32_t*)(c->d_eval + c->d_eval.cap() / 2);  // behind the costs
+  HIP_TRY(c, fleet::launch_cifar_test(classes, (const float*)d_w, (const float*)d_b, (const float*)d_images,
+                                      (int64_t)n_images, F, (const int32_t*)d_labels, (const int32_t*)d_idx, B, pred,
+                                      (float*)d_prob, cost, (float*)d_probsN, (float*)d_result, c->d_dev_err,
+                                      pick(c, stream)));
+  return FLEET_OK;
+}
+
+int fleet_cifar_test(fleet_ctx* c, int classes, const float* w, size_t n_w, const float* b, size_t n_b,
+                     const float* images, size_t n_images, int F, const int32_t* labels, const int32_t* idx, int B,
+                     float* error, float* accuracy, int32_t* correct, int32_t* pred, float* prob, float* cost,
+                     float* probsN) {
+  if (!c || !w || !b || !images || !labels || B <= 0 || F < fleet::cifarnet::kPix || n_images == 0) return FLEET_ERR_ARG;
+  if (!fleet::cifarnet::classes_ok(classes)) return fail(c, FLEET_ERR_ARG, "cifar test: %d classes, the network has 10 or 100", classes);
+  if (n_w != fleet_cifar_weight_count(classes) || n_b != fleet_cifar_bias_count(classes))
+    return fail(c, FLEET_ERR_ARG, "cifar test: %zu weights and %zu biases, expected %zu and %zu", n_w, n_b,
+                fleet_cifar_weight_count(classes), fleet_cifar_bias_count(classes));
+  if (!idx && (size_t)B > n_images) return fail(c, FLEET_ERR_ARG, "cifar test: %d images asked of %zu", B, n_images);
+  for (int i = 0; idx && i < B; ++i)
+    if (idx[i] < 0 || (size_t)idx[i] >= n_images)
+      return fail(c, FLEET_ERR_ARG, "image %d: index %d outside the %zu images", i, idx[i], n_images);
+  // the images the evaluation reads: all of them with idx, the first B without
+  const size_t rows = idx ? n_images : (size_t)B, nB = (size_t)B;
+  const size_t o_b = round16(sizeof(float) * n_w), o_x = o_b + round16(sizeof(float) * n_b);
+  const size_t o_l = o_x + round16(sizeof(float) * rows * (size_t)F), o_i = o_l + round16(4 * rows);
+  const size_t o_pred = o_i + round16(4 * nB), o_prob = o_pred + round16(4 * nB), o_cost = o_prob + round16(4 * nB);
+  const size_t o_pn = o_cost + round16(4 * nB), o_res = o_pn + (probsN ? round16(4 * nB * (size_t)classes) : 0);
+  const size_t o_end = o_res + 16;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  int rc;
+  if ((rc = grow_dev(c, c->d_a, o_end))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  uint8_t* d = c->d_a;
+  HIP_TRY(c, hipMemcpyAsync(d, w, sizeof(float) * n_w, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(d + o_b, b, sizeof(float) * n_b, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(d + o_x, images, sizeof(float) * rows * (size_t)F, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(d + o_l, labels, 4 * rows, hipMemcpyHostToDevice, c->stream));
+  if (idx) HIP_TRY(c, hipMemcpyAsync(d + o_i, idx, 4 * nB, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, fleet::launch_cifar_test(classes, (const float*)d, (const float*)(d + o_b), (const float*)(d + o_x),
+                                      (int64_t)rows, F, (const int32_t*)(d + o_l),
+                                      idx ? (const int32_t*)(d + o_i) : nullptr, B, (int32_t*)(d + o_pred),
+                                      (float*)(d + o_prob), (float*)(d + o_cost),
+                                      probsN ? (float*)(d + o_pn) : nullptr, (float*)(d + o_res), c->d_err, c->stream));
+  float res[4] = {0, 0, 0, 0};
+  HIP_TRY(c, hipMemcpyAsync(res, d + o_res, 12, hipMemcpyDeviceToHost, c->stream));
+  if (pred) HIP_TRY(c, hipMemcpyAsync(pred, d + o_pred, 4 * nB, hipMemcpyDeviceToHost, c->stream));
+  if (prob) HIP_TRY(c, hipMemcpyAsync(prob, d + o_prob, 4 * nB, hipMemcpyDeviceToHost, c->stream));
+  if (cost) HIP_TRY(c, hipMemcpyAsync(cost, d + o_cost, 4 * nB, hipMemcpyDeviceToHost, c->stream));
+  if (probsN) HIP_TRY(c, hipMemcpyAsync(probsN, d + o_pn, 4 * nB * (size_t)classes, hipMemcpyDeviceToHost, c->stream));
+  if ((rc = read_err(c, c->stream))) return rc;
+  if (error) *error = res[0];
+  if (accuracy) *accuracy = res[1];
+  if (correct) std::memcpy(correct, &res[2], 4);
   return FLEET_OK;
 }
 

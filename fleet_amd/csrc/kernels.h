@@ -200,6 +200,16 @@ hipError_t launch_eval(const float* w, const float* b, const float* images, int6
                        float* probs10, float* result, int* err, hipStream_t s);
 int eval_block_images();
 int eval_set_grid(int max_blocks);  // 0: three blocks per CU; returns the previous value
+// the Driver's test() on the reference's CIFAR network (cifar_kernels.hip), classes 10 or 100:
+// k_cifar_forward over images idx[0..B) (idx == nullptr: images 0..B-1) of the n_images x F rows,
+// then k_eval_reduce. pred[B], cost[B] and result (float error, float accuracy, int32 correct)
+// are written; prob[B] and probsN[B][classes] when not nullptr. hipErrorInvalidValue for other
+// classes, B <= 0, F < 3072 or a missing pred / cost / result.
+hipError_t launch_cifar_test(int classes, const float* w, const float* b, const float* images, int64_t n_images, int F,
+                             const int32_t* labels, const int32_t* idx, int B, int32_t* pred, float* prob, float* cost,
+                             float* probsN, float* result, int* err, hipStream_t s);
+int cifar_block_images();
+int cifar_set_grid(int max_blocks);  // 0: one block per CU; returns the previous value
 // the client's getGradients (client_kernels.hip): per client c of C its gradients() vector over
 // samples idx[c*B + k] (idx == nullptr: images c*B + k) under shift[c*B + k] = {dx, dy} (nullptr:
 // none) on model row model_of_client[c] (nullptr: row 0) of models (rows of model_pitch floats,

@@ -252,6 +252,66 @@ int fleet::eval_check_mnist(const fleet_model* m, std::string* why) {
   return FLEET_OK;
 }
 
+int fleet::cifar_check(const fleet_model* m, int* classes, std::string* why) {
+  struct Want {
+    const char *name, *type, *act;
+    long args[3];
+    int n_args;
+  };
+  static const Want want[] = {{"I1", "input", "identity", {32, 32, 3}, 3},
+                              {"C1", "convolution", "elu", {3, 16, 1}, 3},
+                              {"P1", "max_pool", "", {3, 2, 0}, 2},
+                              {"C2", "convolution", "elu", {3, 64, 1}, 3},
+                              {"P2", "max_pool", "", {4, 4, 0}, 2},
+                              {"local4", "fully_connected", "relu", {384, 0, 0}, 1},
+                              {"local5", "fully_connected", "relu", {192, 0, 0}, 1},
+                              {"FC2", "fully_connected", "softmax", {10, 0, 0}, 1}};
+  const size_t n = sizeof want / sizeof want[0];
+  auto config = [](const std::string& type, const std::vector<long>& args, const std::string& act) {
+    std::string s = type;
+    for (long a : args) s += " " + std::to_string(a);
+    return act.empty() ? s : s + " " + act;
+  };
+  const char* chain = "the layer graph is not the chain I1 - C1 - P1 - C2 - P2 - local4 - local5 - FC2";
+  int N = 0;
+  for (size_t k = 0; k < n; ++k) {
+    const Want& W = want[k];
+    const bool head = k + 1 == n;  // FC2: 10 or 100 outputs
+    const std::string expect = config(W.type, std::vector<long>(W.args, W.args + W.n_args), W.act) + (head ? " (or 100)" : "");
+    if (k >= m->layers.size()) {
+      *why = std::string("layer ") + std::to_string(k) + " (" + W.name + " " + expect + ") is missing";
+      return FLEET_ERR_ARG;
+    }
+    const Layer& L = m->layers[k];
+    const bool act_ok = L.act == W.act || (k == 0 && L.act.empty());
+    bool args_ok = L.args == std::vector<long>(W.args, W.args + W.n_args);
+    if (head && L.args.size() == 1 && L.args[0] == 100) args_ok = true;
+    if (L.type != W.type || !act_ok || !args_ok) {
+      *why = "layer " + std::to_string(k) + " is " + L.name + " " + config(L.type, L.args, L.act) + ", the CIFAR network has " +
+             W.name + " " + expect;
+      return FLEET_ERR_ARG;
+    }
+    if (head) N = (int)L.args[0];
+  }
+  if (m->layers.size() != n) {
+    *why = "layer " + std::to_string(n) + " (" + m->layers[n].name + ") follows FC2, the CIFAR network ends there";
+    return FLEET_ERR_ARG;
+  }
+  // a chain: every layer feeds the next and nothing else
+  const int32_t dims[15] = {3, 3, 48, 3, 3, 1024, 576, 384, 1, 384, 192, 1, 192, N, 1};
+  if (m->edge_w_size.size() != n - 1 || m->dims.size() != 15) {
+    *why = chain;
+    return FLEET_ERR_ARG;
+  }
+  for (int i = 0; i < 15; ++i)
+    if (m->dims[(size_t)i] != dims[i]) {
+      *why = chain;
+      return FLEET_ERR_ARG;
+    }
+  *classes = N;
+  return FLEET_OK;
+}
+
 namespace {
 
 size_t n_weights(const fleet_model* m) {
@@ -531,6 +591,27 @@ int fleet_model_evaluate(fleet_model* m, int version, const float* images, size_
   const int rc = fleet_evaluate(m->ctx, v->w.data(), v->w.size(), v->b.data(), v->b.size(), images, n_images, F, labels, idx,
                                 B, error, accuracy, correct, pred, prob);
   if (rc) return mfail(m, rc, "evaluate: %s", m->ctx ? fleet_last_error(m->ctx) : "the model has no device context");
+  return FLEET_OK;
+}
+
+int fleet_model_cifar_test(fleet_model* m, int version, const float* images, size_t n_images, int F,
+                           const int32_t* labels, const int32_t* idx, int B, float* error, float* accuracy,
+                           int32_t* correct, int32_t* pred, float* prob) {
+  if (!m) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (!images || !labels || B <= 0 || F < 3 * 32 * 32 || n_images == 0)
+    return mfail(m, FLEET_ERR_ARG, "cifar test: images and labels, B >= 1, F >= 3072");
+  std::string why;
+  int classes = 0;
+  if (fleet::cifar_check(m, &classes, &why)) return mfail(m, FLEET_ERR_ARG, "cifar test: %s", why.c_str());
+  const Version* v = &m->cnn;
+  if (version >= 0) {
+    if ((size_t)version >= m->models.size()) return mfail(m, FLEET_ERR_ARG, "model version %d of %zu", version, m->models.size());
+    v = &m->models[(size_t)version];
+  }
+  const int rc = fleet_cifar_test(m->ctx, classes, v->w.data(), v->w.size(), v->b.data(), v->b.size(), images, n_images, F,
+                                  labels, idx, B, error, accuracy, correct, pred, prob, nullptr, nullptr);
+  if (rc) return mfail(m, rc, "cifar test: %s", m->ctx ? fleet_last_error(m->ctx) : "the model has no device context");
   return FLEET_OK;
 }
 

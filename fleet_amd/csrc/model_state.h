@@ -33,6 +33,10 @@ namespace fleet {
 // FLEET_OK when m is the Driver's MNIST network (Driver/src/main/c++/cppNN_backend.cpp:109-115),
 // the only one the evaluation kernels run; otherwise *why names the first layer that differs
 int eval_check_mnist(const fleet_model* m, std::string* why);
+// FLEET_OK when m is the reference's CIFAR network (Driver/src/main/c++/cppNN_backend.cpp:128-138:
+// type, arguments and activation word of every layer, and the chain), *classes then FC2's size,
+// 10 or 100; otherwise *why names the first layer that differs
+int cifar_check(const fleet_model* m, int* classes, std::string* why);
 }  // namespace fleet
 
 struct fleet_model {

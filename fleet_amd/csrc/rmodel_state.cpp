@@ -56,7 +56,7 @@ struct FLEET_MEM_LOCAL fleet_rmodel {
   int solver = 0;
   bool stepped = false;
   fleet::DevBuf<int32_t> d_client_rows;  // client gradients: the row of every client's version
-  fleet::DevBuf<uint8_t> eval_ws;  // evaluation: [B costs | B predictions | B p | result | staged images, labels, indices]
+  fleet::DevBuf<uint8_t> eval_ws;  // evaluation, either network's: [B costs | B predictions | B p | result | staged images, labels, indices]
   fleet::PinBuf<int> h_pin;  // [0] the error word's copy, [4..] the counts line
   // carved from tab / work
   fleet::RmLayout lay{};
@@ -394,6 +394,71 @@ int evaluate_on(fleet_rmodel* m, int version, const void* d_images, size_t n_ima
   return FLEET_OK;
 }
 
+// both forms of test() on the CIFAR network, the lock held: evaluate_on with cifar_check and
+// fleet_cifar_test_device in its places, on the same workspace
+int cifar_test_on(fleet_rmodel* m, int version, const void* d_images, size_t n_images, int F, const void* d_labels,
+                  const void* d_idx, int B, void* d_pred, void* d_prob, void* d_result, size_t staged, hipStream_t s) {
+  std::string why;
+  int classes = 0;
+  if (fleet::cifar_check(m->host, &classes, &why)) return rfail(m, FLEET_ERR_ARG, "cifar test: %s", why.c_str());
+  int row = 0, rc;
+  if (version >= 0 && (rc = version_row(m, version, &row))) return rc;
+  if ((rc = eval_workspace(m, 3 * r256(4 * (size_t)B) + 256 + staged))) return rc;
+  uint8_t* ws = m->eval_ws;
+  if ((rc = fleet_cifar_test_device(m->ctx, classes, row_w(m, row), row_b(m, row), d_images, n_images, F, d_labels, d_idx,
+                                    B, d_pred ? d_pred : ws + r256(4 * (size_t)B), d_prob, ws, nullptr, d_result,
+                                    (void*)s)))
+    return rfail(m, rc, "cifar test: %s", rc == FLEET_ERR_ARG ? "images, labels and a result, B >= 1 (and <= n_images without indices), F >= 3072"
+                                                              : fleet_last_error(m->ctx));
+  return FLEET_OK;
+}
+
+// the host form of either network's test(), the lock held and the device set: every refusal
+// first, then images, labels and indices staged behind the per-image part of the workspace,
+// evaluate_on / cifar_test_on on the model's own stream, and the results copied out
+int host_test(fleet_rmodel* m, bool cifar, int version, const float* images, size_t n_images, int F,
+              const int32_t* labels, const int32_t* idx, int B, float* error, float* accuracy, int32_t* correct,
+              int32_t* pred, float* prob) {
+  const char* what = cifar ? "cifar test" : "evaluate";
+  const int min_F = cifar ? 3 * 32 * 32 : 28 * 28;
+  if (!images || !labels || B <= 0 || F < min_F || n_images == 0 || (!idx && (size_t)B > n_images))
+    return rfail(m, FLEET_ERR_ARG, "%s: images and labels, B >= 1 (and <= n_images without indices), F >= %d", what, min_F);
+  for (int i = 0; idx && i < B; ++i)
+    if (idx[i] < 0 || (size_t)idx[i] >= n_images)
+      return rfail(m, FLEET_ERR_ARG, "image %d: index %d outside the %zu images", i, idx[i], n_images);
+  std::string why;
+  int classes = 0;
+  if (cifar ? fleet::cifar_check(m->host, &classes, &why) : fleet::eval_check_mnist(m->host, &why))
+    return rfail(m, FLEET_ERR_ARG, "%s: %s", what, why.c_str());
+  int row = 0, rc;
+  if (version >= 0 && (rc = version_row(m, version, &row))) return rc;
+  const size_t rows = idx ? n_images : (size_t)B;  // the images the evaluation reads
+  const size_t per = 3 * r256(4 * (size_t)B) + 256;
+  const size_t o_x = per, o_l = o_x + r256(sizeof(float) * rows * (size_t)F), o_i = o_l + r256(4 * rows);
+  const size_t staged = o_i + r256(4 * (size_t)B) - per;
+  if ((rc = eval_workspace(m, per + staged))) return rc;
+  uint8_t* ws = m->eval_ws;
+  hipStream_t s = m->stream;
+  RM_HIP(m, hipMemcpyAsync(ws + o_x, images, sizeof(float) * rows * (size_t)F, hipMemcpyHostToDevice, s));
+  RM_HIP(m, hipMemcpyAsync(ws + o_l, labels, 4 * rows, hipMemcpyHostToDevice, s));
+  if (idx) RM_HIP(m, hipMemcpyAsync(ws + o_i, idx, 4 * (size_t)B, hipMemcpyHostToDevice, s));
+  uint8_t* d_pred = ws + r256(4 * (size_t)B);
+  uint8_t* d_prob = ws + 2 * r256(4 * (size_t)B);
+  uint8_t* d_res = ws + 3 * r256(4 * (size_t)B);
+  if ((rc = (cifar ? cifar_test_on : evaluate_on)(m, version, ws + o_x, rows, F, ws + o_l, idx ? ws + o_i : nullptr, B,
+                                                  d_pred, d_prob, d_res, staged, s)))
+    return rc;
+  float res[4] = {0, 0, 0, 0};
+  RM_HIP(m, hipMemcpyAsync(res, d_res, 12, hipMemcpyDeviceToHost, s));
+  if (pred) RM_HIP(m, hipMemcpyAsync(pred, d_pred, 4 * (size_t)B, hipMemcpyDeviceToHost, s));
+  if (prob) RM_HIP(m, hipMemcpyAsync(prob, d_prob, 4 * (size_t)B, hipMemcpyDeviceToHost, s));
+  if ((rc = fleet_check(m->ctx, (void*)s))) return rfail(m, rc, "%s: %s", what, fleet_last_error(m->ctx));
+  if (error) *error = res[0];
+  if (accuracy) *accuracy = res[1];
+  if (correct) std::memcpy(correct, &res[2], 4);
+  return FLEET_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -724,39 +789,28 @@ int fleet_rmodel_evaluate(fleet_rmodel* m, int version, const float* images, siz
   if (!m) return FLEET_ERR_ARG;
   std::lock_guard<std::mutex> lk(m->mu);
   RM_SCOPE(m);
-  if (!images || !labels || B <= 0 || F < 28 * 28 || n_images == 0 || (!idx && (size_t)B > n_images))
-    return rfail(m, FLEET_ERR_ARG, "evaluate: images and labels, B >= 1 (and <= n_images without indices), F >= 784");
-  for (int i = 0; idx && i < B; ++i)
-    if (idx[i] < 0 || (size_t)idx[i] >= n_images)
-      return rfail(m, FLEET_ERR_ARG, "image %d: index %d outside the %zu images", i, idx[i], n_images);
-  std::string why;
-  if (fleet::eval_check_mnist(m->host, &why)) return rfail(m, FLEET_ERR_ARG, "evaluate: %s", why.c_str());
-  int row = 0, rc;
-  if (version >= 0 && (rc = version_row(m, version, &row))) return rc;
-  const size_t rows = idx ? n_images : (size_t)B;  // the images the evaluation reads
-  const size_t per = 3 * r256(4 * (size_t)B) + 256;
-  const size_t o_x = per, o_l = o_x + r256(sizeof(float) * rows * (size_t)F), o_i = o_l + r256(4 * rows);
-  const size_t staged = o_i + r256(4 * (size_t)B) - per;
-  if ((rc = eval_workspace(m, per + staged))) return rc;
-  uint8_t* ws = m->eval_ws;
-  hipStream_t s = m->stream;
-  RM_HIP(m, hipMemcpyAsync(ws + o_x, images, sizeof(float) * rows * (size_t)F, hipMemcpyHostToDevice, s));
-  RM_HIP(m, hipMemcpyAsync(ws + o_l, labels, 4 * rows, hipMemcpyHostToDevice, s));
-  if (idx) RM_HIP(m, hipMemcpyAsync(ws + o_i, idx, 4 * (size_t)B, hipMemcpyHostToDevice, s));
-  uint8_t* d_pred = ws + r256(4 * (size_t)B);
-  uint8_t* d_prob = ws + 2 * r256(4 * (size_t)B);
-  uint8_t* d_res = ws + 3 * r256(4 * (size_t)B);
-  if ((rc = evaluate_on(m, version, ws + o_x, rows, F, ws + o_l, idx ? ws + o_i : nullptr, B, d_pred, d_prob, d_res, staged, s)))
-    return rc;
-  float res[4] = {0, 0, 0, 0};
-  RM_HIP(m, hipMemcpyAsync(res, d_res, 12, hipMemcpyDeviceToHost, s));
-  if (pred) RM_HIP(m, hipMemcpyAsync(pred, d_pred, 4 * (size_t)B, hipMemcpyDeviceToHost, s));
-  if (prob) RM_HIP(m, hipMemcpyAsync(prob, d_prob, 4 * (size_t)B, hipMemcpyDeviceToHost, s));
-  if ((rc = fleet_check(m->ctx, (void*)s))) return rfail(m, rc, "evaluate: %s", fleet_last_error(m->ctx));
-  if (error) *error = res[0];
-  if (accuracy) *accuracy = res[1];
-  if (correct) std::memcpy(correct, &res[2], 4);
-  return FLEET_OK;
+  return host_test(m, false, version, images, n_images, F, labels, idx, B, error, accuracy, correct, pred, prob);
+}
+
+int fleet_rmodel_cifar_test_device(fleet_rmodel* m, int version, const void* d_images, size_t n_images, int F,
+                                   const void* d_labels, const void* d_idx, int B, void* d_pred, void* d_prob,
+                                   void* d_result, void* stream) {
+  if (!m) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  RM_SCOPE(m);
+  if (!d_images || !d_labels || !d_result || B <= 0 || F < 3 * 32 * 32 || n_images == 0 || (!d_idx && (size_t)B > n_images))
+    return rfail(m, FLEET_ERR_ARG, "cifar test: images, labels and a result, B >= 1 (and <= n_images without indices), F >= 3072");
+  return cifar_test_on(m, version, d_images, n_images, F, d_labels, d_idx, B, d_pred, d_prob, d_result, 0,
+                       caller_stream(stream));
+}
+
+int fleet_rmodel_cifar_test(fleet_rmodel* m, int version, const float* images, size_t n_images, int F,
+                            const int32_t* labels, const int32_t* idx, int B, float* error, float* accuracy,
+                            int32_t* correct, int32_t* pred, float* prob) {
+  if (!m) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  RM_SCOPE(m);
+  return host_test(m, true, version, images, n_images, F, labels, idx, B, error, accuracy, correct, pred, prob);
 }
 
 int fleet_rmodel_client_ex_grads_device(fleet_rmodel* m, const int32_t* versions, const void* d_images, size_t n_images,

@@ -904,6 +904,52 @@ int fleet_evaluate(fleet_ctx* ctx, const float* w, size_t n_w, const float* b, s
                    size_t n_images, int F, const int32_t* labels, const int32_t* idx, int B, float* error,
                    float* accuracy, int32_t* correct, int32_t* pred, float* prob);
 
+/* The same test() (Driver/src/main/c++/cppNN_backend.cpp:53-75) on the reference's CIFAR
+ * network (:128-138), bit for bit, `classes` = 10 or 100 (:136, :135):
+ *   I1 input 32 32 3, C1 convolution 3 16 1 elu, P1 max_pool 3 2, C2 convolution 3 64 1 elu,
+ *   P2 max_pool 4 4, local4 fully_connected 384 relu, local5 fully_connected 192 relu,
+ *   FC2 fully_connected `classes` softmax.
+ * Per image cnn.forward(x, 1.f, thread, 0) (commonLib/cppNN/network.h:523-592): the
+ * convolutions of layer.h:805-872 in the non-AVX order of core_math.h:136-148, 172-185 (one
+ * running binary32 sum per output, input channel outer, nine taps inner) with elu::fc
+ * (activation.h:172-179); max_pool (layer.h:363-456: strict `<`, ties keep the first, a NaN
+ * in first place stays); fully_connected (layer.h:200-239, dot of core_math.h:67-70) with
+ * relu::f (activation.h:199-206) and, for FC2, softmax::f at temperature 1 (:273-286); then
+ * arg_max, the cost and the closing lines as fleet_evaluate states them, under the same NaN
+ * rule. fleet_amd/csrc/cifar_forward.h restates the arithmetic.
+ * w: the non-null W in order, C1 432, C2 9216, local4 221184, local5 73728, FC2 192 *
+ * classes; b: the use_bias() layers' biases in layer order, 16, 64, 384, 192, classes
+ * (FC2's are carried and not read: softmax adds none). images [n_images][F], F >= 3072:
+ * the first 3072 floats of a row are read, planar (channel, row, column), as
+ * commonLib/cppNN/cifar_parser.h:88-94 delivers them. */
+/* the vector lengths for classes 10 (306480, 666) and 100 (323760, 756); 0 for any other */
+size_t fleet_cifar_weight_count(int classes);
+size_t fleet_cifar_bias_count(int classes);
+/* images a block of the forward kernel takes at a time (its group size) */
+size_t fleet_cifar_block_images(void);
+/* tests: cap the forward kernel's grid at max_blocks so that a small B walks more than one
+ * grid-stride pass (0: the default, one block per CU); returns the previous cap */
+int fleet_cifar_set_grid(int max_blocks);
+/* device buffers, on the caller's stream, not synchronised. Per-image outputs d_pred
+ * (int32[B]), d_prob (float[B], p), d_cost (float[B]), d_probsN (float[B][classes]) may each
+ * be NULL; d_result: float error, float accuracy, int32 correct. Costs and predictions the
+ * caller does not take go to fleet_evaluate_device's workspace, under its rule: allocated on
+ * first use, grown only for a larger B (the old one retired, not freed), and calls that use
+ * it ordered with each other. An index outside [0, n_images) is reported by fleet_check as
+ * FLEET_ERR_ARG, the outputs then unspecified. FLEET_ERR_ARG at once: NULL inputs, classes
+ * not 10 or 100, F < 3072, B <= 0, B > n_images without indices. */
+int fleet_cifar_test_device(fleet_ctx* ctx, int classes, const void* d_w, const void* d_b, const void* d_images,
+                            size_t n_images, int F, const void* d_labels, const void* d_idx, int B, void* d_pred,
+                            void* d_prob, void* d_cost, void* d_probsN, void* d_result, void* stream);
+/* host buffers, synchronous; error, accuracy, correct, pred[B], prob[B], cost[B] and
+ * probsN[B][classes] may each be NULL. FLEET_ERR_ARG before any launch: NULL inputs, classes
+ * not 10 or 100, F < 3072, B <= 0, n_w / n_b other than fleet_cifar_weight_count(classes) /
+ * fleet_cifar_bias_count(classes), an index outside the images. */
+int fleet_cifar_test(fleet_ctx* ctx, int classes, const float* w, size_t n_w, const float* b, size_t n_b,
+                     const float* images, size_t n_images, int F, const int32_t* labels, const int32_t* idx, int B,
+                     float* error, float* accuracy, int32_t* correct, int32_t* pred, float* prob, float* cost,
+                     float* probsN);
+
 /* The client's gradients: Java_..._getGradients' hot loop (Client/app/src/main/cpp/
  * cppNN-lib.cpp:101-113 the train_class calls, :218-234 cnn.gradients() and the upload), for
  * C clients of B samples each. Client c's row is the float vector cnn.gradients() returns
@@ -1163,6 +1209,16 @@ int fleet_mledger_stage_model(fleet_mledger* ledger, fleet_model* m, int version
 int fleet_model_evaluate(fleet_model* m, int version, const float* images, size_t n_images, int F,
                          const int32_t* labels, const int32_t* idx, int B, float* error, float* accuracy,
                          int32_t* correct, int32_t* pred, float* prob);
+/* fleet_cifar_test of models[version] (version -1: cnn), as fleet_model_evaluate is
+ * fleet_evaluate of it: fetchParamsNative + evaluateNative (Driver/src/main/c++/
+ * cppNN_backend.cpp:179-205) of that version's text on the CIFAR network of :128-138. The
+ * model must be that network -- I1 input 32 32 3, C1 convolution 3 16 1 elu, P1 max_pool 3 2,
+ * C2 convolution 3 64 1 elu, P2 max_pool 4 4, local4 fully_connected 384 relu, local5
+ * fully_connected 192 relu, FC2 fully_connected 10 or 100 softmax, from which `classes` is
+ * read -- or FLEET_ERR_ARG names the first layer that differs, with nothing launched. */
+int fleet_model_cifar_test(fleet_model* m, int version, const float* images, size_t n_images, int F,
+                           const int32_t* labels, const int32_t* idx, int B, float* error, float* accuracy,
+                           int32_t* correct, int32_t* pred, float* prob);
 
 /* The same model resident in HBM (fleet_rmodel): `cnn` and every entry of `models`
  * live on the device, so a model step takes a merged gradient that is already there
@@ -1261,6 +1317,16 @@ int fleet_rmodel_evaluate_device(fleet_rmodel* m, int version, const void* d_ima
 int fleet_rmodel_evaluate(fleet_rmodel* m, int version, const float* images, size_t n_images, int F,
                           const int32_t* labels, const int32_t* idx, int B, float* error, float* accuracy,
                           int32_t* correct, int32_t* pred, float* prob);
+/* fleet_model_cifar_test of the resident row, in fleet_rmodel_evaluate's two forms and under
+ * its rules (Driver/src/main/c++/cppNN_backend.cpp:53-75, 128-138, 179-205): no weight crosses
+ * PCIe, the device form runs on the caller's stream and does not synchronise, the workspace is
+ * the evaluation's (one allocation serves both, counted in fleet_rmodel_stats). F >= 3072. */
+int fleet_rmodel_cifar_test_device(fleet_rmodel* m, int version, const void* d_images, size_t n_images, int F,
+                                   const void* d_labels, const void* d_idx, int B, void* d_pred, void* d_prob,
+                                   void* d_result, void* stream);
+int fleet_rmodel_cifar_test(fleet_rmodel* m, int version, const float* images, size_t n_images, int F,
+                            const int32_t* labels, const int32_t* idx, int B, float* error, float* accuracy,
+                            int32_t* correct, int32_t* pred, float* prob);
 /* fleet_client_grads_device with the models taken from the resident rows where they live
  * (cppNN-lib.cpp:101-113, 218-234; network.h:1806-2008, 1551-1611, 1289-1331, 1038-1056):
  * versions[C] (host) names client c's model as fleet_rmodel_evaluate_device names a version
