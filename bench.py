@@ -800,13 +800,16 @@ def end_to_end(torch, codec, name, reps=None):
     dt = min(times)
     # copy-free ingress: the uploads deserialised into one page-locked buffer (a
     # registered direct ByteBuffer on the Java side), DMAed straight to HBM
-    rows = np.empty((M, L), np.uint8)
+    # (allocated page-locked: not every driver can lock memory the process already has)
+    rows = torch.empty((M, L), dtype=torch.uint8, pin_memory=True).numpy()
     for c in range(M):
         rows[c] = np.frombuffer(ups[c], np.uint8)
     codec.register_host(rows)
     try:
         if codec.update_rows(rows, L, d) != merged:
             raise RuntimeError("fleet_update_rows differs from fleet_update")
+        if F.lib().fleet_last_ingress(None) != 2:  # FLEET_INGRESS_PINNED
+            raise RuntimeError("fleet_update_rows staged the registered rows: no copy-free figure to report")
         pt = []
         for _ in range(reps):
             t0 = time.perf_counter()

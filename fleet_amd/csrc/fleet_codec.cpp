@@ -165,7 +165,10 @@ int fail(fleet_ctx* c, int code, const char* fmt, ...) {
 #define HIP_TRY(ctx, expr)                                                                       \
   do {                                                                                           \
     hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess) return fail((ctx), FLEET_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+    if (e_ != hipSuccess) {                                                                      \
+      (void)hipGetLastError(); /* reported here, not by the thread's next launch check */        \
+      return fail((ctx), FLEET_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                 \
+    }                                                                                            \
   } while (0)
 
 // Every entry point runs on its context's device and leaves the calling
@@ -805,15 +808,37 @@ namespace {
 // to lie inside ONE recorded registration. A record cannot tell whether its
 // memory was freed and reused since (the caller's contract, fleet_codec.h:
 // unregister before freeing); it only stops rows that straddle two ranges.
+struct HostReg {
+  uintptr_t base;
+  size_t bytes;
+  bool locked_here;  // hipHostRegister'ed by the library; false: the caller allocated it page-locked
+};
 std::mutex g_reg_mu;
-std::vector<std::pair<uintptr_t, size_t>> g_registered;  // (base, bytes)
+std::vector<HostReg> g_registered;
 
 bool in_one_registration(const void* p, size_t bytes) {
   const uintptr_t a = (uintptr_t)p;
   std::lock_guard<std::mutex> lk(g_reg_mu);
   for (const auto& r : g_registered)
-    if (a >= r.first && bytes <= r.second && a - r.first <= r.second - bytes) return true;
+    if (a >= r.base && bytes <= r.bytes && a - r.base <= r.bytes - bytes) return true;
   return false;
+}
+
+// Does [p, p + bytes) lie inside ONE allocation of host memory that HIP already holds
+// page-locked (hipHostMalloc, torch's pin_memory)? Pageable memory answers the attribute
+// query with an error or with hipMemoryTypeUnregistered, depending on the runtime; a range
+// that runs past its allocation's end is not page-locked as a whole.
+bool is_page_locked(const void* p, size_t bytes) {
+  hipPointerAttribute_t at{};
+  void* base = nullptr;
+  size_t size = 0;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeHost ||
+      hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)base;
+  return a >= b && bytes <= size && a - b <= size - bytes;
 }
 
 int update_multi_impl(fleet_ctx* const* ctxs, int n_ctx, const char* const* uploads, const size_t* lens, int M,
@@ -921,17 +946,22 @@ int fleet_host_register(fleet_ctx* c, void* ptr, size_t bytes) {
     // freed and reused (a collected direct buffer): it is released first
     std::lock_guard<std::mutex> rk(g_reg_mu);
     for (size_t i = g_registered.size(); i-- > 0;) {
-      const auto r = g_registered[i];
-      if (r.first < a + bytes && a < r.first + r.second) {
-        (void)hipHostUnregister((void*)r.first);
-        (void)hipGetLastError();
+      const HostReg r = g_registered[i];
+      if (r.base < a + bytes && a < r.base + r.bytes) {
+        if (r.locked_here) {
+          (void)hipHostUnregister((void*)r.base);
+          (void)hipGetLastError();
+        }
         g_registered.erase(g_registered.begin() + (long)i);
       }
     }
   }
-  HIP_TRY(c, hipHostRegister(ptr, bytes, hipHostRegisterPortable));
+  // memory that was allocated page-locked needs no lock of the library's (and HIP refuses
+  // to register it again): it is only recorded
+  const bool locked = is_page_locked(ptr, bytes);
+  if (!locked) HIP_TRY(c, hipHostRegister(ptr, bytes, hipHostRegisterPortable));
   std::lock_guard<std::mutex> rk(g_reg_mu);
-  g_registered.emplace_back(a, bytes);
+  g_registered.push_back(HostReg{a, bytes, !locked});
   return FLEET_OK;
 }
 
@@ -939,12 +969,16 @@ int fleet_host_unregister(fleet_ctx* c, void* ptr) {
   if (!c || !ptr) return FLEET_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DEVICE_SCOPE(c);
+  bool recorded_only = false;  // allocated page-locked by the caller: nothing of the library's to unlock
   {
     std::lock_guard<std::mutex> rk(g_reg_mu);
     for (size_t i = g_registered.size(); i-- > 0;)
-      if (g_registered[i].first == (uintptr_t)ptr) g_registered.erase(g_registered.begin() + (long)i);
+      if (g_registered[i].base == (uintptr_t)ptr) {
+        recorded_only = !g_registered[i].locked_here;
+        g_registered.erase(g_registered.begin() + (long)i);
+      }
   }
-  HIP_TRY(c, hipHostUnregister(ptr));
+  if (!recorded_only) HIP_TRY(c, hipHostUnregister(ptr));
   return FLEET_OK;
 }
 

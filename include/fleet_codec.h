@@ -141,13 +141,20 @@ int fleet_update_rows(fleet_ctx* ctx, const char* rows, size_t row_pitch, size_t
 int fleet_update_rows_multi(fleet_ctx* const* ctxs, int n_ctx, const char* rows, size_t row_pitch, size_t len, int M,
                             const double* dampen, char* merged, size_t cap, size_t* out_len, float* merged_f32);
 /* Page-lock (hipHostRegister, portable to every device) / release a long-lived
- * host buffer, e.g. the upload rows of fleet_update_rows. The registrations
- * are tracked process-wide: registering a range that overlaps a recorded
- * registration releases the old one first. Contract: unregister BEFORE the
- * memory is freed. The library cannot tell a registration whose memory was
- * freed and reused (a collected Java direct buffer, a new allocation at the
- * same addresses) from a live one: rows inside it would be DMA'd from the
- * stale pinned pages. */
+ * host buffer, e.g. the upload rows of fleet_update_rows. Memory that was
+ * allocated page-locked (hipHostMalloc, torch's pin_memory) is only recorded:
+ * the whole range must lie inside one such allocation, and it needs no
+ * further lock. A lock the driver refuses is reported (FLEET_ERR_HIP, with no
+ * HIP error left behind for the thread's next launch) and nothing is
+ * recorded, so those rows are staged. A driver that cannot lock memory a
+ * process already has (some virtual machines) refuses every pageable range:
+ * there, a caller that wants copy-free rows allocates them page-locked.
+ * The registrations are tracked process-wide: registering a range that
+ * overlaps a recorded registration releases the old one first. Contract:
+ * unregister BEFORE the memory is freed. The library cannot tell a
+ * registration whose memory was freed and reused (a collected Java direct
+ * buffer, a new allocation at the same addresses) from a live one: rows
+ * inside it would be DMA'd from the stale pinned pages. */
 int fleet_host_register(fleet_ctx* ctx, void* ptr, size_t bytes);
 int fleet_host_unregister(fleet_ctx* ctx, void* ptr);
 /* How the last host-buffer update on ctx (fleet_update*, its window on this context)

@@ -77,9 +77,27 @@ def host_rows(torch, codec, name):
     return layout, M, L, rows, bench.dampen_policy(M)
 
 
+def page_locked_copy(torch, a):
+    """`a` in memory allocated page-locked, which every driver serves copy-free once it is
+    registered (not every driver can lock memory the process already has)."""
+    out = torch.empty(a.shape, dtype=torch.uint8, pin_memory=True).numpy()
+    out[...] = a
+    return out
+
+
+def registered_batch(codec, rows, L, d):
+    """fleet_update_rows on the registered rows, which must have gone to HBM copy-free."""
+    import fleet_amd as F
+    merged = codec.update_rows(rows, L, d)
+    if F.lib().fleet_last_ingress(None) != 2:  # FLEET_INGRESS_PINNED
+        raise RuntimeError("fleet_update_rows staged the registered rows")
+    return merged
+
+
 def measure(torch, codec, name, reps, trace_only=False):
     import fleet_amd as F
     layout, M, L, rows, d = host_rows(torch, codec, name)
+    rows = page_locked_copy(torch, rows)
     lib, groups = codec._L, (F.b64_count(L) + 2) // 3
     ptr = [rows[c].ctypes.data for c in range(M)]
     out = np.empty(L + 16, np.uint8)
@@ -121,7 +139,7 @@ def measure(torch, codec, name, reps, trace_only=False):
 
     codec.register_host(rows)
     try:
-        expect = codec.update_rows(rows, L, d)  # warm-up of the batch path (staging, allocations)
+        expect = registered_batch(codec, rows, L, d)  # warm-up of the batch path (staging, allocations)
         for c in range(M):  # and of the streaming one, checked against it
             push(c)
         if finish() != expect:

@@ -44,7 +44,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from acc_latency import HBM_PEAK, host_rows, spread  # noqa: E402
+from acc_latency import HBM_PEAK, host_rows, page_locked_copy, registered_batch, spread  # noqa: E402
 
 
 def measure(torch, codec, name, reps, trace_only=False):
@@ -54,7 +54,8 @@ def measure(torch, codec, name, reps, trace_only=False):
     B = F.ACC_BURST
     # the pick order: a fixed scramble of the slots; upload c lives in slot c
     order = [int(s) for s in np.random.default_rng(M).permutation(M)]
-    picked = np.ascontiguousarray(rows[order])  # the same uploads in pick order, for the batch and accumulator paths
+    # the same uploads in pick order, for the batch and accumulator paths
+    picked = page_locked_copy(torch, rows[order])
     ptr = [rows[c].ctypes.data for c in range(M)]
     pptr = [picked[k].ctypes.data for k in range(M)]
     out = np.empty(L + 16, np.uint8)
@@ -82,7 +83,7 @@ def measure(torch, codec, name, reps, trace_only=False):
     last = order[-1]  # the M-th arrival is the last pick for every path
     codec.register_host(picked)
     try:
-        expect = codec.update_rows(picked, L, d)  # warm-up of the batch path (staging, allocations)
+        expect = registered_batch(codec, picked, L, d)  # warm-up of the batch path (staging, allocations)
         for c in range(M):
             put(c)
         if update() != expect:

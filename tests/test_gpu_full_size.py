@@ -146,7 +146,8 @@ def test_full_size_host_ingress_paths(oracle):
         codec.check()
         want = merged.cpu().numpy()[:L].tobytes()
         want_f32 = merged_f32.cpu().numpy()[:n]
-        rows = np.ascontiguousarray(text.cpu().numpy())  # [M, 16*groups], rows[i, :L] = upload i
+        # [M, 16*groups], rows[i, :L] = upload i; allocated page-locked for fleet_update_rows below
+        rows = torch.empty(text.shape, dtype=torch.uint8, pin_memory=True).copy_(text).numpy()
         ups = [rows[i, :L].tobytes() for i in range(M)]
 
         got, f32 = codec.update(ups, dampen, want_f32=True)
@@ -160,7 +161,7 @@ def test_full_size_host_ingress_paths(oracle):
             assert F.update_rows(cs, rows, L, dampen) == want
         finally:
             codec.unregister_host(rows)
-        assert F.update_rows(cs[:2], rows, L, dampen) == want  # pageable rows: staged copy
+        assert F.update_rows(cs[:2], np.array(rows), L, dampen) == want  # pageable rows: staged copy
 
         # Kardam side outputs at full size on a 16-client slice (kardam_grads is host-paced)
         K = 16

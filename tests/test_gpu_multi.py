@@ -12,6 +12,7 @@ import pytest
 
 import fleet_amd as F
 from fleet_amd.layouts import CIFAR10, MNIST, synthetic
+from hostmem import page_locked
 
 pytestmark = pytest.mark.gpu
 
@@ -95,7 +96,8 @@ def test_update_rows(contexts, oracle, N, pad, pinned):
     ups = uploads_for(oracle, MNIST, 5, seed=21 + pad)
     d = [1.0 / ((c % 3) + 1) for c in range(5)]
     L = len(ups[0])
-    rows = np.full((5, L + pad), ord("!"), np.uint8)  # bytes past len are never read as values
+    # bytes past len are never read as values
+    rows = page_locked((5, L + pad), ord("!")) if pinned else np.full((5, L + pad), ord("!"), np.uint8)
     for i, u in enumerate(ups):
         rows[i, :L] = np.frombuffer(u, np.uint8)
     if pinned:
@@ -105,9 +107,39 @@ def test_update_rows(contexts, oracle, N, pad, pinned):
     finally:
         if pinned:
             contexts[0].unregister_host(rows)
+    assert F.lib().fleet_last_ingress(None) == (2 if pinned else 1)  # FLEET_INGRESS_PINNED / _STAGED
     expected = oracle.update_faithful(ups, d)
     assert merged == expected
     assert np.array_equal(f32.view(np.uint32), oracle.decode_floats(expected).view(np.uint32))
+
+
+@pytest.mark.parametrize("N,pad", [(1, 0), (3, 3)])
+def test_update_rows_pageable_registration(contexts, oracle, N, pad):
+    """Rows in pageable memory: where the driver page-locks them in place (hipHostRegister)
+    they are served copy-free, every context's window of them. Where it cannot, the
+    registration reports that once -- no error is left for the thread's next launch to
+    report -- nothing is recorded and the rows are staged. The bytes are the same."""
+    ups = uploads_for(oracle, MNIST, 4, seed=33 + pad)
+    d = [1.0, 0.5, 0.25, 1 / 3]
+    L = len(ups[0])
+    rows = np.full((4, L + pad), ord("!"), np.uint8)
+    for i, u in enumerate(ups):
+        rows[i, :L] = np.frombuffer(u, np.uint8)
+    expected = oracle.update_faithful(ups, d)
+    try:
+        contexts[0].register_host(rows)
+        locked = True
+    except F.FleetError as e:
+        assert "hipHostRegister" in str(e)
+        locked = False
+    try:
+        assert F.update_rows(contexts[:N], rows, L, d) == expected
+        assert F.lib().fleet_last_ingress(None) == (2 if locked else 1)  # FLEET_INGRESS_PINNED / _STAGED
+    finally:
+        if locked:
+            contexts[0].unregister_host(rows)
+    assert F.update_rows(contexts[:N], rows, L, d) == expected
+    assert F.lib().fleet_last_ingress(None) == 1  # unregistered: staged
 
 
 def test_entry_points_keep_the_callers_device(contexts, oracle):

@@ -11,6 +11,7 @@ import pytest
 
 import fleet_amd as F
 from fleet_amd.layouts import MNIST
+from hostmem import page_locked
 
 JNI = os.path.join(os.path.dirname(F.LIB_PATH), "libfleet_native.so")
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -186,7 +187,7 @@ def test_shim_aggregate_direct_buffer(oracle):
     d = [1.0, 0.5, 1 / 3, 1.0, 0.5]
     Lb = len(ups[0])
     pitch = Lb + 5
-    rows = np.zeros(M * pitch, np.uint8)
+    rows = page_locked(M * pitch)
     for i, u in enumerate(ups):
         rows[i * pitch: i * pitch + Lb] = np.frombuffer(u, np.uint8)
     J.begin()
@@ -246,7 +247,7 @@ def test_shim_direct_buffer_reregistration(oracle):
     ups = [oracle.encode_floats(oracle.synth_upload(9, c, list(MNIST.w_sizes), list(MNIST.b_sizes)))
            for c in range(M)]
     Lb = len(ups[0])
-    rows = np.zeros(M * Lb, np.uint8)
+    rows = page_locked(M * Lb)
     for i, u in enumerate(ups):
         rows[i * Lb:(i + 1) * Lb] = np.frombuffer(u, np.uint8)
     d = [1.0, 0.5, 0.25]
@@ -277,7 +278,7 @@ def test_shim_collected_registration_is_not_used(oracle):
     ups = [oracle.encode_floats(oracle.synth_upload(11, c, list(MNIST.w_sizes), list(MNIST.b_sizes)))
            for c in range(M)]
     Lb = len(ups[0])
-    rows = np.zeros(M * Lb, np.uint8)
+    rows = page_locked(M * Lb)
     for i, u in enumerate(ups):
         rows[i * Lb:(i + 1) * Lb] = np.frombuffer(u, np.uint8)
     d = [1.0, 0.5, 0.25]
