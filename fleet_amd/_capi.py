@@ -209,6 +209,14 @@ SIGNATURES = {
     "fleet_rmodel_client_ex_grads_device": (i32, [vp, vp, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, i32, vp, vp, vp,
                                                   sz, vp, sz, vp]),
     "fleet_client_dp_noise": (i32, [vp, sz]),
+    "fleet_rgbnet_grad_len": (sz, [i32]),
+    "fleet_rgbnet_sample_tile": (sz, []),
+    "fleet_rgbnet_set_chunk": (i32, [i32]),
+    "fleet_rgbnet_grads_device": (i32, [vp, i32, vp, sz, i32, vp, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, vp, sz,
+                                        vp, sz, vp]),
+    "fleet_rgbnet_grads": (i32, [vp, i32, vp, sz, vp, sz, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, vp, vp, sz]),
+    "fleet_rmodel_rgbnet_grads_device": (i32, [vp, vp, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, vp, sz, vp, sz,
+                                               vp]),
     "fleet_model_load": (i32, [vp, vp, sz, i32, C.POINTER(vp)]),
     "fleet_model_destroy": (None, [vp]),
     "fleet_model_last_error": (C.c_char_p, [vp]),

@@ -33,7 +33,9 @@ SOURCES = [("kernels.hip", True), ("stream_kernels.hip", True), ("acc_kernels.hi
            ("model_state.cpp", True), ("teacher.hip", True), ("sampler_state.cpp", True),
            ("rmodel_kernels.hip", True), ("rmodel_state.cpp", True),
            ("solver_kernels.hip", True), ("eval_kernels.hip", True), ("client_kernels.hip", True),
-           ("cifar_kernels.hip", True)]
+           ("cifar_kernels.hip", True), ("cifar_client_kernels.hip", True)]
+# units built without packed fp32 instructions (v_pk_*_f32): every operation its own rounding
+NO_PACKED_FP32 = ("cifar_client_kernels.hip",)
 
 
 def _newer(target: str, deps) -> bool:
@@ -75,6 +77,8 @@ def build_codec(force: bool = False, out: str = LIB, defines=()) -> str:
         main_sched = os.environ.get("FLEET_MAIN_SCHED", "")  # experiments: the main unit's scheduler
         if main_sched and src.endswith("/kernels.hip"):
             extra = ["-mllvm", f"-amdgpu-sched-strategy={main_sched}"]
+        if os.path.basename(src) in NO_PACKED_FP32:
+            extra = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
         _run([HIPCC, *lang, *COMMON, *extra, *[f"-D{d}" for d in defines], "-c", src, "-o", obj])
         return obj
 

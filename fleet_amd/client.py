@@ -134,9 +134,10 @@ def device_args(images_f32, labels_i32, idx, shifts, C, B, grads, uploads):
     return images_f32.shape[0], images_f32.shape[1], C, B, grads, uploads
 
 
-def upload_texts(uploads) -> list:
-    """The Base64 texts of upload rows (device or host), one ``bytes`` per client."""
-    n = b64_len(client_grad_len())
+def upload_texts(uploads, n_values: int = None) -> list:
+    """The Base64 texts of upload rows (device or host), one ``bytes`` per client; ``n_values``:
+    the values of a row where it is not the MNIST vector (:mod:`fleet_amd.cifar_client`)."""
+    n = b64_len(client_grad_len() if n_values is None else int(n_values))
     a = uploads.cpu().numpy() if hasattr(uploads, "cpu") else np.asarray(uploads)
     return [a[c, :n].tobytes() for c in range(a.shape[0])]
 

@@ -195,6 +195,17 @@ FLEET_TM evalnet::Verdict tail(float* node, int N, int32_t label, float* probsN)
   return evalnet::Verdict{max_j, best, mojo_mul(mojo_mul(0.5f, d), d)};
 }
 
+// softmax::f at a temperature in place on node[N] (activation.h:273-286): the head of a
+// training forward (network.h:1857-1861), tail's first three loops with the division kept
+FLEET_TM void softmax_at(float* node, int N, float temperature) {
+  float mx = node[0];
+  for (int j = 1; j < N; ++j)
+    if (node[j] > mx) mx = mojo_div(node[j], temperature);
+  float denom = 0.0f;
+  for (int j = 0; j < N; ++j) denom = mojo_add(denom, mojo_expf(mojo_sub(mojo_div(node[j], temperature), mx)));
+  for (int j = 0; j < N; ++j) node[j] = mojo_div(mojo_expf(mojo_sub(mojo_div(node[j], temperature), mx)), denom);
+}
+
 #if !defined(__HIP_DEVICE_COMPILE__)
 // every layer's node of one image, for the checks (any pointer may be NULL)
 struct Layers {

@@ -1968,6 +1968,105 @@ int fleet_client_grads(fleet_ctx* c, const float* w, size_t n_w, const float* b,
                                FLEET_COST_CROSS_ENTROPY, nullptr, nullptr, grads, uploads, upload_pitch);
 }
 
+// ------------------------------------------ getGradients on the CIFAR network (cifar_client_kernels.hip)
+
+size_t fleet_rgbnet_grad_len(int classes) { return (size_t)fleet::rgbnet_grad_len(classes); }
+size_t fleet_rgbnet_sample_tile(void) { return (size_t)fleet::rgbnet_sample_tile(); }
+int fleet_rgbnet_set_chunk(int max_clients) { return fleet::rgbnet_set_chunk(max_clients); }
+
+namespace {
+
+// both forms, the lock held and the device set: the records' workspace (the one of
+// fleet_client_grads_device, under its rule), the launches per chunk of clients, the encode
+int rgbnet_grads_locked(fleet_ctx* c, int classes, const void* d_models, size_t model_pitch, int n_models,
+                        const void* d_model_of_client, const void* d_images, size_t n_images, int F,
+                        const void* d_labels, const void* d_idx, const void* d_shift, int C, int B, float temperature,
+                        void* d_grads, size_t grad_pitch, void* d_uploads, size_t upload_pitch, hipStream_t s) {
+  const int chunk = fleet::rgbnet_chunk(classes, C, B);
+  const size_t need = fleet::rgbnet_workspace_bytes(classes, chunk, B);
+  const hipError_t ew = c->d_client_ws.grow_exact(need, 64, &c->retired);
+  if (ew != hipSuccess) return nomem(c, "hipMalloc", need, ew);
+  HIP_TRY(c, fleet::launch_rgbnet_grads(classes, (const float*)d_models, (int64_t)model_pitch, n_models,
+                                        (const int32_t*)d_model_of_client, (const float*)d_images, (int64_t)n_images, F,
+                                        (const int32_t*)d_labels, (const int32_t*)d_idx, (const int32_t*)d_shift, C, B,
+                                        chunk, temperature, (float*)c->d_client_ws.get(), (float*)d_grads,
+                                        (int64_t)grad_pitch, c->d_dev_err, s));
+  if (d_uploads)
+    HIP_TRY(c, fleet::launch_encode_f32((const float*)d_grads, (int64_t)fleet_rgbnet_grad_len(classes), grad_pitch, C,
+                                        (uint8_t*)d_uploads, upload_pitch, s));
+  return FLEET_OK;
+}
+
+}  // namespace
+
+int fleet_rgbnet_grads_device(fleet_ctx* c, int classes, const void* d_models, size_t model_pitch, int n_models,
+                              const void* d_model_of_client, const void* d_images, size_t n_images, int F,
+                              const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
+                              float temperature, void* d_grads, size_t grad_pitch, void* d_uploads,
+                              size_t upload_pitch, void* stream) {
+  const size_t n_up = fleet_rgbnet_grad_len(classes);
+  if (!c || !n_up || !d_models || !d_images || !d_labels || !d_grads || C <= 0 || B <= 0 || F < fleet::cifarnet::kPix ||
+      n_models <= 0 || n_images == 0 || model_pitch < fleet_cifar_weight_count(classes) + fleet_cifar_bias_count(classes) ||
+      grad_pitch < n_up || (size_t)C * (size_t)B > (size_t)INT32_MAX || (!d_idx && (size_t)C * (size_t)B > n_images))
+    return FLEET_ERR_ARG;
+  if (d_uploads && (upload_pitch % 16 != 0 || upload_pitch < 16 * groups_of(n_up)))
+    return fail(c, FLEET_ERR_ARG, "bad upload pitch");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  return rgbnet_grads_locked(c, classes, d_models, model_pitch, n_models, d_model_of_client, d_images, n_images, F,
+                             d_labels, d_idx, d_shift, C, B, temperature, d_grads, grad_pitch, d_uploads, upload_pitch,
+                             pick(c, stream));
+}
+
+int fleet_rgbnet_grads(fleet_ctx* c, int classes, const float* w, size_t n_w, const float* b, size_t n_b,
+                       const float* images, size_t n_images, int F, const int32_t* labels, const int32_t* idx,
+                       const int32_t* shifts, int C, int B, float temperature, float* grads, char* uploads,
+                       size_t upload_pitch) {
+  if (!c || !w || !b || !images || !labels || !grads || C <= 0 || B <= 0 || F < fleet::cifarnet::kPix || n_images == 0)
+    return FLEET_ERR_ARG;
+  if (!fleet::cifarnet::classes_ok(classes))
+    return fail(c, FLEET_ERR_ARG, "client gradients: %d classes, the network has 10 or 100", classes);
+  if (n_w != fleet_cifar_weight_count(classes) || n_b != fleet_cifar_bias_count(classes))
+    return fail(c, FLEET_ERR_ARG, "client gradients: %zu weights and %zu biases, expected %zu and %zu", n_w, n_b,
+                fleet_cifar_weight_count(classes), fleet_cifar_bias_count(classes));
+  const size_t n = (size_t)C * (size_t)B, n_up = fleet_rgbnet_grad_len(classes);
+  if (n > (size_t)INT32_MAX) return fail(c, FLEET_ERR_ARG, "client gradients: %d clients of %d samples", C, B);
+  if (!idx && n > n_images) return fail(c, FLEET_ERR_ARG, "client gradients: %zu images asked of %zu", n, n_images);
+  for (size_t i = 0; idx && i < n; ++i)
+    if (idx[i] < 0 || (size_t)idx[i] >= n_images)
+      return fail(c, FLEET_ERR_ARG, "sample %zu: index %d outside the %zu images", i, idx[i], n_images);
+  for (size_t i = 0; shifts && i < 2 * n; ++i)
+    if (shifts[i] < -1 || shifts[i] > 1)
+      return fail(c, FLEET_ERR_ARG, "sample %zu: shift %d outside {-1, 0, 1}", i / 2, shifts[i]);
+  const size_t up_len = fleet_b64_len(n_up), groups_bytes = 16 * groups_of(n_up);
+  if (uploads && upload_pitch < up_len) return fail(c, FLEET_ERR_CAPACITY, "upload pitch %zu < %zu", upload_pitch, up_len);
+  const size_t rows = idx ? n_images : n;  // the images the call reads
+  const size_t o_x = round16(sizeof(float) * (n_w + n_b)), o_l = o_x + round16(sizeof(float) * rows * (size_t)F);
+  const size_t o_i = o_l + round16(4 * rows), o_s = o_i + round16(4 * n), o_g = o_s + round16(8 * n);
+  const size_t o_u = o_g + round16(sizeof(float) * (size_t)C * n_up), o_end = o_u + (uploads ? (size_t)C * groups_bytes : 0);
+  int rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DEVICE_SCOPE(c);
+  if ((rc = grow_dev(c, c->d_a, o_end))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  uint8_t* d = c->d_a;
+  HIP_TRY(c, hipMemcpyAsync(d, w, sizeof(float) * n_w, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(d + sizeof(float) * n_w, b, sizeof(float) * n_b, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(d + o_x, images, sizeof(float) * rows * (size_t)F, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(d + o_l, labels, 4 * rows, hipMemcpyHostToDevice, c->stream));
+  if (idx) HIP_TRY(c, hipMemcpyAsync(d + o_i, idx, 4 * n, hipMemcpyHostToDevice, c->stream));
+  if (shifts) HIP_TRY(c, hipMemcpyAsync(d + o_s, shifts, 8 * n, hipMemcpyHostToDevice, c->stream));
+  if ((rc = rgbnet_grads_locked(c, classes, d, n_w + n_b, 1, nullptr, d + o_x, rows, F, d + o_l, idx ? d + o_i : nullptr,
+                                shifts ? d + o_s : nullptr, C, B, temperature, d + o_g, n_up, uploads ? d + o_u : nullptr,
+                                groups_bytes, c->stream)))
+    return rc;
+  HIP_TRY(c, hipMemcpyAsync(grads, d + o_g, sizeof(float) * (size_t)C * n_up, hipMemcpyDeviceToHost, c->stream));
+  if (uploads)
+    HIP_TRY(c, hipMemcpy2DAsync(uploads, upload_pitch, d + o_u, groups_bytes, up_len, (size_t)C, hipMemcpyDeviceToHost,
+                                c->stream));
+  return read_err(c, c->stream, c->d_dev_err);
+}
+
 int fleet_model_params(fleet_ctx* c, const float* weights, size_t n_weights, const float* biases, size_t n_biases,
                        int graph_edges, char* out, size_t cap, size_t* out_len) {
   if (!c || graph_edges < 0 || (n_weights && !weights) || (n_biases && !biases)) return FLEET_ERR_ARG;

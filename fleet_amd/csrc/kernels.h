@@ -235,6 +235,20 @@ int64_t client_grad_len();  // 22961
 size_t client_grad_workspace_bytes(int chunk, int B);
 int client_grad_chunk(int C, int B);
 int client_grad_set_chunk(int max_clients);  // 0: what fits the workspace cap; returns the previous value
+// the client's getGradients on the CIFAR network (cifar_client_kernels.hip), classes 10 or 100:
+// launch_client_grads' arguments on that network's model rows (w then b, cifar_forward.h's
+// layout), into grads (rows of grad_pitch >= rgbnet_grad_len(classes) floats), `chunk` clients at
+// a time. workspace: rgbnet_workspace_bytes(classes, chunk, B), the samples' records.
+hipError_t launch_rgbnet_grads(int classes, const float* models, int64_t model_pitch, int n_models,
+                               const int32_t* model_of_client, const float* images, int64_t n_images, int F,
+                               const int32_t* labels, const int32_t* idx, const int32_t* shift, int C, int B, int chunk,
+                               float temperature, float* workspace, float* grads, int64_t grad_pitch, int* err,
+                               hipStream_t s);
+int64_t rgbnet_grad_len(int classes);  // 313867, 331237; 0 for other classes
+int rgbnet_sample_tile();              // samples k_rgb_fc_sum stages at a time
+size_t rgbnet_workspace_bytes(int classes, int chunk, int B);
+int rgbnet_chunk(int classes, int C, int B);
+int rgbnet_set_chunk(int max_clients);  // 0: what fits the workspace cap; returns the previous value
 hipError_t launch_encode_model_params(const float* weights, int64_t n_w, const float* biases, int64_t n_b, int64_t reps,
                                       uint8_t* out, hipStream_t s);
 hipError_t launch_encode_i32(const int32_t* codes, int64_t n, uint8_t* out, hipStream_t s);

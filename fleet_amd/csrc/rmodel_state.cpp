@@ -858,6 +858,42 @@ int fleet_rmodel_client_grads_device(fleet_rmodel* m, const int32_t* versions, c
                                              grad_pitch, d_uploads, upload_pitch, stream);
 }
 
+int fleet_rmodel_rgbnet_grads_device(fleet_rmodel* m, const int32_t* versions, const void* d_images, size_t n_images,
+                                     int F, const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
+                                     float temperature, void* d_grads, size_t grad_pitch, void* d_uploads,
+                                     size_t upload_pitch, void* stream) {
+  if (!m) return FLEET_ERR_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  RM_SCOPE(m);
+  if (!versions || !d_images || !d_labels || !d_grads || C <= 0 || B <= 0 || F < 3 * 32 * 32 || n_images == 0)
+    return rfail(m, FLEET_ERR_ARG, "client gradients: versions, images, labels and rows, C >= 1, B >= 1, F >= 3072");
+  std::string why;
+  int classes = 0;
+  if (fleet::cifar_check(m->host, &classes, &why)) return rfail(m, FLEET_ERR_ARG, "client gradients: %s", why.c_str());
+  std::vector<int32_t> rows((size_t)C, 0);
+  int rc, n_rows = 1;
+  for (int c = 0; c < C; ++c) {
+    int row = 0;
+    if (versions[c] >= 0 && (rc = version_row(m, versions[c], &row))) return rc;
+    rows[(size_t)c] = row;
+    n_rows = std::max(n_rows, row + 1);
+  }
+  hipStream_t s = caller_stream(stream);
+  if ((size_t)C > m->d_client_rows.cap()) {
+    // (a call on another stream may still read the old one)
+    if (m->d_client_rows) RM_HIP(m, hipDeviceSynchronize());
+    if ((rc = dev_alloc(m, m->d_client_rows, (size_t)C))) return rc;
+  }
+  // pageable source: the copy has left `rows` when the call returns
+  RM_HIP(m, hipMemcpyAsync(m->d_client_rows, rows.data(), 4 * (size_t)C, hipMemcpyHostToDevice, s));
+  if ((rc = fleet_rgbnet_grads_device(m->ctx, classes, m->state, m->stride, n_rows, m->d_client_rows, d_images, n_images,
+                                      F, d_labels, d_idx, d_shift, C, B, temperature, d_grads, grad_pitch, d_uploads,
+                                      upload_pitch, (void*)s)))
+    return rfail(m, rc, "client gradients: %s", rc == FLEET_ERR_ARG ? "C*B images without indices, a row pitch of the vector's length, an upload pitch of whole groups"
+                                                                     : fleet_last_error(m->ctx));
+  return FLEET_OK;
+}
+
 int fleet_rmodel_stats(fleet_rmodel* m, size_t* resident_bytes, int* device_allocs) {
   if (!m) return FLEET_ERR_ARG;
   std::lock_guard<std::mutex> lk(m->mu);

@@ -1048,6 +1048,42 @@ int fleet_client_ex_grads(fleet_ctx* ctx, const float* w, size_t n_w, const floa
  * resident. Nothing of it is computed on the device. */
 int fleet_client_dp_noise(double* out, size_t n);
 
+/* The client's gradients on the reference's CIFAR-10/100 network (the network of the test()
+ * above; classes 10 or 100): the calls above on that network, with the cross_entropy cost.
+ * Client c's row is what cnn.gradients() returns after train_class on its B samples in the
+ * single-thread order: fleet_rgbnet_grad_len(classes) = 313867 or 331237 values (0 for any other
+ * classes), [7, (size, dW..)*, 8, (size, dbias..)*] with dW blocks C1 432, 0, C2 9216, 0,
+ * local4 221184, local5 73728, FC2 192 * classes and dbias blocks I1 3072, 0, P1 3136, 0,
+ * P2 576, local4 384, local5 192, FC2 classes. Per sample: the shift on each of the three
+ * planes, the training forward (both max_pools keep their picks, softmax at `temperature`),
+ * the output delta, both passes of backward_hidden; then dW_sets[0] += dW_sets[b] in sample
+ * order. fleet_amd/csrc/cifar_backward.h restates every step with the reference's lines, and
+ * the device computes that restatement's bits; no vector recorded from the reference's own
+ * network class stands behind this path yet. The NaN rule is the one above. Models: w then b
+ * in the CIFAR test()'s layout. Not covered: DPgradients and the distillation cost on this
+ * network. */
+size_t fleet_rgbnet_grad_len(int classes);
+/* samples whose nodes and deltas the fully connected dW kernel stages at a time (tests: B at
+ * and just above it) */
+size_t fleet_rgbnet_sample_tile(void);
+/* tests: walk the clients in chunks of at most max_clients (0: the default, what fits a
+ * 256 MiB workspace of per-sample records); returns the previous value */
+int fleet_rgbnet_set_chunk(int max_clients);
+/* fleet_client_grads_device's arguments and rules with `classes`: F >= 3072, model_pitch >=
+ * weights + biases of that network, grad_pitch >= fleet_rgbnet_grad_len(classes), upload_pitch a
+ * multiple of 16 holding the vector's groups. The workspace is that call's. */
+int fleet_rgbnet_grads_device(fleet_ctx* ctx, int classes, const void* d_models, size_t model_pitch, int n_models,
+                              const void* d_model_of_client, const void* d_images, size_t n_images, int F,
+                              const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
+                              float temperature, void* d_grads, size_t grad_pitch, void* d_uploads,
+                              size_t upload_pitch, void* stream);
+/* fleet_client_grads' arguments and rules with `classes`; FLEET_ERR_ARG before any launch also
+ * for classes other than 10 or 100 and n_w / n_b other than that network's counts */
+int fleet_rgbnet_grads(fleet_ctx* ctx, int classes, const float* w, size_t n_w, const float* b, size_t n_b,
+                       const float* images, size_t n_images, int F, const int32_t* labels, const int32_t* idx,
+                       const int32_t* shifts, int C, int B, float temperature, float* grads, char* uploads,
+                       size_t upload_pitch);
+
 /* Kardam bookkeeping of CppNNUpdater.update (Server/src/main/java/apps/cppNN/
  * CppNNUpdater.java:463-481, utils/Kardam.java:48-62) for the M
  * picked uploads in one call:
@@ -1350,6 +1386,14 @@ int fleet_rmodel_client_ex_grads_device(fleet_rmodel* m, const int32_t* versions
                                         int B, float temperature, int cost, const float* clip, const float* sigma,
                                         void* d_grads, size_t grad_pitch, void* d_uploads, size_t upload_pitch,
                                         void* stream);
+/* fleet_rgbnet_grads_device with the models taken from the resident rows where they live, the
+ * arguments of fleet_rmodel_client_grads_device: the CIFAR network only (10 or 100 classes, as
+ * the model's layers say; any other network is refused by layer name, as
+ * fleet_rmodel_cifar_test_device refuses it). F >= 3072, grad_pitch >= the vector's length. */
+int fleet_rmodel_rgbnet_grads_device(fleet_rmodel* m, const int32_t* versions, const void* d_images, size_t n_images,
+                                     int F, const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
+                                     float temperature, void* d_grads, size_t grad_pitch, void* d_uploads,
+                                     size_t upload_pitch, void* stream);
 
 /* The offline sampler's state (the CppNNOfflineSampler natives
  * of Server/src/main/c++/cppNN_backend.cpp and the globals they keep). Random
