@@ -20,6 +20,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
+EXPORTS = os.path.join(CSRC, "exports.map")
 LIB = os.path.join(PKG, "libfleetcodec.so")
 JNI_LIB = os.path.join(PKG, "libfleet_native.so")
 ARCH = os.environ.get("FLEET_OFFLOAD_ARCH", "gfx950")
@@ -30,6 +31,7 @@ COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "
 SOURCES = [("kernels.hip", True), ("stream_kernels.hip", True), ("acc_kernels.hip", True), ("model_codec.hip", True),
            ("mledger_kernels.hip", True), ("mledger_table.cpp", False),
            ("fleet_codec.cpp", True), ("launch_plan.cpp", False),  # (file, needs HIP)
+           ("net_entry.cpp", True), ("stream_state.cpp", True), ("kardam_state.cpp", True),
            ("model_state.cpp", True), ("teacher.hip", True), ("sampler_state.cpp", True),
            ("rmodel_kernels.hip", True), ("rmodel_state.cpp", True),
            ("solver_kernels.hip", True), ("eval_kernels.hip", True), ("client_kernels.hip", True),
@@ -58,7 +60,7 @@ def build_codec(force: bool = False, out: str = LIB, defines=()) -> str:
     variant elsewhere (e.g. ab/ for gpu_ab_workloads.sh (r04 tree)) from the same sources."""
     srcs = [os.path.join(CSRC, s) for s, _ in SOURCES]
     deps = srcs + [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + [
-        os.path.join(INCLUDE, "fleet_codec.h")]
+        os.path.join(INCLUDE, "fleet_codec.h"), EXPORTS]
     if not force and not defines and not _newer(out, deps):
         return out
     objdir = os.path.join(PKG, "build") if out == LIB else out + ".objs"
@@ -85,7 +87,8 @@ def build_codec(force: bool = False, out: str = LIB, defines=()) -> str:
     with ThreadPoolExecutor(max_workers=min(len(srcs), 16)) as ex:  # at most 16 compilers at once
         objs = list(ex.map(compile_one, srcs))
     tmp = out + ".tmp"
-    _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, "-o", tmp])
+    # every build, variants included, exports the C-ABI alone (csrc/exports.map says why)
+    _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", f"-Wl,--version-script={EXPORTS}", *objs, "-o", tmp])
     os.replace(tmp, out)
     return out
 

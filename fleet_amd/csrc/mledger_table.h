@@ -1,7 +1,7 @@
 // fleet_amd/csrc/mledger_table.h -- the host bookkeeping of the Kardam model ledger
 // (fleet_mledger_*): Kardam.java's `models` map (worker -> model, Kardam.java:114-125) over
 // a slab of rows that belong to model VERSIONS, not to workers. Plain C++ (no HIP header):
-// fleet_codec.cpp fills the rows and computes the norms the table asks for.
+// kardam_state.cpp fills the rows and computes the norms the table asks for.
 //
 //   version id -> row, worker -> row, a reference count per row. "Storing" a worker's
 //   model (models.put, :124) is a table update and copies nothing; workers at one version

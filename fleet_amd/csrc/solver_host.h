@@ -1,5 +1,5 @@
 // fleet_amd/csrc/solver_host.h -- the host model's way into the stateless solver step
-// (fleet_codec.cpp <-> model_state.cpp).
+// (net_entry.cpp <-> model_state.cpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

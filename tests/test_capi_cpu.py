@@ -19,6 +19,27 @@ def test_library_exports_every_declared_symbol():
     assert F.lib().fleet_version().startswith(b"fleet-mi355x")
 
 
+def test_library_exports_nothing_but_the_header():
+    """The library's defined dynamic symbols are exactly the functions include/fleet_codec.h
+    declares (csrc/exports.map): no helper, no fleet:: internal, no template instantiation
+    that a library loaded beside it in the same process could take over or be taken over by."""
+    import glob
+    import os
+    import shutil
+    import subprocess
+    from fleet_amd.build import HIPCC, LIB
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(HIPCC)))
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or next(
+        iter(sorted(glob.glob(os.path.join(rocm, "**", "llvm-nm"), recursive=True))), None)
+    if nm is None:
+        pytest.skip("neither nm nor llvm-nm is installed")
+    out = subprocess.run([nm, "-D", "--defined-only", LIB], capture_output=True, text=True, check=True).stdout
+    defined = {line.split()[-1].split("@")[0] for line in out.splitlines() if line.strip()}
+    declared = set(F.exported_symbols_from_header())
+    assert len(declared) >= 218
+    assert defined == declared, (sorted(defined - declared)[:20], sorted(declared - defined)[:20])
+
+
 def test_b64_lengths():
     for n in list(range(0, 50)) + [22961, 313867, 1 << 20]:
         L = F.lib().fleet_b64_len(n)

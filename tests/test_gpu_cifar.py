@@ -340,3 +340,28 @@ def test_workspace_is_allocated_once(codec, main):
     cifar.resident_evaluate_device(rm, dx[:50], dl[:50], version=-1)
     assert rm.stats()["device_allocs"] == grown
     rm.close()
+
+
+# -- fleet_cifar_test's refusals, their codes and texts (the body is shared with fleet_evaluate) ------
+
+def _counts_text(who, classes, dw=0, db=0):
+    from host_form_refusals import counts
+    n_w, n_b = counts("cifar_test", classes)
+    return f"{who}: {n_w + dw} weights and {n_b + db} biases, expected {n_w} and {n_b}"
+
+
+@pytest.mark.parametrize("kw,code,text", [
+    (dict(classes=7), F.FLEET_ERR_ARG, "cifar test: 7 classes, the network has 10 or 100"),
+    (dict(classes=0, extra_w=1), F.FLEET_ERR_ARG, "cifar test: 0 classes, the network has 10 or 100"),  # before the counts
+    (dict(extra_w=1), F.FLEET_ERR_ARG, lambda: _counts_text("cifar test", 10, dw=1)),
+    (dict(classes=100, sized_for=100, extra_b=-1), F.FLEET_ERR_ARG, lambda: _counts_text("cifar test", 100, db=-1)),
+    (dict(B=2), F.FLEET_ERR_ARG, "cifar test: 2 images asked of 1"),
+    (dict(idx=[-1]), F.FLEET_ERR_ARG, "image 0: index -1 outside the 1 images"),
+    (dict(idx=[0, 1], B=2), F.FLEET_ERR_ARG, "image 1: index 1 outside the 1 images"),
+    # two checks could fire: the counts come before the picks and the indices
+    (dict(extra_w=1, idx=[1]), F.FLEET_ERR_ARG, lambda: _counts_text("cifar test", 10, dw=1)),
+    (dict(extra_b=1, B=2), F.FLEET_ERR_ARG, lambda: _counts_text("cifar test", 10, db=1)),
+])
+def test_host_form_refusals(codec, kw, code, text):
+    from host_form_refusals import refusal
+    assert refusal(codec, "cifar_test", **kw) == (code, text() if callable(text) else text)

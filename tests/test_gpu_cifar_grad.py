@@ -162,3 +162,40 @@ def test_a_nan_forward_is_reported_and_the_other_clients_stand(codec, world):
     assert e.value.code == F.FLEET_ERR_ARG
     codec.check()  # the word is cleared
     _same(g.cpu().numpy()[[0, 2]], case[-1][[0, 2]], "the sound clients")
+
+
+# -- fleet_rgbnet_grads' refusals, their codes and texts (the body is shared with fleet_client_ex_grads)
+
+def _counts_text(classes, dw=0, db=0):
+    from host_form_refusals import counts
+    n_w, n_b = counts("rgbnet_grads", classes)
+    return f"client gradients: {n_w + dw} weights and {n_b + db} biases, expected {n_w} and {n_b}"
+
+
+def _pitch_text(classes):
+    from host_form_refusals import grad_len
+    up_len = F.b64_len(grad_len("rgbnet_grads", classes))
+    return f"upload pitch {up_len - 1} < {up_len}"
+
+
+@pytest.mark.parametrize("kw,code,text", [
+    (dict(classes=7), F.FLEET_ERR_ARG, "client gradients: 7 classes, the network has 10 or 100"),
+    (dict(classes=0, extra_w=1), F.FLEET_ERR_ARG, "client gradients: 0 classes, the network has 10 or 100"),  # before the counts
+    (dict(extra_w=1), F.FLEET_ERR_ARG, lambda: _counts_text(10, dw=1)),
+    (dict(classes=100, sized_for=100, extra_b=-1), F.FLEET_ERR_ARG, lambda: _counts_text(100, db=-1)),
+    (dict(B=2), F.FLEET_ERR_ARG, "client gradients: 2 images asked of 1"),
+    (dict(idx=[-1]), F.FLEET_ERR_ARG, "sample 0: index -1 outside the 1 images"),
+    (dict(idx=[0, 1], B=2), F.FLEET_ERR_ARG, "sample 1: index 1 outside the 1 images"),
+    (dict(shifts=[0, 2]), F.FLEET_ERR_ARG, "sample 0: shift 2 outside {-1, 0, 1}"),
+    (dict(idx=[0, 0], shifts=[1, -1, -2, 0], B=2), F.FLEET_ERR_ARG, "sample 1: shift -2 outside {-1, 0, 1}"),
+    (dict(upload_pitch=-1), F.FLEET_ERR_CAPACITY, lambda: _pitch_text(10)),  # one below fleet_b64_len
+    # two checks could fire: counts, picks, indices, shifts, pitch, in this order
+    (dict(extra_w=1, idx=[1]), F.FLEET_ERR_ARG, lambda: _counts_text(10, dw=1)),
+    (dict(idx=[1], shifts=[0, 2]), F.FLEET_ERR_ARG, "sample 0: index 1 outside the 1 images"),
+    (dict(shifts=[-2, 0], upload_pitch=16), F.FLEET_ERR_ARG, "sample 0: shift -2 outside {-1, 0, 1}"),
+])
+def test_host_form_refusals(codec, kw, code, text):
+    from host_form_refusals import grad_len, refusal
+    if kw.get("upload_pitch") == -1:
+        kw = dict(kw, upload_pitch=F.b64_len(grad_len("rgbnet_grads", 10)) - 1)
+    assert refusal(codec, "rgbnet_grads", **kw) == (code, text() if callable(text) else text)

@@ -259,3 +259,27 @@ def test_bad_indices_and_a_nan_forward_set_the_error_bit(codec, fresh):
     codec.check()  # the bit was read and cleared
     g = K.client_gradients(codec, w, b, x[:2], lab[:2])  # and the context still works
     assert np.isfinite(g).all()
+
+
+# -- fleet_client_ex_grads' refusals, their codes and texts (the body is shared with fleet_rgbnet_grads)
+
+_UP_LEN = F.b64_len(22961)  # 122460
+
+
+@pytest.mark.parametrize("kw,code,text", [
+    (dict(extra_w=1), F.FLEET_ERR_ARG, "client gradients: 21449 weights and 82 biases, expected 21448 and 82"),
+    (dict(extra_b=-1), F.FLEET_ERR_ARG, "client gradients: 21448 weights and 81 biases, expected 21448 and 82"),
+    (dict(B=2), F.FLEET_ERR_ARG, "client gradients: 2 images asked of 1"),
+    (dict(idx=[-1]), F.FLEET_ERR_ARG, "sample 0: index -1 outside the 1 images"),
+    (dict(idx=[0, 1], B=2), F.FLEET_ERR_ARG, "sample 1: index 1 outside the 1 images"),
+    (dict(shifts=[0, 2]), F.FLEET_ERR_ARG, "sample 0: shift 2 outside {-1, 0, 1}"),
+    (dict(idx=[0, 0], shifts=[1, -1, -2, 0], B=2), F.FLEET_ERR_ARG, "sample 1: shift -2 outside {-1, 0, 1}"),
+    (dict(upload_pitch=_UP_LEN - 1), F.FLEET_ERR_CAPACITY, f"upload pitch {_UP_LEN - 1} < {_UP_LEN}"),
+    # two checks could fire: counts, picks, indices, shifts, pitch, in this order
+    (dict(extra_w=1, idx=[1]), F.FLEET_ERR_ARG, "client gradients: 21449 weights and 82 biases, expected 21448 and 82"),
+    (dict(idx=[1], shifts=[0, 2]), F.FLEET_ERR_ARG, "sample 0: index 1 outside the 1 images"),
+    (dict(shifts=[-2, 0], upload_pitch=16), F.FLEET_ERR_ARG, "sample 0: shift -2 outside {-1, 0, 1}"),
+])
+def test_host_form_refusals(codec, kw, code, text):
+    from host_form_refusals import refusal
+    assert refusal(codec, "client_grads", **kw) == (code, text)

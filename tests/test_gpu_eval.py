@@ -292,3 +292,20 @@ def test_workspace_is_allocated_once(codec, data, dev):
     rm.evaluate_device(dx[:100], dl[:100], version=-1)
     assert rm.stats()["device_allocs"] == grown
     rm.close()
+
+
+# -- fleet_evaluate's refusals, their codes and texts (the body is shared with fleet_cifar_test) ------
+
+@pytest.mark.parametrize("kw,code,text", [
+    (dict(extra_w=1), F.FLEET_ERR_ARG, "evaluate: 21449 weights and 82 biases, expected 21448 and 82"),
+    (dict(extra_b=-1), F.FLEET_ERR_ARG, "evaluate: 21448 weights and 81 biases, expected 21448 and 82"),
+    (dict(B=2), F.FLEET_ERR_ARG, "evaluate: 2 images asked of 1"),
+    (dict(idx=[-1]), F.FLEET_ERR_ARG, "image 0: index -1 outside the 1 images"),
+    (dict(idx=[0, 1], B=2), F.FLEET_ERR_ARG, "image 1: index 1 outside the 1 images"),
+    # two checks could fire: the counts come before the picks and the indices
+    (dict(extra_w=1, idx=[1]), F.FLEET_ERR_ARG, "evaluate: 21449 weights and 82 biases, expected 21448 and 82"),
+    (dict(extra_b=1, B=2), F.FLEET_ERR_ARG, "evaluate: 21448 weights and 83 biases, expected 21448 and 82"),
+])
+def test_host_form_refusals(codec, kw, code, text):
+    from host_form_refusals import refusal
+    assert refusal(codec, "evaluate", **kw) == (code, text)

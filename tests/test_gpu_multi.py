@@ -143,7 +143,7 @@ def test_update_rows_pageable_registration(contexts, oracle, N, pad):
 
 
 def test_entry_points_keep_the_callers_device(contexts, oracle):
-    """Every C-ABI entry restores the calling thread's current device (fleet_codec.cpp
+    """Every C-ABI entry restores the calling thread's current device (host_ctx.h
     DeviceGuard): creating a context on the last visible GPU, a multi-context update,
     device-resident and host-buffer calls leave torch's current device as it was."""
     torch = pytest.importorskip("torch")

@@ -51,7 +51,7 @@ def test_edges_follow_the_constants_in_the_sources():
     assert int(_one(r"constexpr int kMaxDescentSegs = (\d+);", h)) == A.MAX_DESCENT_SEGS
     assert int(_one(r"constexpr int kMaxHeaderSlots = (\d+);", h)) == F.FLEET_MAX_HEADERS == A.FLEET_MAX_HEADERS
     assert int(_one(r"#define FLEET_MAX_HEADERS (\d+)", open(F.HEADER_PATH).read())) == F.FLEET_MAX_HEADERS
-    assert "segs->back().n == fleet::kMaxDescentSegs" in _src("fleet_codec.cpp")
+    assert "segs->back().n == fleet::kMaxDescentSegs" in _src("net_entry.cpp")
     want = {17, 1023, 1024, 1025, 4095, 4096, 2 * 576 + 1}
     for nw in (4, 5, 6, 8, 9):
         want |= {64 * nw - 1, 64 * nw, 64 * nw + 1}
