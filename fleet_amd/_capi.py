@@ -217,6 +217,13 @@ SIGNATURES = {
     "fleet_rgbnet_grads": (i32, [vp, i32, vp, sz, vp, sz, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, vp, vp, sz]),
     "fleet_rmodel_rgbnet_grads_device": (i32, [vp, vp, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, vp, sz, vp, sz,
                                                vp]),
+    "fleet_rgb_dp_grads_device": (i32, [vp, i32, vp, sz, i32, vp, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, vp, vp,
+                                        vp, sz, vp, sz, vp]),
+    "fleet_rgb_dp_grads": (i32, [vp, i32, vp, sz, vp, sz, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, vp, vp, vp, vp,
+                                 sz]),
+    "fleet_rmodel_rgb_dp_grads_device": (i32, [vp, vp, vp, sz, i32, vp, vp, vp, i32, i32, C.c_float, vp, vp, vp, sz, vp,
+                                               sz, vp]),
+    "fleet_rgb_dp_noise": (i32, [vp, sz]),
     "fleet_model_load": (i32, [vp, vp, sz, i32, C.POINTER(vp)]),
     "fleet_model_destroy": (None, [vp]),
     "fleet_model_last_error": (C.c_char_p, [vp]),

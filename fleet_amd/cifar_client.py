@@ -1,6 +1,7 @@
 """The client's gradients on the reference's CIFAR-10/100 network: what
 ``cnn.gradients()`` returns after B ``train_class`` calls, for C clients in one launch sequence,
-with the cross-entropy cost (``fleet_rgbnet_*`` of include/fleet_codec.h).
+with the cross-entropy cost (``fleet_rgbnet_*`` of include/fleet_codec.h), or, for the clients given
+a ``sigma`` > 0, what ``cnn.DPgradients(clip, sigma)`` returns (``fleet_rgb_dp_*``).
 
 * :func:`client_gradients` -- host buffers, one model, on a :class:`~fleet_amd.Codec`;
 * :func:`client_gradients_device` -- tensors where they live, any number of model rows;
@@ -8,18 +9,19 @@ with the cross-entropy cost (``fleet_rgbnet_*`` of include/fleet_codec.h).
   :class:`~fleet_amd.ResidentModel`'s versions, so that a CIFAR model trains, steps
   (``descent_device``) and is evaluated (:func:`fleet_amd.cifar.resident_evaluate_device`)
   without leaving HBM;
-* :func:`grad_len`, :func:`sample_tile`, :class:`chunk_override`.
+* :func:`grad_len`, :func:`sample_tile`, :class:`chunk_override`, :func:`dp_noise_table`.
 
 The shifts are :func:`fleet_amd.client.client_shifts`'s and the upload rows' texts
-:func:`fleet_amd.client.upload_texts` (with ``grad_len(classes)``). ``DPgradients`` and the
-distillation cost exist on the MNIST network only (:mod:`fleet_amd.client`)."""
+:func:`fleet_amd.client.upload_texts` (with ``grad_len(classes)``). ``clip`` and ``sigma`` are
+:mod:`fleet_amd.client`'s keywords, a scalar or one value per client; left at None a call is the
+one it was before they existed. The distillation cost exists on the MNIST network only."""
 from __future__ import annotations
 
 import numpy as np
 
 from ._capi import _ptr, _stream, b64_len, lib
 from .cifar import PIXELS, bias_count, weight_count
-from .client import host_args
+from .client import _fptr, ex_args, host_args
 
 
 def grad_len(classes: int) -> int:
@@ -49,6 +51,23 @@ class chunk_override:
         return False
 
 
+def dp_noise_table(n: int = None) -> np.ndarray:
+    """float64 [n] (default all ``grad_len(100)`` = 331237): the standard-normal draws a DP call
+    adds to the slots of its vector before scaling them by ``clip * sigma``:
+    :func:`fleet_amd.client.dp_noise_table`'s sequence continued, slot i taking draw i."""
+    n = grad_len(100) if n is None else int(n)
+    out = np.empty(n, np.float64)
+    if lib().fleet_rgb_dp_noise(out.ctypes.data, n) != 0:
+        raise ValueError(f"at most {grad_len(100)} draws")
+    return out
+
+
+def _dp(clip, sigma, C):
+    """(clip float32[C], sigma float32[C]) of a call's keywords, or None for the plain call"""
+    ex = ex_args("cross_entropy", clip, sigma, C)
+    return None if ex is None else ex[1:]
+
+
 def _need_classes(classes) -> int:
     classes = int(classes)
     if grad_len(classes) == 0:
@@ -56,10 +75,12 @@ def _need_classes(classes) -> int:
     return classes
 
 
-def client_gradients(codec, classes, w, b, images, labels, idx=None, shifts=None, temperature=2.0, uploads=False):
+def client_gradients(codec, classes, w, b, images, labels, idx=None, shifts=None, temperature=2.0, uploads=False, *,
+                     clip=None, sigma=None):
     """float32 [C, grad_len(classes)]: the rows of :func:`fleet_amd.client.client_gradients` on
     the CIFAR network with weights ``w`` and biases ``b`` (:func:`fleet_amd.cifar.weight_count`,
-    ``bias_count``); images [N, >= 3072] planar. With ``uploads``: (rows, [bytes])."""
+    ``bias_count``); images [N, >= 3072] planar. With ``uploads``: (rows, [bytes]). ``clip`` and
+    ``sigma``: a client with sigma > 0 gets ``cnn.DPgradients(clip, sigma)``'s vector."""
     classes = _need_classes(classes)
     wv = np.ascontiguousarray(w, dtype=np.float32).reshape(-1)
     bv = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
@@ -68,10 +89,15 @@ def client_gradients(codec, classes, w, b, images, labels, idx=None, shifts=None
     grads = np.empty((max(C, 1), n), np.float32)
     pitch = b64_len(n)
     up = np.zeros((max(C, 1), pitch), np.uint8) if uploads else None
-    codec._check(codec._L.fleet_rgbnet_grads(
-        codec._live(), classes, wv.ctypes.data, len(wv), bv.ctypes.data, len(bv), x.ctypes.data, x.shape[0], x.shape[1],
-        lab.ctypes.data, None if ix is None else ix.ctypes.data, None if sh is None else sh.ctypes.data, C, B,
-        float(temperature), grads.ctypes.data, None if up is None else up.ctypes.data, pitch))
+    head = (codec._live(), classes, wv.ctypes.data, len(wv), bv.ctypes.data, len(bv), x.ctypes.data, x.shape[0],
+            x.shape[1], lab.ctypes.data, None if ix is None else ix.ctypes.data, None if sh is None else sh.ctypes.data,
+            C, B, float(temperature))
+    tail = (grads.ctypes.data, None if up is None else up.ctypes.data, pitch)
+    dp = _dp(clip, sigma, C)
+    if dp is None:
+        codec._check(codec._L.fleet_rgbnet_grads(*head, *tail))
+    else:
+        codec._check(codec._L.fleet_rgb_dp_grads(*head, _fptr(dp[0]), _fptr(dp[1]), *tail))
     return (grads, [up[c].tobytes() for c in range(C)]) if uploads else grads
 
 
@@ -116,7 +142,7 @@ def _device_args(classes, images_f32, labels_i32, idx, shifts, C, B, grads, uplo
 
 def client_gradients_device(codec, classes, models_f32, images_f32, labels_i32, idx=None, shifts=None,
                             model_of_client=None, C=None, B=None, temperature=2.0, grads=None, uploads=False,
-                            stream=None):
+                            stream=None, *, clip=None, sigma=None):
     """Device-resident :func:`client_gradients`, the tensors of
     :func:`fleet_amd.client.client_gradients_device`: models [rows, >= weights + biases] (w then
     b per row), images [N, F >= 3072]. Runs on ``stream`` (default: torch's current) and does
@@ -136,15 +162,20 @@ def client_gradients_device(codec, classes, models_f32, images_f32, labels_i32, 
     n_img, F, C, B, grads, up, tail = _device_args(classes, images_f32, labels_i32, idx, shifts, C, B, grads, uploads)
     if model_of_client is not None and model_of_client.numel() != C:
         raise ValueError("model_of_client: one row per client")
-    codec._check(codec._L.fleet_rgbnet_grads_device(
-        codec._live(), classes, models_f32.data_ptr(), models_f32.stride(0), models_f32.shape[0], _ptr(model_of_client),
-        images_f32.data_ptr(), n_img, F, labels_i32.data_ptr(), _ptr(idx), _ptr(shifts), C, B, float(temperature), *tail,
-        _stream(stream)))
+    head = (codec._live(), classes, models_f32.data_ptr(), models_f32.stride(0), models_f32.shape[0],
+            _ptr(model_of_client), images_f32.data_ptr(), n_img, F, labels_i32.data_ptr(), _ptr(idx), _ptr(shifts), C, B,
+            float(temperature))
+    dp = _dp(clip, sigma, C)
+    if dp is None:
+        codec._check(codec._L.fleet_rgbnet_grads_device(*head, *tail, _stream(stream)))
+    else:
+        codec._check(codec._L.fleet_rgb_dp_grads_device(*head, _fptr(dp[0]), _fptr(dp[1]), *tail, _stream(stream)))
     return (grads, up) if up is not None else grads
 
 
 def resident_client_gradients_device(rm, classes, versions, images_f32, labels_i32, idx=None, shifts=None,
-                                     uploads=False, C=None, B=None, temperature=2.0, grads=None, stream=None):
+                                     uploads=False, C=None, B=None, temperature=2.0, grads=None, stream=None, *,
+                                     clip=None, sigma=None):
     """The gradients C clients compute on versions of the resident CIFAR model ``rm`` (of
     ``classes`` classes), where the versions live; ``versions`` as
     :func:`fleet_amd.client.resident_client_gradients_device` takes them. Returns the fp32 rows
@@ -155,7 +186,11 @@ def resident_client_gradients_device(rm, classes, versions, images_f32, labels_i
     if len(vs) != C:
         raise ValueError("one version per client")
     v = np.array([rm._eval_version(x) for x in vs], np.int32)
-    rm._check(rm._L.fleet_rmodel_rgbnet_grads_device(
-        rm._live(), v.ctypes.data, images_f32.data_ptr(), n_img, F, labels_i32.data_ptr(), _ptr(idx), _ptr(shifts), C, B,
-        float(temperature), *tail, _stream(stream)))
+    head = (rm._live(), v.ctypes.data, images_f32.data_ptr(), n_img, F, labels_i32.data_ptr(), _ptr(idx), _ptr(shifts),
+            C, B, float(temperature))
+    dp = _dp(clip, sigma, C)
+    if dp is None:
+        rm._check(rm._L.fleet_rmodel_rgbnet_grads_device(*head, *tail, _stream(stream)))
+    else:
+        rm._check(rm._L.fleet_rmodel_rgb_dp_grads_device(*head, _fptr(dp[0]), _fptr(dp[1]), *tail, _stream(stream)))
     return (grads, up) if up is not None else grads

@@ -60,12 +60,17 @@
 // fully connected inputs. sum_element() adds the records' first part in sample order, fc_step()
 // the outer products.
 //
+// DPgradients(C, sigma): further down, beside the functions it uses (FLEET_RGB_CLIP_ORDER,
+// record_sqsum, dp_sum_element; rgb_dp_host is the plain form, tests/native/check_cifar_dp.cpp
+// drives it).
+//
 // NaN: client_backward.h's rule. A NaN forward makes E NaN: sample_stages reports it and the
 // client's row is unspecified. With a NaN met only in the backward pass, nothing is pinned.
 #pragma once
 #include <stdint.h>
 
 #include "cifar_forward.h"
+#include "client_backward.h"  // clip_scale and noisy: DPgradients' two formulas, network-independent
 
 namespace fleet {
 namespace rgbnet {
@@ -158,6 +163,60 @@ FLEET_TM FcBlock fc_block(int i, int N) {
 FLEET_TM float fc_step(float acc, bool first, float node, float delta) {
   const float p = node * delta;
   return first ? p : acc + p;
+}
+
+// ---- DPgradients(C, sigma) on this network (network.h:1092-1181, as client_backward.h states it
+// for MNIST; clientnet::clip_scale and clientnet::noisy are used as they are).
+//
+// scale_gradients' walk for a batch slot b >= 1: the layers of cppNN_backend.cpp:128-138 (I1, C1,
+// P1, C2, P2, local4, local5, FC2) last to first, per layer the backward link's dW block element
+// by element, then the layer's dbias block; the convolutions' dbias and the pools' dW blocks have
+// size 0. In terms of a sample's record: `fc` >= 0 is fully connected dW block fc_block(fc), which
+// no record holds: its element (b, t) is the bare product node[t] * delta[b], row b outer, t
+// inner; otherwise `len` values at `rec` of the record. 313,850 + 193 (N - 10) squares.
+struct ClipSegment {
+  int fc, rec, len;
+};
+constexpr int kClipSegments = 11;
+#define FLEET_RGB_CLIP_ORDER(N)                                                                               \
+  {{2, 0, 0}, {-1, kR_Bfc, N}, {1, 0, 0}, {-1, kR_B5, kFc5}, {0, 0, 0}, {-1, kR_B4, kFc4}, {-1, kR_BP2, kFcIn}, \
+   {-1, kR_W2, kR_BI1 - kR_W2}, {-1, kR_BP1, kP1Out}, {-1, kR_W1, kR_W2 - kR_W1}, {-1, kR_BI1, kPix}}
+FLEET_TM ClipSegment clip_segment(int i, int N) {  // (selects, not an indexed read: see header())
+  const ClipSegment seg[kClipSegments] = FLEET_RGB_CLIP_ORDER(N);
+  ClipSegment s = seg[0];
+#pragma unroll
+  for (int j = 1; j < kClipSegments; ++j)
+    if (i == j) s = seg[j];
+  return s;
+}
+
+// sqsum += x*x: the rounded square, then the rounded add
+FLEET_TM float clip_add(float sqsum, float x) { return sqsum + x * x; }
+
+// one sample's sqsum from its record, in the walk's order (the plain form of k_rgb_clip's chain)
+FLEET_TM float record_sqsum(const float* rec, int N) {
+  float sqsum = 0.0f;
+  for (int i = 0; i < kClipSegments; ++i) {
+    const ClipSegment s = clip_segment(i, N);
+    if (s.fc < 0) {
+      for (int j = 0; j < s.len; ++j) sqsum = clip_add(sqsum, rec[s.rec + j]);
+      continue;
+    }
+    const FcBlock f = fc_block(s.fc, N);
+    for (int b = 0; b < f.rows; ++b)
+      for (int t = 0; t < f.cols; ++t) sqsum = clip_add(sqsum, rec[f.node + t] * rec[f.delta + b]);
+  }
+  return sqsum;
+}
+
+// sum_element under DPgradients, before the noise: the second loop of scale_gradients scales
+// the dbias blocks of slots >= 1 and no dW (client_backward.h has why), so the convolutions' dW
+// elements are added as they are
+FLEET_TM float dp_sum_element(const float* recs, int64_t pitch, int B, int q, const float* scale) {
+  if (q < kR_BI1) return sum_element(recs, pitch, B, q);
+  float a = recs[q];
+  for (int k = 1; k < B; ++k) a = a + recs[(int64_t)k * pitch + q] * scale[k];
+  return a;
 }
 
 constexpr int kFcCols = 8;  // columns of a fully connected layer staged at a time in the forward
@@ -393,6 +452,29 @@ inline int rgb_grads_host(int N, const float* w, const float* b, const float* im
       }
   }
   return blown;
+}
+
+// DPgradients(clip, sigma), sigma > 0, from the records rgb_grads_host left: z [grad_len(N)] the
+// draws (clientnet::dp_noise_draws), out [grad_len(N)] is overwritten, scale: scratch [B]
+inline void rgb_dp_host(int N, const float* recs, int B, float clip, float sigma, const double* z, float* scale,
+                        float* out) {
+  const int64_t pitch = record_len(N);
+  const double s = (double)(clip * sigma);
+  for (int k = 0; k < B; ++k) scale[k] = k ? clientnet::clip_scale(record_sqsum(recs + k * pitch, N), clip) : 1.0f;
+  for (int q = 0; q < summed_len(N); ++q) {
+    const int pos = summed_pos(q, N);
+    out[pos] = clientnet::noisy(dp_sum_element(recs, pitch, B, q, scale), z[pos], s);
+  }
+  for (int i = 0; i < kFcBlocks; ++i) {
+    const FcBlock f = fc_block(i, N);
+    for (int r = 0; r < f.rows; ++r)
+      for (int t = 0; t < f.cols; ++t) {
+        float a = 0.0f;
+        for (int k = 0; k < B; ++k) a = fc_step(a, k == 0, recs[k * pitch + f.node + t], recs[k * pitch + f.delta + r]);
+        out[f.pos + r * f.cols + t] = clientnet::noisy(a, z[f.pos + r * f.cols + t], s);
+      }
+  }
+  for (int i = 0; i < kHeaders; ++i) out[header(i, N).pos] = header(i, N).value;
 }
 #endif
 

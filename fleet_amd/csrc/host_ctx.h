@@ -76,6 +76,9 @@ struct FLEET_MEM_LOCAL fleet_ctx {
   // standard-normal draws, made on the host on the first DP call and resident from then on
   fleet::DevBuf<float> d_client_dp;
   fleet::DevBuf<double> d_dp_z;
+  // the same table continued to the CIFAR-100 vector's 331,237 draws (2.65 MB), uploaded on
+  // the first DP call on the CIFAR network
+  fleet::DevBuf<double> d_rgb_z;
 };
 
 namespace fleet {

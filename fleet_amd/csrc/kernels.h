@@ -244,6 +244,16 @@ hipError_t launch_rgbnet_grads(int classes, const float* models, int64_t model_p
                                const int32_t* labels, const int32_t* idx, const int32_t* shift, int C, int B, int chunk,
                                float temperature, float* workspace, float* grads, int64_t grad_pitch, int* err,
                                hipStream_t s);
+// the same and, where d_clip is given, DPgradients for the clients with sigma > 0:
+// launch_client_grads_ex's DP arguments, d_z the rgbnet_grad_len(classes) draws of client_dp_noise,
+// scale: rgbnet_scale_bytes(chunk, B) on the device
+hipError_t launch_rgbnet_grads_dp(int classes, const float* models, int64_t model_pitch, int n_models,
+                                  const int32_t* model_of_client, const float* images, int64_t n_images, int F,
+                                  const int32_t* labels, const int32_t* idx, const int32_t* shift, int C, int B,
+                                  int chunk, float temperature, const float* d_clip, const float* d_sigma,
+                                  const uint8_t* dp_of_client, const double* d_z, float* scale, float* workspace,
+                                  float* grads, int64_t grad_pitch, int* err, hipStream_t s);
+size_t rgbnet_scale_bytes(int chunk, int B);
 int64_t rgbnet_grad_len(int classes);  // 313867, 331237; 0 for other classes
 int rgbnet_sample_tile();              // samples k_rgb_fc_sum stages at a time
 size_t rgbnet_workspace_bytes(int classes, int chunk, int B);

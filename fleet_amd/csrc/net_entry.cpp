@@ -715,21 +715,63 @@ int fleet_rgbnet_set_chunk(int max_clients) { return fleet::rgbnet_set_chunk(max
 
 namespace {
 
-// both forms, the lock held and the device set: the records' workspace (the one of
-// fleet_client_grads_device, under its rule), the launches per chunk of clients, the encode
+// the draws of a DP vector on this network: fleet_client_dp_noise's table continued to the
+// CIFAR-100 vector's length by the same host code, made once per process and kept
+const std::vector<double>& rgb_dp_table() {
+  static const std::vector<double> z = [] {
+    std::vector<double> t(fleet_rgbnet_grad_len(100));
+    fleet::client_dp_noise(t.data(), t.size());
+    return t;
+  }();
+  return z;
+}
+
+// every form, the lock held and the device set: the records' workspace (the one of
+// fleet_client_grads_device, under its rule), the launches per chunk of clients, the encode.
+// clip, sigma: host [C] or both NULL (checked by client_ex_args_ok).
 int rgbnet_grads_locked(fleet_ctx* c, int classes, const void* d_models, size_t model_pitch, int n_models,
                         const void* d_model_of_client, const void* d_images, size_t n_images, int F,
                         const void* d_labels, const void* d_idx, const void* d_shift, int C, int B, float temperature,
-                        void* d_grads, size_t grad_pitch, void* d_uploads, size_t upload_pitch, hipStream_t s) {
+                        const float* clip, const float* sigma, void* d_grads, size_t grad_pitch, void* d_uploads,
+                        size_t upload_pitch, hipStream_t s) {
   const int chunk = fleet::rgbnet_chunk(classes, C, B);
-  const size_t need = fleet::rgbnet_workspace_bytes(classes, chunk, B);
+  const size_t recs_bytes = fleet::rgbnet_workspace_bytes(classes, chunk, B);
+  std::vector<uint8_t> dp_of_client;
+  bool dp = false;
+  if (sigma) {
+    dp_of_client.resize((size_t)C);
+    for (int i = 0; i < C; ++i) dp |= (dp_of_client[(size_t)i] = sigma[i] > 0.0f) != 0;
+  }
+  // the scales lie behind the records, with or without DP, so a DP call grows nothing a plain one made
+  const size_t need = recs_bytes + fleet::rgbnet_scale_bytes(chunk, B);
   const hipError_t ew = c->d_client_ws.grow_exact(need, 64, &c->retired);
   if (ew != hipSuccess) return nomem(c, "hipMalloc", need, ew);
-  HIP_TRY(c, fleet::launch_rgbnet_grads(classes, (const float*)d_models, (int64_t)model_pitch, n_models,
-                                        (const int32_t*)d_model_of_client, (const float*)d_images, (int64_t)n_images, F,
-                                        (const int32_t*)d_labels, (const int32_t*)d_idx, (const int32_t*)d_shift, C, B,
-                                        chunk, temperature, (float*)c->d_client_ws.get(), (float*)d_grads,
-                                        (int64_t)grad_pitch, c->d_dev_err, s));
+  if (dp) {
+    if (!c->d_rgb_z) {  // once per context
+      const std::vector<double>& z = rgb_dp_table();
+      const hipError_t e = c->d_rgb_z.alloc(z.size());
+      if (e != hipSuccess) return nomem(c, "hipMalloc", sizeof(double) * z.size(), e);
+      const hipError_t e2 = hipMemcpy(c->d_rgb_z, z.data(), sizeof(double) * z.size(), hipMemcpyHostToDevice);
+      if (e2 != hipSuccess) {
+        c->d_rgb_z.reset();
+        return fail(c, FLEET_ERR_HIP, "the DP noise table: %s", hipGetErrorString(e2));
+      }
+    }
+    const hipError_t ed = c->d_client_dp.grow_exact(2 * (size_t)C, 0, &c->retired);
+    if (ed != hipSuccess) return nomem(c, "hipMalloc", 8 * (size_t)C, ed);
+    // pageable sources: the copies have left clip and sigma when the call returns
+    HIP_TRY(c, hipMemcpyAsync(c->d_client_dp, clip, sizeof(float) * (size_t)C, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->d_client_dp + C, sigma, sizeof(float) * (size_t)C, hipMemcpyHostToDevice, s));
+  }
+  HIP_TRY(c, fleet::launch_rgbnet_grads_dp(classes, (const float*)d_models, (int64_t)model_pitch, n_models,
+                                           (const int32_t*)d_model_of_client, (const float*)d_images,
+                                           (int64_t)n_images, F, (const int32_t*)d_labels, (const int32_t*)d_idx,
+                                           (const int32_t*)d_shift, C, B, chunk, temperature,
+                                           dp ? c->d_client_dp : nullptr, dp ? c->d_client_dp + C : nullptr,
+                                           dp ? dp_of_client.data() : nullptr, dp ? c->d_rgb_z : nullptr,
+                                           dp ? (float*)(c->d_client_ws + recs_bytes) : nullptr,
+                                           (float*)c->d_client_ws.get(), (float*)d_grads, (int64_t)grad_pitch,
+                                           c->d_dev_err, s));
   if (d_uploads)
     HIP_TRY(c, fleet::launch_encode_f32((const float*)d_grads, (int64_t)fleet_rgbnet_grad_len(classes), grad_pitch, C,
                                         (uint8_t*)d_uploads, upload_pitch, s));
@@ -738,40 +780,70 @@ int rgbnet_grads_locked(fleet_ctx* c, int classes, const void* d_models, size_t 
 
 }  // namespace
 
-int fleet_rgbnet_grads_device(fleet_ctx* c, int classes, const void* d_models, size_t model_pitch, int n_models,
+int fleet_rgb_dp_noise(double* out, size_t n) {
+  if (!out || n > fleet_rgbnet_grad_len(100)) return FLEET_ERR_ARG;
+  std::memcpy(out, rgb_dp_table().data(), sizeof(double) * n);
+  return FLEET_OK;
+}
+
+int fleet_rgb_dp_grads_device(fleet_ctx* c, int classes, const void* d_models, size_t model_pitch, int n_models,
                               const void* d_model_of_client, const void* d_images, size_t n_images, int F,
                               const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
-                              float temperature, void* d_grads, size_t grad_pitch, void* d_uploads,
-                              size_t upload_pitch, void* stream) {
+                              float temperature, const float* clip, const float* sigma, void* d_grads,
+                              size_t grad_pitch, void* d_uploads, size_t upload_pitch, void* stream) {
   const size_t n_up = fleet_rgbnet_grad_len(classes);
   if (!c || !n_up || !d_models || !d_images || !d_labels || !d_grads || C <= 0 || B <= 0 || F < fleet::cifarnet::kPix ||
       n_models <= 0 || n_images == 0 || model_pitch < fleet_cifar_weight_count(classes) + fleet_cifar_bias_count(classes) ||
       grad_pitch < n_up || (size_t)C * (size_t)B > (size_t)INT32_MAX || (!d_idx && (size_t)C * (size_t)B > n_images))
     return FLEET_ERR_ARG;
+  if (!client_ex_args_ok(FLEET_COST_CROSS_ENTROPY, clip, sigma, C))
+    return fail(c, FLEET_ERR_ARG, "client gradients: clip and sigma both or neither, sigma >= 0 and finite, clip > 0 "
+                                  "and finite where sigma > 0");
   if (d_uploads && (upload_pitch % 16 != 0 || upload_pitch < 16 * groups_of(n_up)))
     return fail(c, FLEET_ERR_ARG, "bad upload pitch");
   std::lock_guard<std::mutex> lk(c->mu);
   DEVICE_SCOPE(c);
   return rgbnet_grads_locked(c, classes, d_models, model_pitch, n_models, d_model_of_client, d_images, n_images, F,
-                             d_labels, d_idx, d_shift, C, B, temperature, d_grads, grad_pitch, d_uploads, upload_pitch,
-                             pick(c, stream));
+                             d_labels, d_idx, d_shift, C, B, temperature, clip, sigma, d_grads, grad_pitch, d_uploads,
+                             upload_pitch, pick(c, stream));
+}
+
+int fleet_rgbnet_grads_device(fleet_ctx* c, int classes, const void* d_models, size_t model_pitch, int n_models,
+                              const void* d_model_of_client, const void* d_images, size_t n_images, int F,
+                              const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
+                              float temperature, void* d_grads, size_t grad_pitch, void* d_uploads,
+                              size_t upload_pitch, void* stream) {
+  return fleet_rgb_dp_grads_device(c, classes, d_models, model_pitch, n_models, d_model_of_client, d_images, n_images, F,
+                                   d_labels, d_idx, d_shift, C, B, temperature, nullptr, nullptr, d_grads, grad_pitch,
+                                   d_uploads, upload_pitch, stream);
+}
+
+int fleet_rgb_dp_grads(fleet_ctx* c, int classes, const float* w, size_t n_w, const float* b, size_t n_b,
+                       const float* images, size_t n_images, int F, const int32_t* labels, const int32_t* idx,
+                       const int32_t* shifts, int C, int B, float temperature, const float* clip, const float* sigma,
+                       float* grads, char* uploads, size_t upload_pitch) {
+  if (!c || !w || !b || !images || !labels || !grads || C <= 0 || B <= 0 || F < fleet::cifarnet::kPix || n_images == 0)
+    return FLEET_ERR_ARG;
+  if (!fleet::cifarnet::classes_ok(classes))
+    return fail(c, FLEET_ERR_ARG, "client gradients: %d classes, the network has 10 or 100", classes);
+  if (!client_ex_args_ok(FLEET_COST_CROSS_ENTROPY, clip, sigma, C))
+    return fail(c, FLEET_ERR_ARG, "client gradients: clip and sigma both or neither, sigma >= 0 and finite, clip > 0 "
+                                  "and finite where sigma > 0");
+  return client_grads_host(
+      c, w, n_w, fleet_cifar_weight_count(classes), b, n_b, fleet_cifar_bias_count(classes), images, n_images, F, labels,
+      idx, shifts, C, B, fleet_rgbnet_grad_len(classes), grads, uploads, upload_pitch, [=](const GradArgs& a) {
+        return rgbnet_grads_locked(c, classes, a.models, a.model_pitch, 1, nullptr, a.images, a.rows, F, a.labels, a.idx,
+                                   a.shift, C, B, temperature, clip, sigma, a.grads, fleet_rgbnet_grad_len(classes),
+                                   a.uploads, a.upload_pitch, c->stream);
+      });
 }
 
 int fleet_rgbnet_grads(fleet_ctx* c, int classes, const float* w, size_t n_w, const float* b, size_t n_b,
                        const float* images, size_t n_images, int F, const int32_t* labels, const int32_t* idx,
                        const int32_t* shifts, int C, int B, float temperature, float* grads, char* uploads,
                        size_t upload_pitch) {
-  if (!c || !w || !b || !images || !labels || !grads || C <= 0 || B <= 0 || F < fleet::cifarnet::kPix || n_images == 0)
-    return FLEET_ERR_ARG;
-  if (!fleet::cifarnet::classes_ok(classes))
-    return fail(c, FLEET_ERR_ARG, "client gradients: %d classes, the network has 10 or 100", classes);
-  return client_grads_host(
-      c, w, n_w, fleet_cifar_weight_count(classes), b, n_b, fleet_cifar_bias_count(classes), images, n_images, F, labels,
-      idx, shifts, C, B, fleet_rgbnet_grad_len(classes), grads, uploads, upload_pitch, [=](const GradArgs& a) {
-        return rgbnet_grads_locked(c, classes, a.models, a.model_pitch, 1, nullptr, a.images, a.rows, F, a.labels, a.idx,
-                                   a.shift, C, B, temperature, a.grads, fleet_rgbnet_grad_len(classes), a.uploads,
-                                   a.upload_pitch, c->stream);
-      });
+  return fleet_rgb_dp_grads(c, classes, w, n_w, b, n_b, images, n_images, F, labels, idx, shifts, C, B, temperature,
+                            nullptr, nullptr, grads, uploads, upload_pitch);
 }
 
 int fleet_model_params(fleet_ctx* c, const float* weights, size_t n_weights, const float* biases, size_t n_biases,

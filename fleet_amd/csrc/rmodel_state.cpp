@@ -862,6 +862,14 @@ int fleet_rmodel_rgbnet_grads_device(fleet_rmodel* m, const int32_t* versions, c
                                      int F, const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
                                      float temperature, void* d_grads, size_t grad_pitch, void* d_uploads,
                                      size_t upload_pitch, void* stream) {
+  return fleet_rmodel_rgb_dp_grads_device(m, versions, d_images, n_images, F, d_labels, d_idx, d_shift, C, B, temperature,
+                                          nullptr, nullptr, d_grads, grad_pitch, d_uploads, upload_pitch, stream);
+}
+
+int fleet_rmodel_rgb_dp_grads_device(fleet_rmodel* m, const int32_t* versions, const void* d_images, size_t n_images,
+                                     int F, const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
+                                     float temperature, const float* clip, const float* sigma, void* d_grads,
+                                     size_t grad_pitch, void* d_uploads, size_t upload_pitch, void* stream) {
   if (!m) return FLEET_ERR_ARG;
   std::lock_guard<std::mutex> lk(m->mu);
   RM_SCOPE(m);
@@ -886,10 +894,10 @@ int fleet_rmodel_rgbnet_grads_device(fleet_rmodel* m, const int32_t* versions, c
   }
   // pageable source: the copy has left `rows` when the call returns
   RM_HIP(m, hipMemcpyAsync(m->d_client_rows, rows.data(), 4 * (size_t)C, hipMemcpyHostToDevice, s));
-  if ((rc = fleet_rgbnet_grads_device(m->ctx, classes, m->state, m->stride, n_rows, m->d_client_rows, d_images, n_images,
-                                      F, d_labels, d_idx, d_shift, C, B, temperature, d_grads, grad_pitch, d_uploads,
-                                      upload_pitch, (void*)s)))
-    return rfail(m, rc, "client gradients: %s", rc == FLEET_ERR_ARG ? "C*B images without indices, a row pitch of the vector's length, an upload pitch of whole groups"
+  if ((rc = fleet_rgb_dp_grads_device(m->ctx, classes, m->state, m->stride, n_rows, m->d_client_rows, d_images, n_images,
+                                      F, d_labels, d_idx, d_shift, C, B, temperature, clip, sigma, d_grads, grad_pitch,
+                                      d_uploads, upload_pitch, (void*)s)))
+    return rfail(m, rc, "client gradients: %s", rc == FLEET_ERR_ARG ? "C*B images without indices, a row pitch of the vector's length, an upload pitch of whole groups, DP parameters in range"
                                                                      : fleet_last_error(m->ctx));
   return FLEET_OK;
 }

@@ -1060,8 +1060,8 @@ int fleet_client_dp_noise(double* out, size_t n);
  * order. fleet_amd/csrc/cifar_backward.h restates every step with the reference's lines, and
  * the device computes that restatement's bits; no vector recorded from the reference's own
  * network class stands behind this path yet. The NaN rule is the one above. Models: w then b
- * in the CIFAR test()'s layout. Not covered: DPgradients and the distillation cost on this
- * network. */
+ * in the CIFAR test()'s layout. DPgradients: the fleet_rgb_dp_* calls below. Not covered: the
+ * distillation cost on this network. */
 size_t fleet_rgbnet_grad_len(int classes);
 /* samples whose nodes and deltas the fully connected dW kernel stages at a time (tests: B at
  * and just above it) */
@@ -1083,6 +1083,27 @@ int fleet_rgbnet_grads(fleet_ctx* ctx, int classes, const float* w, size_t n_w, 
                        const float* images, size_t n_images, int F, const int32_t* labels, const int32_t* idx,
                        const int32_t* shifts, int C, int B, float temperature, float* grads, char* uploads,
                        size_t upload_pitch);
+/* DPgradients on that network: the two calls above with clip and sigma after temperature, host
+ * float[C], both NULL for no DP (the call above, the same launches), under the rules and the
+ * refusals of fleet_client_ex_grads. Client c with sigma[c] > 0 gets what
+ * cnn.DPgradients(clip[c], sigma[c]) returns; scale_gradients' walk here is dW FC2, dbias FC2,
+ * dW local5, dbias local5, dW local4, dbias local4, dbias P2, dW C2, dbias P1, dW C1, dbias I1
+ * (313850 or 331220 squares in one binary32 running sum per sample; a fully connected dW
+ * element is the rounded product node[t] * delta[b], row b outer). A client with sigma[c] == 0
+ * gets exactly the row of the call above. */
+int fleet_rgb_dp_grads_device(fleet_ctx* ctx, int classes, const void* d_models, size_t model_pitch, int n_models,
+                              const void* d_model_of_client, const void* d_images, size_t n_images, int F,
+                              const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
+                              float temperature, const float* clip, const float* sigma, void* d_grads,
+                              size_t grad_pitch, void* d_uploads, size_t upload_pitch, void* stream);
+int fleet_rgb_dp_grads(fleet_ctx* ctx, int classes, const float* w, size_t n_w, const float* b, size_t n_b,
+                       const float* images, size_t n_images, int F, const int32_t* labels, const int32_t* idx,
+                       const int32_t* shifts, int C, int B, float temperature, const float* clip, const float* sigma,
+                       float* grads, char* uploads, size_t upload_pitch);
+/* host only: the first n (<= 331237) draws of fleet_client_dp_noise's sequence, the table the
+ * calls above add from (slot i of the vector takes draw i). Made once per process; a context
+ * uploads it on its first DP call on this network (2.65 MB resident). */
+int fleet_rgb_dp_noise(double* out, size_t n);
 
 /* Kardam bookkeeping of CppNNUpdater.update (Server/src/main/java/apps/cppNN/
  * CppNNUpdater.java:463-481, utils/Kardam.java:48-62) for the M
@@ -1394,6 +1415,12 @@ int fleet_rmodel_rgbnet_grads_device(fleet_rmodel* m, const int32_t* versions, c
                                      int F, const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
                                      float temperature, void* d_grads, size_t grad_pitch, void* d_uploads,
                                      size_t upload_pitch, void* stream);
+/* fleet_rgb_dp_grads_device with the models taken from the resident rows: the call above with
+ * clip and sigma after temperature */
+int fleet_rmodel_rgb_dp_grads_device(fleet_rmodel* m, const int32_t* versions, const void* d_images, size_t n_images,
+                                     int F, const void* d_labels, const void* d_idx, const void* d_shift, int C, int B,
+                                     float temperature, const float* clip, const float* sigma, void* d_grads,
+                                     size_t grad_pitch, void* d_uploads, size_t upload_pitch, void* stream);
 
 /* The offline sampler's state (the CppNNOfflineSampler natives
  * of Server/src/main/c++/cppNN_backend.cpp and the globals they keep). Random
